@@ -15,10 +15,18 @@ steps are a separate call.  Inputs are synthetic (make_synthetic-shaped: X ~ N(0
 labels ~ Bernoulli(sigmoid(5 sum x))), parameters at the reference init
 (mean = 0, sd = softplus^-1(1e-6), corr = 0), N_data = 800, v = 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
          (a bare `bench.py --gpus N` starts that itself, as a child process)
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and no more: set-up, the W warm-up
+steps, the K timed steps, the result line.  --dump-outputs DIR writes what the
+timed call left its caller after its last step (params, adam_m, adam_v, the
+per-step negative ELBO) as DIR/<name>.npy.  --full adds every side
+measurement: the cold call, the per-phase split and the rooflines read from
+it, the C4 / C2 / C5 / trainer lines, the CPU baselines, and at N > 1 the
+weak-scaled shards, C4 on one GPU and the data-parallel alternative.
 """
 import argparse
 import ctypes
@@ -324,13 +332,15 @@ def sharded_steps(rt, loop, u, z, w, params, m, v, seed, k0, n, parts=None, ev=N
              overlap=overlap)
 
 
-def sharded_timed(rt, steps, warmup, layers, S, M, ev_every=5, seed=20251015, overlap=False):
+def sharded_timed(rt, steps, warmup, layers, S, M, ev_every=5, seed=20251015, overlap=False,
+                  phases=True):
     """K timed sharded inner steps of fn2 at (S, M) after W warm-up steps
     (ShardedInnerLoop.run: rows of L (whole 64-row bands) x samples sharded,
     two all_to_alls per step), the timed call continuing the warm-up's Philox
     stream and Adam steps.  Returns (elapsed s, the (warmup + steps) x 2 [NLL,
     KL] parts of this rank, per-phase ms from a separate 50-step call after the
-    timed one, loop)."""
+    timed one (phases=False: no such call, None), loop, this rank's (params,
+    m, v) as the timed call left them)."""
     loop = make_sharded_loop("fullcov", layers, S, M, rt)
     u, z, w = fn2_inputs(layers, M, rt.dev, 0)
     params = reference_init_params(layers, rt.dev)
@@ -340,6 +350,8 @@ def sharded_timed(rt, steps, warmup, layers, S, M, ev_every=5, seed=20251015, ov
     sharded_steps(rt, loop, u, z, w, params, m, v, seed, 0, warmup, parts, overlap=overlap)
     elapsed = rt.timed(lambda: sharded_steps(rt, loop, u, z, w, params, m, v, seed,
                                              warmup, steps, parts, overlap=overlap))
+    if not phases:
+        return elapsed, parts, None, loop, (params, m, v)
     # the per-phase split: HIP events between the launches of a separate call
     # (outside the timed region), every ev_every-th of 50 steps
     nph = 50
@@ -354,7 +366,7 @@ def sharded_timed(rt, steps, warmup, layers, S, M, ev_every=5, seed=20251015, ov
         ph["update+sample"].append(e[1].elapsed_time(e[2]))
     avg_ms = {k: sum(x) / max(len(x), 1) for k, x in ph.items()}
     avg_ms["samples"] = len(ev)
-    return elapsed, parts, avg_ms, loop
+    return elapsed, parts, avg_ms, loop, (params, m, v)
 
 
 def weak_line(rt, steps, warmup, layers=LAYERS, s_per_gpu=S_PER_GPU, M=M):
@@ -362,7 +374,7 @@ def weak_line(rt, steps, warmup, layers=LAYERS, s_per_gpu=S_PER_GPU, M=M):
     sharded step.  inner-steps/s of the whole job (one step = all S samples;
     not multiplied by N)."""
     S = s_per_gpu * rt.world
-    elapsed, parts, _, loop = sharded_timed(rt, steps, warmup, layers, S, M)
+    elapsed, parts, _, loop, _ = sharded_timed(rt, steps, warmup, layers, S, M, phases=False)
     negelbo = loop.reduce_elbo(parts)
     return {"config": f"C3 shards x {rt.world}: fn2 full-cov S={S} ({s_per_gpu} per GPU), "
                       f"M={M} (weak scaling)",
@@ -630,9 +642,10 @@ def headline_world1(rt, args, prep=None):
     does the full work of K steps -- each a network step with the next draw
     and an update with the next sample, the last one writing the packed
     arrays -- and its numbers are those of one call of W + K steps, bit for
-    bit (tests/test_hip_loop_resident.py).  Per-phase HIP
-    events (PSVI_DBG_LOOP_TIMING) on every 10th step of one more call after
-    the timed one."""
+    bit (tests/test_hip_loop_resident.py).  With --full: the same K steps as
+    a cold call, and per-phase HIP events (PSVI_DBG_LOOP_TIMING) on every
+    10th step of one more call after the timed one (a plain run: None for
+    both).  The last element is what the timed call left its caller."""
     dev = rt.dev
     prep = prep or headline_prep(rt, args)
     plan, u, z, w, p_init = prep["plan"], prep["u"], prep["z"], prep["w"], prep["p_init"]
@@ -658,6 +671,9 @@ def headline_world1(rt, args, prep=None):
                                                step0=args.warmup + 1, seed=20251015,
                                                offset=args.warmup * eps_stride,
                                                elbo_out=elbo_t, ws=ws))
+    state = dict(params=params, adam_m=m, adam_v=v, neg_elbo=elbo_t)
+    if not getattr(args, "full", False):
+        return elapsed, elbo_t, None, plan.param_count, None, state
     # the same K steps as a cold call (fresh Adam state and packed arrays: the
     # packed -> tiled conversion, the first draw and sample inside), as every
     # hyper_step / nested_step inner loop runs: the per-call fixed cost the
@@ -696,7 +712,36 @@ def headline_world1(rt, args, prep=None):
         raise RuntimeError("psvi_debug_loop_timing failed")
     lib.psvi_debug_set(8, 0)
     avg_ms = {"exchange+net": tm[0] * 1e-3, "update": tm[1] * 1e-3, "samples": int(tm[2])}
-    return elapsed, elbo_t, avg_ms, plan.param_count, cold
+    return elapsed, elbo_t, avg_ms, plan.param_count, cold, state
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: each array as path/<name>.npy, float32 or float64 as
+    computed, flattened.  All of them whole where they fit in 64 MB together;
+    otherwise every array larger than its equal share of that is cut to a
+    fixed sample of its entries (a seeded choice of indices, ascending: the
+    same entries in every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    budget = DUMP_LIMIT_BYTES - 1024 * len(arrs)  # the .npy headers
+    if sum(a.nbytes for a in arrs.values()) > budget:
+        share = budget // len(arrs)
+        rng = np.random.default_rng(seed)
+        for k in sorted(arrs):
+            a = arrs[k]
+            if a.nbytes > share:
+                idx = np.sort(rng.choice(a.size, share // a.itemsize, replace=False))
+                arrs[k] = a[idx]
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def rows_fraction(loop, layers):
@@ -709,59 +754,10 @@ def rows_fraction(loop, layers):
     return nnz_own / sum((k - 1) * (k - 2) // 2 for k in n)
 
 
-def run(rt, args, shapes=None):
-    """Everything after the process set-up; returns the JSON line's dict on
-    rank 0 (None on the other ranks).  shapes: smaller stand-ins for the
-    configs (CPU rehearsals of the N > 1 control flow under gloo,
-    tests/test_bench_gloo.py); None = the BASELINE configs.
-
-    N = 1: the headline is C3 (BASELINE configs[2]: fn2 S = 128, M = 100 on one
-    GPU), with C4 on one GPU as the side line `c4_1gpu`.  N > 1: the headline
-    is C4 (configs[3]: S = 1024, M = 200 over the N GPUs, strong scaling; one
-    step is one step of all 1024 samples), with C4 on one GPU of the same run
-    as `c4_1gpu` and the speed-up over it, and the weak-scaled C3 shards as
-    the side line `weak`."""
-    sh = dict(layers=LAYERS, s_per_gpu=S_PER_GPU, M=M, c4={}, c5={})
-    sh.update(shapes or {})
-    world, rank = rt.world, rt.rank
-    c4sh = dict(layers=LAYERS, S=C4["S"], M=C4["M"])
-    c4sh.update({k: sh["c4"][k] for k in ("layers", "S", "M") if k in sh["c4"]})
-    # N = 1: the C4 line first, so that the headline's one short timed call
-    # (K = 20 steps, ~1.4 ms, in the driver's run) starts on a GPU at its
-    # working clocks rather than straight after process start-up
-    c4 = None
-    schedules = None
-    if world == 1:
-        prep = headline_prep(rt, args) if shapes is None else None
-        if not args.no_c4:
-            log("C4 line")
-            c4 = c4_timings(rt, **sh["c4"])
-        elapsed, parts, avg_ms, pcount, cold = headline_world1(rt, args, prep)
-        elbo = parts
-        S, Mh, layers = sh["s_per_gpu"], sh["M"], sh["layers"]
-    else:
-        S, Mh, layers = c4sh["S"], c4sh["M"], c4sh["layers"]
-        # two complete schedules of the same step (ShardedInnerLoop.run): the
-        # exchanges in series with the network, and overlapped with it (two
-        # sample halves, each its own x -> network -> G chain, the second on a
-        # side stream); the headline is the faster (the same pick on every
-        # rank: the times are maxima over ranks), both are reported
-        sched = {}
-        for ov in (False, True):
-            log(f"C4 headline over {world} ranks ({'overlapped' if ov else 'plain'} exchanges)")
-            r_ = sharded_timed(rt, args.steps, args.warmup, layers, S, Mh, overlap=ov)
-            sched["overlap" if ov else "plain"] = r_
-        pick = min(sched, key=lambda k: sched[k][0])
-        elapsed, parts, avg_ms, loop = sched[pick]
-        schedules = {k: {"inner_steps_per_s": round(args.steps / v_[0], 2),
-                         "ms_per_step": round(v_[0] / args.steps * 1e3, 4)} for k, v_ in sched.items()}
-        schedules["headline"] = pick
-        elbo = loop.reduce_elbo(parts)
-        pcount = loop.plan.param_count
-        cold = None
-    finite = bool(torch.isfinite(elbo).all().item())
-    steps_per_s = args.steps / elapsed
-    value = steps_per_s  # one step = one inner step of ALL S samples, on every N
+def kernel_roofline(world, S, layers, avg_ms, loop=None):
+    """The dominant kernel (N > 1: phase) of the headline step against its
+    roofline, from the per-phase times avg_ms of the --full run's separate
+    event-bracketed call (headline_world1 / sharded_timed)."""
     if world == 1:
         upd_s = max(avg_ms["update"], 1e-9) * 1e-3
         # dominant kernel: the update with the fused next-step sample (its
@@ -812,6 +808,77 @@ def run(rt, args, shapes=None):
                                              / BF16_MFMA_PEAK_TFLOPS, 4)) if world == 1 else None,
                     kernels={k: {kk: round(vv, 2) for kk, vv in d.items()}
                              for k, d in kernels.items()})
+    return roofline
+
+
+def run(rt, args, shapes=None):
+    """Everything after the process set-up; returns the JSON line's dict on
+    rank 0 (None on the other ranks).  shapes: smaller stand-ins for the
+    configs (CPU rehearsals of the N > 1 control flow under gloo,
+    tests/test_bench_gloo.py); None = the BASELINE configs.
+
+    N = 1: the headline is C3 (BASELINE configs[2]: fn2 S = 128, M = 100 on one
+    GPU), with C4 on one GPU as the side line `c4_1gpu`.  N > 1: the headline
+    is C4 (configs[3]: S = 1024, M = 200 over the N GPUs, strong scaling; one
+    step is one step of all 1024 samples), with C4 on one GPU of the same run
+    as `c4_1gpu` and the speed-up over it, and the weak-scaled C3 shards as
+    the side line `weak`.  The side lines, the cold call and the kernel
+    roofline only with args.full; args.dump_outputs: see dump_outputs."""
+    full = getattr(args, "full", False)
+    dump = getattr(args, "dump_outputs", None)
+    sh = dict(layers=LAYERS, s_per_gpu=S_PER_GPU, M=M, c4={}, c5={})
+    sh.update(shapes or {})
+    world, rank = rt.world, rt.rank
+    c4sh = dict(layers=LAYERS, S=C4["S"], M=C4["M"])
+    c4sh.update({k: sh["c4"][k] for k in ("layers", "S", "M") if k in sh["c4"]})
+    # N = 1 with --full: the C4 line first, so that the headline's one short timed call
+    # (K = 20 steps, ~1.4 ms, in the driver's run) starts on a GPU at its
+    # working clocks rather than straight after process start-up (a plain
+    # run has headline_world1's own 200 scratch steps for that)
+    c4 = None
+    schedules = None
+    loop = None
+    if world == 1:
+        prep = headline_prep(rt, args) if shapes is None else None
+        if full and not args.no_c4:
+            log("C4 line")
+            c4 = c4_timings(rt, **sh["c4"])
+        elapsed, parts, avg_ms, pcount, cold, state = headline_world1(rt, args, prep)
+        elbo = parts
+        S, Mh, layers = sh["s_per_gpu"], sh["M"], sh["layers"]
+    else:
+        S, Mh, layers = c4sh["S"], c4sh["M"], c4sh["layers"]
+        # two complete schedules of the same step (ShardedInnerLoop.run): the
+        # exchanges in series with the network, and overlapped with it (two
+        # sample halves, each its own x -> network -> G chain, the second on a
+        # side stream); the headline is the faster (the same pick on every
+        # rank: the times are maxima over ranks), both are reported
+        sched = {}
+        for ov in (False, True):
+            log(f"C4 headline over {world} ranks ({'overlapped' if ov else 'plain'} exchanges)")
+            r_ = sharded_timed(rt, args.steps, args.warmup, layers, S, Mh, overlap=ov,
+                               phases=full)
+            sched["overlap" if ov else "plain"] = r_
+        pick = min(sched, key=lambda k: sched[k][0])
+        elapsed, parts, avg_ms, loop, held = sched[pick]
+        schedules = {k: {"inner_steps_per_s": round(args.steps / v_[0], 2),
+                         "ms_per_step": round(v_[0] / args.steps * 1e3, 4)} for k, v_ in sched.items()}
+        schedules["headline"] = pick
+        elbo = loop.reduce_elbo(parts)
+        pcount = loop.plan.param_count
+        cold = None
+        if dump:
+            # every rank's owned slices summed into whole arrays (a collective)
+            held = [t.clone() for t in held]
+            loop.gather_params(*held)
+            state = dict(zip(("params", "adam_m", "adam_v"), held), neg_elbo=elbo[args.warmup:])
+    if dump and rank == 0:
+        rt.sync()
+        dump_outputs(dump, state)
+    finite = bool(torch.isfinite(elbo).all().item())
+    steps_per_s = args.steps / elapsed
+    value = steps_per_s  # one step = one inner step of ALL S samples, on every N
+    roofline = kernel_roofline(world, S, layers, avg_ms, loop) if full else None
     # SURVEY.md section 8(d): the whole inner step's algorithmic work (C3: 2.682
     # GFLOP per step; C4: 23.54 GFLOP, split over the N GPUs) against the fp32
     # MFMA peak of the N GPUs -- the step's roofline fraction, beside the
@@ -823,33 +890,34 @@ def run(rt, args, shapes=None):
                          frac=round(step_floor_us / (elapsed / args.steps * 1e6), 4))
     log(f"headline: {steps_per_s:.1f} steps/s")
     weak = one = None
-    if world > 1:
+    if full and world > 1:
         log("weak-scaled C3 shards")
         weak = weak_line(rt, args.steps, args.warmup, layers=sh["layers"],
                          s_per_gpu=sh["s_per_gpu"], M=sh["M"])
         if rank == 0 and not args.no_c4:
             log("C4 on one GPU (rank 0)")
             one = c4_single_gpu(rt, **c4sh)
-            one["speedup_of_headline"] = round(value / one["inner_steps_per_s"], 3)
+            # of the line's own (rounded) figures
+            one["speedup_of_headline"] = round(round(value, 2) / one["inner_steps_per_s"], 3)
         rt.barrier()
     dp = None
-    if world > 1 and not args.no_dp:
+    if full and world > 1 and not args.no_dp:
         log("data-parallel alternative")
         dp = dp_timings(rt, **dict(c4sh, **sh.get("dp", {})))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("CPU baseline")
         cpu = cpu_baseline(args.cpu_budget)
     c2 = None
-    if rank == 0 and world == 1 and not args.no_c2:
+    if full and rank == 0 and world == 1 and not args.no_c2:
         log("C2 line")
         c2 = c2_timings(rt.dev, cpu=not args.no_cpu_baseline)
     trainers = None
-    if rank == 0 and world == 1 and not args.no_trainers:
+    if full and rank == 0 and world == 1 and not args.no_trainers:
         log("trainers")
         trainers = trainer_timings(rt.dev, cpu=not args.no_cpu_baseline)
     lenet = None
-    if not args.no_lenet:
+    if full and not args.no_lenet:
         # every rank takes part at N > 1 (C5 is an 8-GPU config: samples sharded)
         log("C5 lenet")
         lenet = lenet_timings(rt, cpu=not args.no_cpu_baseline, **sh["c5"])
@@ -934,11 +1002,19 @@ def relaunch(n, argv, script=None):
     return proc.wait()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call left its caller "
+                         "(params, adam_m, adam_v, neg_elbo per timed step) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement (cold call, per-phase split and kernel "
+                         "roofline, C4 / C2 / C5 / trainer lines, CPU baselines; N > 1: weak "
+                         "scaling, C4 on one GPU, data-parallel alternative); the --no-* "
+                         "switches below trim that set")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-lenet", action="store_true",
@@ -958,7 +1034,11 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="every rank on device 0 (rehearsing N ranks on a one-GPU box; "
                          "needs --comm gloo)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a bare `bench.py --gpus N`: start the N ranks under torchrun as a
         # child process (this process never touches the GPU) and exit with

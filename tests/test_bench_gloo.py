@@ -36,7 +36,7 @@ def _fake_draw(t, seed, offset):
     t.copy_(torch.randn(t.numel(), generator=g))
 
 
-def _rank_main(rank, world, port, out):
+def _rank_main(rank, world, port, out, dump=None):
     import sys
     for p in (os.path.join(ROOT, "blackbox-coresets-vi_amd"), os.path.join(ROOT, "oracle"),
               os.path.join(ROOT, "tests"), ROOT):
@@ -67,7 +67,8 @@ def _rank_main(rank, world, port, out):
         rt = bench.Runtime(torch.device("cpu"), world, rank, HostStagedComm())
         args = argparse.Namespace(steps=3, warmup=1, no_c4=False, no_cpu_baseline=True,
                                   no_c2=True, no_trainers=True, no_lenet=False, cpu_budget=1.0,
-                                  no_dp=True)
+                                  no_dp=True, full=True,
+                                  dump_outputs=dump)
         shapes = dict(layers=FN2, s_per_gpu=4, M=5,
                       c4=dict(layers=FN2, S=7, M=6, steps=2, warmup=1),
                       c5=dict(S=world + 1, M=3, T=2, second_order=False))
@@ -92,14 +93,15 @@ def _rank_main(rank, world, port, out):
 
 
 @pytest.mark.parametrize("world", [2, 3])
-def test_bench_multi_rank_control_flow(world):
+def test_bench_multi_rank_control_flow(world, tmp_path):
     import psvi_oracle as O
     from golden_util import l2rel, rel
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_rank_main, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_rank_main, args=(r, world, port, q, str(tmp_path / "dump")))
+             for r in range(world)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=600) for _ in range(world)], key=lambda x: x[0])
@@ -134,6 +136,15 @@ def test_bench_multi_rank_control_flow(world):
     c5 = line["lenet_c5"]
     assert c5 is not None and c5["gpu_inner_steps_per_s"] > 0 and c5["elbo_finite"]
     assert "gpu_hvp_ms" not in c5      # second order: the GPU rehearsal covers it
+    # --dump-outputs: rank 0 wrote the headline's last state, whole (the ranks'
+    # owned slices gathered), and the negative ELBO of the 3 timed steps
+    dumped = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(dumped) == ["adam_m", "adam_v", "neg_elbo", "params"]
+    for k in ("params", "adam_m", "adam_v"):
+        assert dumped[k].dtype == np.float32 and dumped[k].shape == (line["config"]["params"],)
+        assert np.isfinite(dumped[k]).all() and np.abs(dumped[k]).max() > 0
+    assert dumped["neg_elbo"].dtype == np.float64 and dumped["neg_elbo"].shape == (3,)
+    assert np.isfinite(dumped["neg_elbo"]).all()
     # the sharded steps: every rank ends with the world-1 oracle loop's state
     _, _, p0, params, m, v, negelbo, u, z, w, neps = res[0]
     S = 4 * world
@@ -151,6 +162,72 @@ def test_bench_multi_rank_control_flow(world):
     assert l2rel(m, o_m) < 1e-5 and l2rel(v, o_v) < 1e-5
     for r in res[1:]:
         assert np.array_equal(r[3], params), "replicas differ after gather_params"
+
+
+def test_plain_run_leaves_the_side_measurements_out():
+    """Without --full, run() at N > 1 times the two schedules and nothing
+    else: no per-phase call, no weak / C4 / data-parallel / C5 legs."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    calls = []
+
+    class Loop:
+        class plan:
+            param_count = 11
+
+        def reduce_elbo(self, parts):
+            return parts.sum(-1)
+
+    def timed(rt, steps, warmup, layers, S, M, overlap=False, phases=True, **kw):
+        calls.append((overlap, phases))
+        st = tuple(torch.zeros(11) for _ in range(3))
+        return 0.5 if overlap else 0.25, torch.zeros(warmup + steps, 2, dtype=torch.float64), None, Loop(), st
+
+    b.sharded_timed = timed
+    for leg in ("weak_line", "c4_single_gpu", "dp_timings", "lenet_timings", "cpu_baseline",
+                "c2_timings", "trainer_timings", "c4_timings", "kernel_roofline"):
+        setattr(b, leg, lambda *a, _leg=leg, **k: pytest.fail(f"{_leg} ran in a plain run"))
+    rt = b.Runtime(torch.device("cpu"), 2, 0)
+    rt.barrier = lambda: None
+    args = b.parse_args(["--gpus", "2", "--steps", "4", "--warmup", "1"])
+    assert not args.full and args.dump_outputs is None
+    line = b.run(rt, args)
+    assert calls == [(False, False), (True, False)]
+    assert line["steps"] == 4 and line["ms_per_step"] == 62.5 and line["value"] == 16.0
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["config"]["exchange_schedules"]["headline"] == "plain"
+    for k in ("roofline", "cold_call", "cpu_baseline", "c4_1gpu", "weak", "dp_alternative", "c2",
+              "trainers", "lenet_c5", "speedup_over_1gpu"):
+        assert line[k] is None, k
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.dump_outputs: arrays whole (flattened, float32 / float64 kept)
+    under the limit; over it, the large ones cut to the same seeded sample of
+    entries in every call, the total within the limit."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(0)
+    big, small = torch.randn(5000, generator=g), torch.randn(3, 2, generator=g, dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "a"), dict(big=big, small=small))
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), big.numpy())
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy().reshape(-1))
+    b.DUMP_LIMIT_BYTES = 2 * 1024 + 8000
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), dict(big=big, small=small))
+    cut = np.load(tmp_path / "b" / "big.npy")
+    assert cut.dtype == np.float32 and cut.shape == (1000,) and np.isin(cut, big.numpy()).all()
+    assert np.array_equal(cut, np.load(tmp_path / "c" / "big.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), small.numpy().reshape(-1))
+    size = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert size <= b.DUMP_LIMIT_BYTES
 
 
 def test_pmc_traffic_matches_template_keys(tmp_path):

@@ -34,7 +34,7 @@ def test_bench_multi_rank_on_one_gpu(world):
            f"--nproc-per-node={world}", "--master-addr=127.0.0.1",
            f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"), "--gpus", str(world),
            "--steps", "5", "--warmup", "2", "--comm", "gloo", "--share-gpu",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-4000:]
