@@ -22,6 +22,9 @@ void net_set_lds_limit();                // kernels_net.hip
 extern int g_net_ablation;               // kernels_net.hip
 extern int g_net_scalar_loads;           // kernels_net.hip
 extern unsigned long long* g_net_stamps; // kernels_net.hip
+extern uint16_t* g_net_draw_planes;      // kernels_net.hip
+extern int g_net_draw_role1;             // kernels_net.hip
+extern int g_net_draw_spare_off;         // kernels_net.hip
 extern int g_upd_ablation;               // kernels_mvn.hip
 extern int g_stream_off;                 // kernels_mvn.hip
 extern int g_stream_bf_off;              // kernels_mvn.hip
@@ -654,6 +657,11 @@ int psvi_debug_set(int32_t key, int32_t value) {
         case PSVI_DBG_NET_SCALAR_LOADS: g_net_scalar_loads = value; return 0;
         case PSVI_DBG_NET_MLOOP_OFF: g_net_mloop_off = value; return 0;
         case PSVI_DBG_NET_GEO_OFF: g_net_geo_off = value; return 0;
+        case PSVI_DBG_NET_DRAW_SPARE_OFF: g_net_draw_spare_off = value; return 0;
+        case PSVI_DBG_NET_DRAW_ROLE1:
+            if (value < 0 || value > 32) return fail(PSVI_EINVAL, "0..32");
+            g_net_draw_role1 = value;
+            return 0;
         case PSVI_DBG_STREAM_WGS: g_stream_wgs = value; return 0;
         case PSVI_DBG_STREAM_COST: g_stream_cost = value; return 0;
         case PSVI_DBG_STREAM_RR: g_stream_rr = value; return 0;
@@ -688,6 +696,7 @@ int psvi_debug_loop_timing(double* out) {
 int psvi_debug_set_ptr(int32_t key, void* ptr) {
     switch (key) {
         case PSVI_DBG_NET_STAMPS: g_net_stamps = (unsigned long long*)ptr; return 0;
+        case PSVI_DBG_NET_DRAW_PLANES: g_net_draw_planes = (uint16_t*)ptr; return 0;
         case PSVI_DBG_UPD_STAMPS: g_upd_stamps = (unsigned long long*)ptr; return 0;
         case PSVI_DBG_BF_STAMPS: g_bf_stamps = (unsigned long long*)ptr; return 0;
         case PSVI_DBG_ROP_STAMPS: g_rop_stamps = (unsigned long long*)ptr; return 0;
@@ -726,10 +735,11 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world, int3
     p->world = world;
     p->rank = rank;
     int rc = build_plan(*p);
-    if (!rc && family == PSVI_FAMILY_FULLCOV && world == 1 && p->fuse_sample && p->tiles_total > 0 &&
-        p->n_str > 0 && p->d.S == 128) {
-        // the streaming update's bf16 planes of every draw (EpsPlanes): rows
-        // padded to 64-column multiples, layers back to back
+    if (!rc && family == PSVI_FAMILY_FULLCOV && world == 1) {
+        // the bf16 planes of a draw (EpsPlanes): rows padded to 64-column
+        // multiples, layers back to back -- the streaming update's operands
+        // (bf_stream: the plans that run it), and for every plan the layout
+        // of the diagnostics planes (PSVI_DBG_NET_DRAW_PLANES)
         psvi::EpsPlanes& E = p->eps_planes;
         E.L = p->L;
         int64_t po = 0, eo = 0;
@@ -744,7 +754,9 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world, int3
         }
         E.eoff[p->L] = eo;
         E.pl = (po + 63) / 64 * 64;
-        p->bf_stream = eo == p->Peps;
+        p->eps_planes_ok = eo == p->Peps;
+        p->bf_stream = p->eps_planes_ok && p->fuse_sample && p->tiles_total > 0 && p->n_str > 0 &&
+                       p->d.S == 128;
     }
     if (!rc && have_dev) {
         // the only device allocations of the library: immutable work lists
@@ -818,7 +830,7 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world, int3
              hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
              hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
             rc = fail(PSVI_EUNSUP, "cannot create the inner loop's conversion stream");
-        if (!rc && p->bf_stream) {
+        if (!rc && p->eps_planes_ok) {
             std::vector<psvi::EpsPlanes> one(1, p->eps_planes);
             rc = upload(one, &p->d_eps_planes);
         }

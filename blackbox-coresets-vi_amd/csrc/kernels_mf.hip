@@ -347,12 +347,12 @@ hipError_t launch_adam(int64_t n, float* p, const float* g, float* m, float* v,
 template <bool VEC>
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int64_t n,
                                                     uint64_t seed, uint64_t offset,
-                                                    double* __restrict__ zero, int64_t nzero) {
-    const int64_t nq = (n + 3) / 4;
+                                                    double* __restrict__ zero, int64_t nzero,
+                                                    int64_t q_lo, int64_t q_hi) {
     const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = gid; i < nzero; i += gs) zero[i] = 0.0;
-    for (int64_t q = gid; q < nq; q += gs)
+    for (int64_t q = q_lo + gid; q < q_hi; q += gs)
         randn_quad<VEC>(out, n, seed, offset, q);
 }
 
@@ -360,32 +360,38 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
 __global__ __launch_bounds__(256) void randn_planes_kernel(float* __restrict__ out, int64_t n,
                                                            uint64_t seed, uint64_t offset,
                                                            double* __restrict__ zero, int64_t nzero,
-                                                           EpsPlanes P, uint16_t* __restrict__ planes) {
-    const int64_t nq = (n + 3) / 4;
+                                                           EpsPlanes P, uint16_t* __restrict__ planes,
+                                                           int64_t q_lo, int64_t q_hi) {
     const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = gid; i < nzero; i += gs) zero[i] = 0.0;
-    for (int64_t q = gid; q < nq; q += gs) randn_quad_planes(out, n, seed, offset, q, P, planes);
+    for (int64_t q = q_lo + gid; q < q_hi; q += gs) randn_quad_planes(out, n, seed, offset, q, P, planes);
 }
 
 hipError_t launch_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st,
-                        double* zero, int64_t nzero, const EpsPlanes* planes_desc, uint16_t* planes) {
+                        double* zero, int64_t nzero, const EpsPlanes* planes_desc, uint16_t* planes,
+                        int64_t q_lo, int64_t q_hi) {
     if (n <= 0 && nzero <= 0) return hipSuccess;
     if (!zero) nzero = 0;
+    // the quads drawn: all of [0, ceil(n / 4)), or the caller's part of them
+    const int64_t nqa = (std::max<int64_t>(n, 0) + 3) / 4;
+    q_hi = q_hi < 0 ? nqa : std::min(q_hi, nqa);
+    q_lo = std::max<int64_t>(q_lo, 0);
+    if (q_hi <= q_lo && nzero <= 0) return hipSuccess;
     const int64_t nb = std::max<int64_t>(
-        1, std::min<int64_t>(std::max((n + 3) / 4, nzero) / 256 + 1, 4096));
+        1, std::min<int64_t>(std::max(std::max<int64_t>(q_hi - q_lo, 0), nzero) / 256 + 1, 4096));
     if (planes && planes_desc) {
         if ((uintptr_t)out & 15) return hipErrorInvalidValue;
         hipLaunchKernelGGL(randn_planes_kernel, dim3((unsigned)nb), dim3(256), 0, st, out, n, seed,
-                           offset, zero, nzero, *planes_desc, planes);
+                           offset, zero, nzero, *planes_desc, planes, q_lo, q_hi);
         return hipGetLastError();
     }
     if (((uintptr_t)out & 15) == 0)
         hipLaunchKernelGGL(randn_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, out, n, seed,
-                           offset, zero, nzero);
+                           offset, zero, nzero, q_lo, q_hi);
     else
         hipLaunchKernelGGL(randn_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, out, n,
-                           seed, offset, zero, nzero);
+                           seed, offset, zero, nzero, q_lo, q_hi);
     return hipGetLastError();
 }
 

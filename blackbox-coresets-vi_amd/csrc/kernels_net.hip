@@ -63,7 +63,7 @@ struct NetArgs {
     // X_0 = u chunk, X_l = relu(a_{l-1})), two gradient buffers, dlogits
     int lw[kMaxL], ldw[kMaxL], lb[kMaxL], lx[kMaxL], ldx[kMaxL];
     int lwt[kMaxL], ldwt[kMaxL];  // W_l^T (l >= 1: the propagation GEMM's k-contiguous operand)
-    int lg[kMaxL], ldl, lddl, lred, lsrc, lzw, lstamp, lds_f4;  // lg[l]: G_l (l < L-1); ldl: dlogits [Mp][lddl]; lzw: z, w
+    int lg[kMaxL], ldl, lddl, lred, lsrc, lzw, lstamp, ldraw, lds_f4;  // lg[l]: G_l (l < L-1); ldl: dlogits [Mp][lddl]; lzw: z, w
     int nslack, nslack_early, slack[5 * kMaxL + 8];  // kNetSlack  // float offsets of the 64-float zero slacks
     int stage_len, stage_off[kMaxWorld + 1];  // FULLCOV: this sample's x row, source blocks back to back
     const float* u;
@@ -114,9 +114,16 @@ struct NetArgs {
     int nbands, bbase[kMaxL];
     int mloop;  // pseudopoint chunks looped inside one workgroup (1: none)
     // this launch's local samples [s_begin, s_begin + gridDim.x) (the sharded
-    // loop's sample halves); the fused draw's part rn_part of rn_nparts
-    // contiguous quad ranges
-    int s_begin, rn_part, rn_nparts;
+    // loop's sample halves)
+    int s_begin;
+    // the fused draw's quads [rn_q0, rn_q1) of this launch (its part of the
+    // stream's quads), dealt out in chunks of 64 quads (one per wave pass):
+    // workgroup j = blockIdx.x + gridDim.x blockIdx.z of role r owns chunks
+    // [c, c + rn_per[r] + (j < rn_rem[r])), c = rn_cbase[r] + j rn_per[r] +
+    // min(j, rn_rem[r]) (role 1 first: it finishes earlier and takes more);
+    // rn_spare: waves without a row tile draw during the row chain
+    int64_t rn_q0, rn_q1, rn_cbase0, rn_cbase1;
+    int rn_per0, rn_per1, rn_rem0, rn_rem1, rn_spare;
     // the fused draw also as bf16 planes (the bf16-plane streaming update)
     const EpsPlanes* rn_P;
     uint16_t* rn_planes;
@@ -127,7 +134,7 @@ struct NetArgs {
 // = 0..15) and a 64-lane float read down k (lanes 16 k4 + i16, rows 4 k4
 // apart) both hit distinct banks.  Regions read before the forward pass come
 // first; every region is followed by a 64-float zero slack.
-constexpr int kNetSlack = 5 * kMaxL + 8;
+constexpr int kNetSlack = 5 * kMaxL + 8;  // >= 5 L + 5 regions
 struct NetDims {
     int L;
     int din[kMaxL], dout[kMaxL];
@@ -135,7 +142,7 @@ struct NetDims {
 struct NetCarve {
     int lw[kMaxL], ldw[kMaxL], lb[kMaxL], lx[kMaxL], ldx[kMaxL], lwt[kMaxL], ldwt[kMaxL],
         lg[kMaxL];
-    int ldl, lddl, lred, lsrc, lzw, lstamp, lds_f4, Mp, nslack, nslack_early;
+    int ldl, lddl, lred, lsrc, lzw, lstamp, ldraw, lds_f4, Mp, nslack, nslack_early;
     int slack[kNetSlack];
 };
 constexpr int net_rup(int x, int m) { return (x + m - 1) / m * m; }
@@ -188,6 +195,9 @@ constexpr NetCarve net_carve(const NetDims& d, int mc, int nbands) {
     for (int l = 0; l + 1 < d.L; ++l) c.lg[l] = take(Mp * net_ld8o(d.din[l + 1]));
     c.lddl = net_ld8o(d.dout[d.L - 1]);
     c.ldl = take(Mp * c.lddl);
+    // the fused draw's chunk counter, the row chain's finished waves, and the
+    // draw wave's finish stamp (uint64); last, so that no other offset moves
+    c.ldraw = take(4);
     off = (off + 3) & ~3;
     c.lx[0] = lx0;
     c.ldx[0] = ldx0;
@@ -205,6 +215,38 @@ constexpr NetCarve net_carve(const NetDims& d, int mc, int nbands) {
 // instruction offsets and no kernel argument is loaded for them.
 constexpr NetDims kFn2Dims{3, {64, 40, 40}, {40, 40, 2}};
 constexpr int kFn2Mp = 112, kFn2Bands = 41 + 26 + 2;
+// The fused draw's bf16-plane placement under the fixed geometry (EpsPlanes
+// of the fn2 stack for S samples): every row length a constant, so the row
+// divisions are multiplications, and all indices 32-bit (the host gates the
+// fixed geometry to draws below 2^31 elements).
+struct Fn2PlaneMap {
+    uint32_t S;
+    static constexpr uint32_t n(int l) { return kFn2Dims.din[l] * kFn2Dims.dout[l] + kFn2Dims.dout[l]; }
+    static constexpr uint32_t npad(int l) { return (n(l) + 63) / 64 * 64; }
+    static constexpr uint32_t ntot() { return n(0) + n(1) + n(2); }
+    static constexpr uint32_t nptot() { return npad(0) + npad(1) + npad(2); }
+    __device__ __forceinline__ int64_t operator()(int64_t i64, int& c, int& nl) const {
+        const uint32_t i = (uint32_t)i64, e1 = S * n(0), e2 = e1 + S * n(1);
+        uint32_t s, o;
+        if (i < e1) {
+            s = i / n(0);
+            c = (int)(i - s * n(0));
+            nl = (int)n(0);
+            o = s * npad(0);
+        } else if (i < e2) {
+            s = (i - e1) / n(1);
+            c = (int)(i - e1 - s * n(1));
+            nl = (int)n(1);
+            o = S * npad(0) + s * npad(1);
+        } else {
+            s = (i - e2) / n(2);
+            c = (int)(i - e2 - s * n(2));
+            nl = (int)n(2);
+            o = S * (npad(0) + npad(1)) + s * npad(2);
+        }
+        return (int64_t)(o + (uint32_t)c);
+    }
+};
 template <int GEO>
 struct NetGeo {
     static constexpr bool kFixed = true;
@@ -233,6 +275,7 @@ struct NetGeo {
     __device__ static constexpr int lsrc() { return C.lsrc; }
     __device__ static constexpr int lzw() { return C.lzw; }
     __device__ static constexpr int lstamp() { return C.lstamp; }
+    __device__ static constexpr int ldraw() { return C.ldraw; }
     __device__ static constexpr int lds_f4() { return C.lds_f4; }
     __device__ static constexpr int Mp() { return C.Mp; }
     __device__ static constexpr int nslack() { return C.nslack; }
@@ -262,6 +305,7 @@ struct NetGeo<0> {
     __device__ int lsrc() const { return a.lsrc; }
     __device__ int lzw() const { return a.lzw; }
     __device__ int lstamp() const { return a.lstamp; }
+    __device__ int ldraw() const { return a.ldraw; }
     __device__ int lds_f4() const { return a.lds_f4; }
     __device__ int Mp() const { return a.Mp; }
     __device__ int nslack() const { return a.nslack; }
@@ -503,6 +547,11 @@ __global__ __launch_bounds__(512) void net_kernel(NetArgs a) {
         __syncthreads();
     }
     if (a.stamps && threadIdx.x < 16) stl[threadIdx.x] = 0;
+    // the fused draw's controls: [0] the next chunk to hand out, [1] row-chain
+    // waves that have finished, [2..3] the draw wave's finish (diagnostics);
+    // zeroed here, first used behind the load phase's barrier
+    int* dctl = reinterpret_cast<int*>(sm + g.ldraw());
+    if (threadIdx.x < 4) dctl[threadIdx.x] = 0;
     NET_STAMP(0, __builtin_amdgcn_s_memtime());
     // diagnostics: each wave's start, for the launch skew in slot 15
     const unsigned long long wstart = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -568,7 +617,53 @@ __global__ __launch_bounds__(512) void net_kernel(NetArgs a) {
     floatx4 wc[kMaxL][kWcUnits][1];
     float bc[kMaxL];
     int ch = 0;
-chunk_top:  // a backward jump only when MLOOP (no loop at all in the other instantiations)
+    // ---- the next step's normals (psvi_randn's stream; with rn_planes also as
+    // bf16 planes).  The draw depends on nothing in the step, so the waves
+    // that carry no row tile (16 wave >= Mp: one of eight at the fn2 geometry)
+    // draw while the others run the row chain; what they have not covered when
+    // the first chain wave finishes is drawn by every wave after the weight
+    // gradients.  Work goes out in chunks of 64 quads -- one full wave pass,
+    // never a ragged one -- from a counter in LDS, so who draws which quad is
+    // decided at run time and changes no value.
+    const int dj = blockIdx.x + gridDim.x * blockIdx.z;
+    const int drem = role ? a.rn_rem1 : a.rn_rem0, dper = role ? a.rn_per1 : a.rn_per0;
+    const int dcnt = dper + (dj < drem ? 1 : 0);  // this workgroup's chunks
+    const int64_t dq0 =
+        a.rn_q0 + 64 * ((role ? a.rn_cbase1 : a.rn_cbase0) + (int64_t)dj * dper + min(dj, drem));
+    const int nchain = min(nthr >> 6, Mp >> 4);  // waves with a row tile
+    auto draw = [&](bool spare) __attribute__((always_inline)) {
+        const int ln = threadIdx.x & 63;
+        EpsPlanes P;
+        if constexpr (!Geo::kFixed)
+            if (a.rn_planes) P = *a.rn_P;
+        for (;;) {
+            int c = 0;
+            // (a spare wave stops once a chain wave of this pseudopoint chunk is
+            // through: the chain barrier waits for it)
+            // (an LDS atomic load: a volatile read became a flat load, whose
+            // wait also drained the wave's global stores before every chunk)
+            if (ln == 0)
+                c = (spare && __hip_atomic_load(dctl + 1, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_WORKGROUP) > ch * nchain)
+                        ? dcnt
+                        : atomicAdd(dctl, 1);
+            c = __builtin_amdgcn_readfirstlane(c);
+            if (c >= dcnt) break;  // wave-uniform
+            const int64_t q = dq0 + 64 * (int64_t)c + ln;
+            if (q >= a.rn_q1) continue;  // (the launch's last chunk)
+            if (a.rn_planes) {
+                if constexpr (Geo::kFixed)
+                    randn_quad_planes_at(a.rn_out, a.rn_n, a.rn_seed, a.rn_off, q,
+                                         Fn2PlaneMap{(uint32_t)a.S_total},
+                                         (int64_t)a.S_total * Fn2PlaneMap::nptot(), a.rn_planes);
+                else
+                    randn_quad_planes(a.rn_out, a.rn_n, a.rn_seed, a.rn_off, q, P, a.rn_planes);
+            } else {
+                randn_quad<true>(a.rn_out, a.rn_n, a.rn_seed, a.rn_off, q);
+            }
+        }
+    };
+chunk_top:// a backward jump only when MLOOP (no loop at all in the other instantiations)
     {
     const int m0 = (blockIdx.z * nloop + ch) * a.mc;
     const int mcnt = min(a.mc, a.M - m0);
@@ -1048,6 +1143,16 @@ chunk_top:  // a backward jump only when MLOOP (no loop at all in the other inst
             row_gemm<true, false>(din, dout, gbuf(0) + r0 * gld(0), gld(0), sm + g.lw(0), g.ldw(0), epi);
         }
     }
+    if (a.rn_out) {
+        if (16 * wave_id() < Mp) {
+            if (lane == 0) atomicAdd(dctl + 1, 1);  // a chain wave is through
+        } else if (a.rn_spare) {
+            draw(true);
+            // diagnostics: the last wave's draw finish (slot 15's high half)
+            if (a.stamps && lane == 0 && wave_id() == nwv - 1)
+                *reinterpret_cast<unsigned long long*>(dctl + 2) = __builtin_amdgcn_s_memtime();
+        }
+    }
     __syncthreads();  // every tile's rows of X_l and G_l
     NET_STAMP(2, __builtin_amdgcn_s_memtime());
 
@@ -1162,29 +1267,22 @@ chunk_top:  // a backward jump only when MLOOP (no loop at all in the other inst
         const float tot = block_sum(part, sm + g.lred());
         if (tid == 0) atomicAdd(a.nll_out, (double)tot);
     }
-    if (a.rn_out) {
-        // the next step's normals (psvi_randn's stream), split over the grid's
-        // workgroups.  Last, so that no s_waitcnt of the phases above waits for
-        // these stores to retire.
-        const int64_t nqa = (a.rn_n + 3) / 4;
-        const int64_t qlo = nqa * a.rn_part / a.rn_nparts, nq = nqa * (a.rn_part + 1) / a.rn_nparts;
-        const int nblk = gridDim.x * gridDim.y * gridDim.z;
-        const int b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const int64_t per = (nq - qlo + nblk - 1) / nblk, q1 = min(nq, qlo + (b + 1) * per);
-        if (a.rn_planes) {
-            const EpsPlanes P = *a.rn_P;
-            for (int64_t q = qlo + b * per + tid; q < q1; q += nthr)
-                randn_quad_planes(a.rn_out, a.rn_n, a.rn_seed, a.rn_off, q, P, a.rn_planes);
-        } else {
-            for (int64_t q = qlo + b * per + tid; q < q1; q += nthr)
-                randn_quad<true>(a.rn_out, a.rn_n, a.rn_seed, a.rn_off, q);
-        }
-    }
+    // the draw's chunks that no spare wave took, on every wave.  Last, so that
+    // no s_waitcnt of the phases above waits for these stores to retire.
+    if (a.rn_out) draw(false);
     NET_STAMP(12, __builtin_amdgcn_s_memtime());
     NET_STAMP(14, __builtin_amdgcn_s_memrealtime());
-    if (a.stamps && threadIdx.x < 16)  // wave 0 wrote them: in order, no barrier needed
-        a.stamps[(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 16 + threadIdx.x] =
-            stl[threadIdx.x];
+    if (a.stamps && threadIdx.x < 16) {  // wave 0 wrote them: in order, no barrier needed
+        unsigned long long v = stl[threadIdx.x];
+        if (threadIdx.x == 15) {
+            // slot 15: low half the launch skew (last wave start - slot 0), high
+            // half the draw wave's finish - slot 0 (0: no spare wave drew; it
+            // wrote before the chain barrier)
+            const unsigned long long df = *reinterpret_cast<unsigned long long*>(dctl + 2);
+            v = ((v - stl[0]) & 0xffffffffull) | ((df ? df - stl[0] : 0ull) << 32);
+        }
+        a.stamps[(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 16 + threadIdx.x] = v;
+    }
 }
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
@@ -1211,7 +1309,7 @@ static size_t net_lds_floats(const psvi_plan& p, int mc, NetArgs* a) {
         }
         for (int k = 0; k < kNetSlack; ++k) a->slack[k] = c.slack[k];
         a->ldl = c.ldl; a->lddl = c.lddl; a->lred = c.lred; a->lsrc = c.lsrc;
-        a->lzw = c.lzw; a->lstamp = c.lstamp; a->Mp = c.Mp;
+        a->lzw = c.lzw; a->lstamp = c.lstamp; a->ldraw = c.ldraw; a->Mp = c.Mp;
         a->nslack = c.nslack; a->nslack_early = c.nslack_early; a->lds_f4 = c.lds_f4;
         if (p.family == PSVI_FAMILY_FULLCOV) {  // the x row's source blocks (no LDS)
             int st = 0;
@@ -1320,6 +1418,9 @@ int g_net_mloop_off = 0;  // psvi_debug_set(PSVI_DBG_NET_MLOOP_OFF, 1): a workgr
 int g_net_scalar_loads = 0;  // psvi_debug_set(PSVI_DBG_NET_SCALAR_LOADS, 1): the scalar load path (A/B)
 int g_net_geo_off = 0;  // psvi_debug_set(PSVI_DBG_NET_GEO_OFF, 1): the run-time geometry for fn2 too (A/B)
 unsigned long long* g_net_stamps = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_NET_STAMPS, buf)
+uint16_t* g_net_draw_planes = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_NET_DRAW_PLANES, buf)
+int g_net_draw_role1 = 17;  // psvi_debug_set(PSVI_DBG_NET_DRAW_ROLE1, n): role 1's 32nds of the fused draw
+int g_net_draw_spare_off = 0;  // psvi_debug_set(PSVI_DBG_NET_DRAW_SPARE_OFF, 1): the whole draw at the end (A/B)
 
 void net_set_lds_limit() {
     // gfx950: up to 160 KiB of LDS per workgroup
@@ -1380,8 +1481,8 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
         rn_part >= rn_nparts)
         return hipErrorInvalidValue;
     a.s_begin = s_begin;
-    a.rn_part = rn_part;
-    a.rn_nparts = rn_nparts;
+    if (!rn_planes && g_net_draw_planes && rn_out && p.family == PSVI_FAMILY_FULLCOV)
+        rn_planes = g_net_draw_planes;  // diagnostics: the planes of a draw that asked for none
     if (outer) {
         a.outer = outer->mode;
         a.n_pseudo = outer->n_pseudo;
@@ -1456,15 +1557,45 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
     // a launch without samples still owes its part of the next step's draw
     // (every rank passes the same global eps to its update): the draw on its
     // own (the whole of it when this is its only part)
+    // this launch's part of the draw's quads
+    const int64_t nqa = rn_out && rn_n > 0 ? (rn_n + 3) / 4 : 0;
+    a.rn_q0 = nqa / rn_nparts * rn_part + nqa % rn_nparts * rn_part / rn_nparts;
+    a.rn_q1 = nqa / rn_nparts * (rn_part + 1) + nqa % rn_nparts * (rn_part + 1) / rn_nparts;
     if (s_count == 0) {
-        if (!rn_out || rn_n <= 0 || rn_part > 0) return hipSuccess;
+        if (a.rn_q1 <= a.rn_q0) return hipSuccess;
         return launch_randn(rn_out, rn_n, rn_seed, rn_off, st, nullptr, 0,
-                            rn_planes ? &p.eps_planes : nullptr, rn_planes);
+                            rn_planes ? &p.eps_planes : nullptr, rn_planes, a.rn_q0, a.rn_q1);
     }
     // per-chunk slots are summed over all the rank's samples: whole launches only
     if (a.gslot && a.outer != 1 && (s_begin != 0 || s_count != S_loc)) return hipErrorInvalidValue;
-    const bool fn2 = net_vec_ok(p) && net_fn2_geo(p);
+    // (the fixed geometry places the draw's planes with 32-bit indices)
+    const bool fn2 = net_vec_ok(p) && net_fn2_geo(p) && rn_n < (int64_t(1) << 31);
     if (fn2 && p.world > 1 && a.nbands != kFn2Bands) return hipErrorInvalidValue;
+    if (fn2 && a.rn_planes) {  // Fn2PlaneMap is the plan's EpsPlanes
+        const EpsPlanes& E = p.eps_planes;
+        bool ok = E.L == kFn2Dims.L && E.pl == (int64_t)p.d.S * Fn2PlaneMap::nptot() &&
+                  E.eoff[E.L] == (int64_t)p.d.S * Fn2PlaneMap::ntot();
+        for (int l = 0; ok && l < kFn2Dims.L; ++l)
+            ok = E.n[l] == (int)Fn2PlaneMap::n(l) && E.npad[l] == (int)Fn2PlaneMap::npad(l);
+        if (!ok) return hipErrorInvalidValue;
+    }
+    {
+        // The draw's chunks of 64 quads over the workgroups: role 1 (the
+        // shorter role) takes g_net_draw_role1 / 32 of them, each role's share
+        // goes evenly (to one chunk) over its workgroups.
+        const int64_t nch = (a.rn_q1 - a.rn_q0 + 63) / 64;
+        const int64_t nper = (int64_t)grid.x * grid.z;
+        const int64_t c1 = grid.y == 2 ? nch / 32 * g_net_draw_role1 + nch % 32 * g_net_draw_role1 / 32 : 0;
+        const int64_t c0 = nch - c1;
+        if (c0 / nper >= INT32_MAX || c1 / nper >= INT32_MAX) return hipErrorInvalidValue;
+        a.rn_cbase1 = 0;
+        a.rn_per1 = (int)(c1 / nper);
+        a.rn_rem1 = (int)(c1 % nper);
+        a.rn_cbase0 = c1;
+        a.rn_per0 = (int)(c0 / nper);
+        a.rn_rem0 = (int)(c0 % nper);
+        a.rn_spare = g_net_draw_spare_off ? 0 : 1;
+    }
     if (p.family == PSVI_FAMILY_MEANFIELD)
         hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_MEANFIELD, false>), grid, block, p.net_lds, st, a);
     else if (fn2 && loop && p.world > 1)

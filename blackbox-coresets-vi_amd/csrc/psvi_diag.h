@@ -20,7 +20,10 @@ int psvi_debug_set(int32_t key, int32_t value);
                                     phase boundaries (1 loads, 9..11 forward
                                     layers, 2 forward, 3 head, 4..8 backward
                                     phases, 12 end; 13 / 14 s_memrealtime
-                                    start / end)                               */
+                                    start / end; 15 two 32-bit spans from slot
+                                    0: low the last wave's start, high the
+                                    finish of the fused draw on the last wave
+                                    when it carries no row tile, else 0)       */
 #define PSVI_DBG_UPD_ABLATION 3  /* value: mask of full-cov update-kernel parts to
                                     replace (1 G/eps loads by one cached
                                     address, 2 dL MFMAs skipped, 4 corr/m/v
@@ -123,6 +126,16 @@ int psvi_debug_set_ptr(int32_t key, void* ptr);
                                     combine (x' = mean + softplus(sd) eps' + the
                                     band's slots) as mvn_fwd_reduce_kernel
                                     instead of in the kernel (A/B)             */
+#define PSVI_DBG_NET_DRAW_PLANES 35  /* ptr: device uint16 buffer of 3 x the plan's
+                                    plane length (full-cov, world 1): a network
+                                    launch whose fused draw asked for no bf16
+                                    planes writes them there (tests: the planes
+                                    of psvi_mvn_phase_net_draw / _part)        */
+#define PSVI_DBG_NET_DRAW_ROLE1 36   /* value: 0..32, the 32nds of the fused
+                                    draw that role-1 workgroups take (tuning)  */
+#define PSVI_DBG_NET_DRAW_SPARE_OFF 37 /* value: 1 = the fused draw wholly behind
+                                    the weight gradients, none of it on the
+                                    waves without a row tile (A/B)             */
 /* mean device microseconds of the recorded windows: out[0] network kernel,
    out[1] update (+ its slot reduce), out[2] windows; synchronizes on them and
    drops the records */

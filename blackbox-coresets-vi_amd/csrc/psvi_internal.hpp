@@ -163,14 +163,12 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
     }
 }
 
-// normals 4q .. 4q+3 of the stream into out[0, n)
-template <bool VEC>
-__device__ __forceinline__ void randn_quad(float* __restrict__ out, int64_t n, uint64_t seed,
-                                           uint64_t offset, int64_t q) {
+// normals 4q .. 4q+3 of the stream (Philox counter offset / 4 + q, Box-Muller)
+__device__ __forceinline__ void randn_quad_vals(uint64_t seed, uint64_t offset, int64_t q,
+                                                float (&r)[4]) {
     const uint64_t ctr = offset / 4 + (uint64_t)q;
     uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    float r[4];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         // Box-Muller on the native transcendentals: u1 in (0, 1], u2 in [0, 1);
@@ -181,6 +179,14 @@ __device__ __forceinline__ void randn_quad(float* __restrict__ out, int64_t n, u
         r[2 * j] = rad * __builtin_amdgcn_cosf(u2);
         r[2 * j + 1] = rad * __builtin_amdgcn_sinf(u2);
     }
+}
+
+// normals 4q .. 4q+3 of the stream into out[0, n)
+template <bool VEC>
+__device__ __forceinline__ void randn_quad(float* __restrict__ out, int64_t n, uint64_t seed,
+                                           uint64_t offset, int64_t q) {
+    float r[4];
+    randn_quad_vals(seed, offset, q, r);
     const int64_t base = q * 4;
     if (VEC && base + 3 < n) {
         *reinterpret_cast<float4*>(out + base) = make_float4(r[0], r[1], r[2], r[3]);
@@ -218,33 +224,13 @@ struct EpsPlanes {
     int64_t poff[kMaxL];
 };
 
-// normals 4q .. 4q+3 of the stream into out[0, n) and, with planes, their
-// three bf16 pieces (randn_quad's values)
-__device__ __forceinline__ void randn_quad_planes(float* __restrict__ out, int64_t n, uint64_t seed,
-                                                  uint64_t offset, int64_t q, const EpsPlanes& P,
-                                                  uint16_t* __restrict__ planes) {
-    const uint64_t ctr = offset / 4 + (uint64_t)q;
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    float r[4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float u1 = ((float)(c[2 * j] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-        const float u2 = (float)(c[2 * j + 1] >> 8) * (1.0f / 16777216.0f);
-        const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
-        r[2 * j] = rad * __builtin_amdgcn_cosf(u2);
-        r[2 * j + 1] = rad * __builtin_amdgcn_sinf(u2);
-    }
-    const int64_t base = q * 4;
-    if (base + 3 < n) {
-        *reinterpret_cast<float4*>(out + base) = make_float4(r[0], r[1], r[2], r[3]);
-    } else {
-        for (int j = 0; j < 4 && base + j < n; ++j) out[base + j] = r[j];
-    }
-    if (!planes) return;
-    // element i's place in the planes (selects over the layers: a dynamic
-    // index into P would put it in scratch)
-    auto place = [&](int64_t i, int& c, int& nl) -> int64_t {
+// Element i's place in the planes for the layers of an EpsPlanes (selects over
+// the layers: a dynamic index into P would put it in scratch).  The row
+// division runs on 32 bits when the whole draw is below 2^31 elements.
+struct EpsPlaneMap {
+    const EpsPlanes& P;
+    bool small;  // uniform: the draw's length < 2^31
+    __device__ __forceinline__ int64_t operator()(int64_t i, int& c, int& nl) const {
         int64_t e0 = P.eoff[0], po = P.poff[0];
         int np = P.npad[0];
         nl = P.n[0];
@@ -257,10 +243,28 @@ __device__ __forceinline__ void randn_quad_planes(float* __restrict__ out, int64
                 nl = P.n[k];
             }
         const int64_t rem = i - e0;
-        const int s = (int)(rem / nl);
+        const int s = small ? (int)((uint32_t)rem / (uint32_t)nl) : (int)(rem / nl);
         c = (int)(rem - (int64_t)s * nl);
         return po + (int64_t)s * np + c;
-    };
+    }
+};
+
+// normals 4q .. 4q+3 of the stream into out[0, n) and, with planes, their
+// three bf16 pieces (randn_quad's values); place(i, c, nl): element i's offset
+// in a plane, its column c and its row's length nl; pl: elements per plane
+template <class Place>
+__device__ __forceinline__ void randn_quad_planes_at(float* __restrict__ out, int64_t n, uint64_t seed,
+                                                     uint64_t offset, int64_t q, const Place& place,
+                                                     int64_t pl, uint16_t* __restrict__ planes) {
+    float r[4];
+    randn_quad_vals(seed, offset, q, r);
+    const int64_t base = q * 4;
+    if (base + 3 < n) {
+        *reinterpret_cast<float4*>(out + base) = make_float4(r[0], r[1], r[2], r[3]);
+    } else {
+        for (int j = 0; j < 4 && base + j < n; ++j) out[base + j] = r[j];
+    }
+    if (!planes) return;
     uint16_t pc[3][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) split3(r[j], pc[0][j], pc[1][j], pc[2][j]);
@@ -270,7 +274,7 @@ __device__ __forceinline__ void randn_quad_planes(float* __restrict__ out, int64
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
             typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<u16x4*>(planes + p * P.pl + o) = u16x4{pc[p][0], pc[p][1], pc[p][2], pc[p][3]};
+            *reinterpret_cast<u16x4*>(planes + p * pl + o) = u16x4{pc[p][0], pc[p][1], pc[p][2], pc[p][3]};
         }
         return;
     }
@@ -280,8 +284,13 @@ __device__ __forceinline__ void randn_quad_planes(float* __restrict__ out, int64
         int cj, nj;
         const int64_t oj = place(base + j, cj, nj);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) planes[p * P.pl + oj] = pc[p][j];
+        for (int p = 0; p < 3; ++p) planes[p * pl + oj] = pc[p][j];
     }
+}
+__device__ __forceinline__ void randn_quad_planes(float* __restrict__ out, int64_t n, uint64_t seed,
+                                                  uint64_t offset, int64_t q, const EpsPlanes& P,
+                                                  uint16_t* __restrict__ planes) {
+    randn_quad_planes_at(out, n, seed, offset, q, EpsPlaneMap{P, n < (int64_t(1) << 31)}, P.pl, planes);
 }
 
 // Adam, both reference variants; returns new p, updates m, v in place.
@@ -552,6 +561,7 @@ struct psvi_plan {
     // the loop also as three bf16 planes (EpsPlanes; device copy for the
     // network kernel's fused draw), two plane buffers in the loop workspace
     bool bf_stream = false;
+    bool eps_planes_ok = false;  // eps_planes describes this plan's draw (full-cov, world 1)
     psvi::EpsPlanes eps_planes{};
     psvi::EpsPlanes* d_eps_planes = nullptr;
     // psvi_inner_loop_ex(PSVI_LOOP_KEEP): what the last call left in its
@@ -621,7 +631,8 @@ hipError_t launch_mvn_tile_convert(const psvi_plan& p, float* params, float* m, 
                                    float* const* pads = nullptr);
 hipError_t launch_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st,
                         double* zero = nullptr, int64_t nzero = 0,
-                        const EpsPlanes* planes_desc = nullptr, uint16_t* planes = nullptr);
+                        const EpsPlanes* planes_desc = nullptr, uint16_t* planes = nullptr,
+                        int64_t q_lo = 0, int64_t q_hi = -1);  // quads [q_lo, q_hi) only (-1: all)
 hipError_t launch_adam(int64_t n, float* p, const float* g, float* m, float* v,
                        const psvi_adam_hp* hp, hipStream_t st);
 AdamC make_adam(const psvi_adam_hp* hp);

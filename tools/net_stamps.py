@@ -2,7 +2,11 @@
 """Per-phase shader-clock breakdown of the network kernel (s_memtime stamps,
 diagnostics API), optionally under ablation masks.
 
-  python tools/net_stamps.py [c3|c4] [abl,abl,...] [world rank]
+  python tools/net_stamps.py [c3|c4] [abl,abl,...] [world rank] [draw[:role1[:nospare]]]
+
+draw: the launch also draws the next step's eps and its bf16 planes, as the
+inner loop's does (role1: role 1's 32nds of the draw, PSVI_DBG_NET_DRAW_ROLE1;
+nospare: the whole draw behind the weight gradients, PSVI_DBG_NET_DRAW_SPARE_OFF).
 """
 import ctypes
 import os
@@ -44,7 +48,13 @@ def report(name, t, abl, S):
         for k, nm in ((4, "setup"), (11, "loads issued"), (5, "load loop"), (1, "load barrier"), (6, "fwd l0"), (7, "fwd l1"),
                       (8, "fwd l2"), (9, "head"), (10, "bwd"), (2, "chain barrier")):
             print(f"    wave0 @ {nm:13s} {float(d[:, k].median()):8.0f}")
-        sk = (r[:, 15].double() - r[:, 0].double())
+        # slot 15: two 32-bit spans from slot 0 -- low the last wave's start,
+        # high the draw wave's finish (0: no wave without a row tile drew)
+        sk = (r[:, 15] & 0xFFFFFFFF).double()
+        df = (r[:, 15] >> 32).double()
+        if float(df.max()) > 0:
+            print(f"  draw wave done  median {float(df.median()):.0f} max {float(df.max()):.0f}"
+                  f"  (chain barrier - draw wave done: median {float((d[:, 2] - df).median()):.0f})")
         print(f"  wave launch skew (last wave start - workgroup start) median {float(sk.median()):.0f} max {float(sk.max()):.0f}")
         timeline(r, 13, 14)
         # workgroups that started late (a second round on their CU): warm caches
@@ -81,6 +91,7 @@ def main():
     # plan (x_recv from every source rank, gradients through the band table)
     world = int(sys.argv[3]) if len(sys.argv) > 3 else 1
     rank = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+    draw = sys.argv[5].split(":") if len(sys.argv) > 5 else None
     layers, S, M = CFG[name]
     if world > 1 and name == "c3":
         S = 128 * world
@@ -96,12 +107,22 @@ def main():
     S = plan.s_local
     nblk = S * 8
     st = torch.zeros(nblk * 16, dtype=torch.int64, device=dev)
+    kw = {}
+    if draw:
+        kw["draw"] = (torch.empty(plan.eps_count, device=dev), 1, 0)
+        if world == 1:  # the planes too (64-column row pads, three planes)
+            npl = sum((a * b + b + 63) // 64 * 64 for a, b in layers) * plan.S
+            planes = torch.zeros(3 * ((npl + 63) // 64 * 64), dtype=torch.int16, device=dev)
+            plan.lib.psvi_debug_set_ptr(35, ctypes.c_void_p(planes.data_ptr()))
+        if len(draw) > 1 and draw[1]:
+            plan.lib.psvi_debug_set(36, int(draw[1]))
+        plan.lib.psvi_debug_set(37, 1 if len(draw) > 2 and draw[2] == "nospare" else 0)
     for abl in abls:
         plan.lib.psvi_debug_set(1, abl)
-        plan.mvn_net(u, z, w, xs, gs, nll)
+        plan.mvn_net(u, z, w, xs, gs, nll, **kw)
         st.zero_()
         plan.lib.psvi_debug_set_ptr(2, ctypes.c_void_p(st.data_ptr()))
-        plan.mvn_net(u, z, w, xs, gs, nll)
+        plan.mvn_net(u, z, w, xs, gs, nll, **kw)
         torch.cuda.synchronize()
         plan.lib.psvi_debug_set_ptr(2, None)
         plan.lib.psvi_debug_set(1, 0)
