@@ -849,6 +849,32 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world, int3
     return 0;
 }
 
+int psvi_plan_create_lik(int32_t family, const psvi_net_desc* d, int32_t world, int32_t rank,
+                         const psvi_likelihood* lik, psvi_plan** out) {
+    if (!lik || lik->kind == PSVI_LIK_CATEGORICAL)
+        return psvi_plan_create(family, d, world, rank, out);
+    if (!out) return fail(PSVI_EINVAL, "null out");
+    *out = nullptr;
+    if (lik->kind != PSVI_LIK_GAUSSIAN) return fail(PSVI_EINVAL, "unknown likelihood kind");
+    if (family != PSVI_FAMILY_MEANFIELD && family != PSVI_FAMILY_FULLCOV &&
+        family != PSVI_FAMILY_LENET)
+        return fail(PSVI_EINVAL, "unknown family");
+    if (family != PSVI_FAMILY_MEANFIELD)
+        return fail(PSVI_EUNSUP, "the Gaussian likelihood runs mean-field plans only");
+    if (int rc = check_desc(d)) return rc;
+    if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world)
+        return fail(PSVI_EINVAL, "world/rank out of range (world <= 8)");
+    if (world != 1) return fail(PSVI_EUNSUP, "the Gaussian likelihood needs world == 1");
+    if (d->dims[d->n_layers] != 1)
+        return fail(PSVI_EINVAL, "the Gaussian likelihood has one output (dims[n_layers] == 1)");
+    if (!(lik->tau > 0.f) || !std::isfinite(lik->tau))
+        return fail(PSVI_EINVAL, "the Gaussian precision tau must be positive and finite");
+    if (int rc = psvi_plan_create(family, d, world, rank, out)) return rc;
+    (*out)->lik = PSVI_LIK_GAUSSIAN;
+    (*out)->lik_tau = lik->tau;
+    return 0;
+}
+
 int psvi_plan_destroy(psvi_plan* p) {
     if (!p) return 0;
     if (p->d_fwd) (void)hipFree(p->d_fwd);
@@ -896,6 +922,7 @@ static size_t tiled_floats(const psvi_plan* p);
 struct OuterWs {
     float *nll, *rowcoef, *ck, *sck, *du;
     double* stats;
+    float* dz;  // Gaussian plans: per-sample target gradients [S][M]
     size_t bytes;
 };
 static OuterWs outer_ws(const psvi_plan* p, void* ws);
@@ -904,6 +931,7 @@ static OuterWs outer_ws(const psvi_plan* p, void* ws);
 // [splits][S][n_tot], d_u parts [S][M][D], NLL_dot [S][M]
 struct HvpWs {
     float *xd, *G, *Gd, *du, *nlld;
+    float* dzd;    // Gaussian plans: per-sample target products [S][M]
     float* part2;  // full-cov: split-K slots of the tangent sample (pair launch)
     size_t bytes;
 };
@@ -927,6 +955,7 @@ static HvpWs hvp_ws(const psvi_plan* p, void* ws) {
     o.Gd = (float*)take(sizeof(float) * ns * S * nt);
     o.du = (float*)take(sizeof(float) * S * M * D);
     o.nlld = (float*)take(sizeof(float) * S * M);
+    if (p->lik == PSVI_LIK_GAUSSIAN) o.dzd = (float*)take(sizeof(float) * S * M);
     if (p->family == PSVI_FAMILY_FULLCOV)
         o.part2 = (float*)take(sizeof(float) *
                                std::max({(size_t)p->n_fwd * S, (size_t)p->n_fp_slots * kKsPass,
@@ -962,6 +991,7 @@ static OuterWs outer_ws(const psvi_plan* p, void* ws) {
     o.sck = (float*)take(sizeof(float));
     o.stats = (double*)take(sizeof(double) * 2 * S);
     o.du = (float*)take(sizeof(float) * S * M * D);
+    if (p->lik == PSVI_LIK_GAUSSIAN) o.dz = (float*)take(sizeof(float) * S * M);
     o.bytes = off;
     return o;
 }
@@ -987,6 +1017,7 @@ int psvi_plan_query(const psvi_plan* p, int32_t key, int64_t* value) {
         case PSVI_Q_NET_PART_OK:
             *value = p->family == PSVI_FAMILY_FULLCOV && !(p->mchunks > 1 && !p->net_mloop);
             break;
+        case PSVI_Q_NET_MCHUNKS: *value = p->mchunks; break;
         default: return fail(PSVI_EINVAL, "unknown query key");
     }
     return 0;
@@ -1486,7 +1517,7 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
                       const float* params, double* loss_out, float* grad_params,
                       float* grad_u, float* grad_w, double* sample_out,
                       const float* ext_coef, void* ws, size_t ws_bytes, void* stream,
-                      int ablated = 0) {
+                      int ablated = 0, float* grad_z = nullptr) {
     drop_resident(p);
     if (!p) return fail(PSVI_EINVAL, "null plan");
     if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
@@ -1498,6 +1529,12 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
         return fail(PSVI_EINVAL, "null pointer");
     if (grad_u && !grad_params)
         return fail(PSVI_EINVAL, "grad_u needs grad_params (one backward pass gives both)");
+    if (grad_z && p->lik != PSVI_LIK_GAUSSIAN)
+        return fail(PSVI_ESTATE, "grad_z needs a Gaussian-likelihood plan");
+    if (grad_z && !grad_params)
+        return fail(PSVI_EINVAL, "grad_z needs grad_params (one backward pass gives both)");
+    if (ablated && p->lik == PSVI_LIK_GAUSSIAN)
+        return fail(PSVI_EUNSUP, "the ablated outer objective has no Gaussian-likelihood form");
     const OuterWs o = outer_ws(p, ws);
     if (!ws || ws_bytes < o.bytes) return fail(PSVI_ENOSPC, "workspace too small");
     hipStream_t st = as_stream(stream);
@@ -1538,7 +1575,8 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
     }
     if (!grad_params) return 0;
     // 3. backward through the network with the row coefficients (+ sampled-KL path)
-    NetOuter bw{2, n_pseudo, nullptr, o.rowcoef, o.ck, grad_u ? o.du : nullptr};
+    NetOuter bw{2, n_pseudo, nullptr, o.rowcoef, o.ck, grad_u ? o.du : nullptr, nullptr,
+                grad_z ? o.dz : nullptr};
     if (p->family == PSVI_FAMILY_FULLCOV) {
         HIP_TRY(launch_net(*p, x_all, z_all, w_all, nullptr, nullptr, nullptr, x, g, nullptr, st,
                            nullptr, 0, 0, 0, &bw));
@@ -1558,6 +1596,7 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
     }
     // 5. explicit log-det term on the scales; d loss / d u
     HIP_TRY(launch_outer_finish(*p, n_pseudo, params, o.sck, grad_params, o.du, grad_u, st));
+    if (grad_z) HIP_TRY(launch_sample_sum(p->d.S, n_pseudo, o.dz, grad_z, st));
     return 0;
 }
 
@@ -1568,8 +1607,18 @@ int psvi_outer_elbo_grad(const psvi_plan* p, int32_t n_pseudo, const float* x_al
                          const float* params, double* loss_out, float* grad_params,
                          float* grad_u, float* grad_w, double* sample_out, void* ws,
                          size_t ws_bytes, void* stream) {
+    return psvi_outer_elbo_grad_ex(p, n_pseudo, x_all, z_all, w_all, eps, params, loss_out,
+                                   grad_params, grad_u, grad_w, nullptr, sample_out, ws, ws_bytes,
+                                   stream);
+}
+
+int psvi_outer_elbo_grad_ex(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
+                            const int32_t* z_all, const float* w_all, const float* eps,
+                            const float* params, double* loss_out, float* grad_params,
+                            float* grad_u, float* grad_w, float* grad_z, double* sample_out,
+                            void* ws, size_t ws_bytes, void* stream) {
     return outer_impl(p, n_pseudo, x_all, z_all, w_all, eps, params, loss_out, grad_params,
-                      grad_u, grad_w, sample_out, nullptr, ws, ws_bytes, stream);
+                      grad_u, grad_w, sample_out, nullptr, ws, ws_bytes, stream, 0, grad_z);
 }
 
 int psvi_outer_ablated_elbo_grad(const psvi_plan* p, const float* x_all,
@@ -1588,9 +1637,19 @@ int psvi_outer_elbo_grad_coef(const psvi_plan* p, int32_t n_pseudo, const float*
                               const float* params, const float* coef, float* grad_params,
                               float* grad_u, float* grad_w, void* ws, size_t ws_bytes,
                               void* stream) {
+    return psvi_outer_elbo_grad_coef_ex(p, n_pseudo, x_all, z_all, w_all, eps, params, coef,
+                                        grad_params, grad_u, grad_w, nullptr, ws, ws_bytes,
+                                        stream);
+}
+
+int psvi_outer_elbo_grad_coef_ex(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
+                                 const int32_t* z_all, const float* w_all, const float* eps,
+                                 const float* params, const float* coef, float* grad_params,
+                                 float* grad_u, float* grad_w, float* grad_z, void* ws,
+                                 size_t ws_bytes, void* stream) {
     if (!coef) return fail(PSVI_EINVAL, "null coefficients");
     return outer_impl(p, n_pseudo, x_all, z_all, w_all, eps, params, nullptr, grad_params,
-                      grad_u, grad_w, nullptr, coef, ws, ws_bytes, stream);
+                      grad_u, grad_w, nullptr, coef, ws, ws_bytes, stream, 0, grad_z);
 }
 
 int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, const int32_t* z_all,
@@ -1600,6 +1659,9 @@ int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, cons
     if (!p) return fail(PSVI_EINVAL, "null plan");
     if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
     if (p->world != 1) return fail(PSVI_ESTATE, "evaluate needs world == 1");
+    if (p->lik != PSVI_LIK_CATEGORICAL)
+        return fail(PSVI_ESTATE, "a Gaussian-likelihood plan evaluates with "
+                                 "psvi_evaluate_regression");
     if (p->d.S < 2) return fail(PSVI_EINVAL, "evaluate needs S > 1 (psvi_classes.py:1036)");
     if (p->d.S > 2048) return fail(PSVI_EUNSUP, "evaluate supports S <= 2048");
     if (n_pseudo < 0 || n_pseudo > p->d.M) return fail(PSVI_EINVAL, "n_pseudo out of [0, M]");
@@ -1630,16 +1692,57 @@ int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, cons
     return 0;
 }
 
+int psvi_evaluate_regression(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
+                             const float* y_all, const float* w_all, const float* eps,
+                             const float* params, int32_t correction, float y_mean, float y_std,
+                             float* pred_out, double* stats_out, void* ws, size_t ws_bytes,
+                             void* stream) {
+    drop_resident(p);
+    if (!p) return fail(PSVI_EINVAL, "null plan");
+    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (p->lik != PSVI_LIK_GAUSSIAN)
+        return fail(PSVI_ESTATE, "psvi_evaluate_regression needs a Gaussian-likelihood plan");
+    if (p->d.S < 2) return fail(PSVI_EINVAL, "evaluate needs S > 1 (psvi_classes.py:2229)");
+    if (p->d.S > 2048) return fail(PSVI_EUNSUP, "evaluate supports S <= 2048");
+    if (n_pseudo < 0 || n_pseudo > p->d.M) return fail(PSVI_EINVAL, "n_pseudo out of [0, M]");
+    if (!x_all || !y_all || !w_all || !eps || !params || !stats_out)
+        return fail(PSVI_EINVAL, "null pointer");
+    if (!ws || ws_bytes < eval_ws_bytes(p)) return fail(PSVI_ENOSPC, "workspace too small");
+    hipStream_t st = as_stream(stream);
+    const OuterWs o = outer_ws(p, ws);
+    char* wsb = (char*)ws;
+    float* f = (float*)(wsb + eval_prob_off(p));  // the data rows' outputs [S][M - n_pseudo]
+    float* W = (float*)(wsb + eval_prob_off(p) +
+                        align256(sizeof(float) * (size_t)p->d.S * p->d.M));
+    HIP_TRY(launch_outer_stats(*p, params, eps, nullptr, o.stats, st));
+    NetOuter fw{1, n_pseudo, o.nll, nullptr, nullptr, nullptr, f};
+    HIP_TRY(launch_net(*p, x_all, reinterpret_cast<const int32_t*>(y_all), w_all, params, eps,
+                       nullptr, nullptr, nullptr, nullptr, st, nullptr, 0, 0, 0, &fw));
+    HIP_TRY(launch_eval_regression(*p, n_pseudo, params, y_all + n_pseudo, o.stats, f,
+                                   correction ? 1 : 0, y_mean, y_std, W, pred_out, stats_out, st));
+    return 0;
+}
+
 int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,
                      size_t ws_bytes, void* stream) {
+    return psvi_hvp_ex(p, u, z, w, eps, params, vec, include_kl, hv_out, du_out, dw_out, nullptr,
+                       ws, ws_bytes, stream);
+}
+
+int psvi_hvp_ex(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
+                const float* eps, const float* params, const float* vec, int32_t include_kl,
+                float* hv_out, float* du_out, float* dw_out, float* dz_out, void* ws,
+                size_t ws_bytes, void* stream) {
     drop_resident(p);
     if (!p) return fail(PSVI_EINVAL, "null plan");
     if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
     if (p->world != 1) return fail(PSVI_ESTATE, "psvi_hvp needs world == 1");
     if (!u || !z || !w || !eps || !params || !vec || !hv_out)
         return fail(PSVI_EINVAL, "null pointer");
+    if (dz_out && p->lik != PSVI_LIK_GAUSSIAN)
+        return fail(PSVI_ESTATE, "dz_out needs a Gaussian-likelihood plan");
     if (p->family == PSVI_FAMILY_LENET) {
         if (!ws || ws_bytes < lenet_tan_ws(*p, nullptr).bytes)
             return fail(PSVI_ENOSPC, "workspace too small");
@@ -1665,7 +1768,8 @@ int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const
                      (p->family != PSVI_FAMILY_FULLCOV || mvn_grad_takes_slots(*p));
     const int64_t slot2 = two ? (int64_t)p->d.S * p->n_tot : 0;
     HIP_TRY(launch_net_rop(*p, u, z, w, x, o.xd, params, vec, eps, o.G, o.Gd,
-                           du_out ? o.du : nullptr, dw_out ? o.nlld : nullptr, st, !two));
+                           du_out ? o.du : nullptr, dw_out ? o.nlld : nullptr, st, !two,
+                           dz_out ? o.dzd : nullptr));
     if (p->family == PSVI_FAMILY_FULLCOV)  // J^T G_dot (mean, sd, corr; + the corr KL block)
         HIP_TRY(launch_mvn_update(*p, eps, o.Gd, const_cast<float*>(params), nullptr, nullptr,
                                   nullptr, nullptr, hv_out, 0, nullptr, nullptr, st, nullptr,
@@ -1673,6 +1777,8 @@ int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const
                                   two ? o.Gd + slot2 : nullptr));
     HIP_TRY(launch_hvp_assemble(*p, params, vec, eps, o.G, o.Gd, o.du, o.nlld, hv_out, du_out,
                                 dw_out, st, include_kl != 0, slot2));
+    // d/dz_m (vec . d elbo / d params) = -sum_s delta_dot_sm, in sample order
+    if (dz_out) HIP_TRY(launch_sample_sum(p->d.S, p->d.M, o.dzd, dz_out, st));
     return 0;
 }
 

@@ -45,6 +45,7 @@
 // logits on a DPP row), else on VALU, one lane per row.  Weight gradients
 // leave straight from the MFMA accumulators.
 #include <algorithm>
+#include <cmath>
 
 #include "mfma_tiles.hpp"
 #include "psvi_internal.hpp"
@@ -127,6 +128,12 @@ struct NetArgs {
     // the fused draw also as bf16 planes (the bf16-plane streaming update)
     const EpsPlanes* rn_P;
     uint16_t* rn_planes;
+    // Gaussian likelihood (net_kernel<..., LIK = PSVI_LIK_GAUSSIAN>; last, so the
+    // categorical kernels' argument offsets stay put): NLL = lik_tau / 2 (f - z)^2
+    // + lik_c, lik_c = log(2 pi / tau) / 2; z holds the fp32 targets' bits;
+    // dz_part (outer backward, nullable): [S][n_pseudo] d loss_s / d z_m
+    float lik_tau, lik_c;
+    float* dz_part;
 };
 
 // ---- LDS carve (float offsets, row strides) of the network kernel.  Row
@@ -506,8 +513,13 @@ __device__ __forceinline__ int64_t fc_addr(const NetArgs& a, int nsrc, const int
 // instantiation has straight-line x loads: with the run-table path in the
 // same kernel the register allocator shares registers across the two paths
 // and the waitcnt pass then serialises the u and x loads (seen in the ISA).
-template <int FAM, bool MSRC, bool VEC = false, bool MLOOP = false, int GEO = 0>
+// LIK: the loss head (PSVI_LIK_CATEGORICAL; PSVI_LIK_GAUSSIAN: one output,
+// mean-field only -- its own instantiation, the categorical ones are unchanged)
+template <int FAM, bool MSRC, bool VEC = false, bool MLOOP = false, int GEO = 0,
+          int LIK = PSVI_LIK_CATEGORICAL>
 __global__ __launch_bounds__(512) void net_kernel(NetArgs a) {
+    static_assert(LIK == PSVI_LIK_CATEGORICAL || (FAM == PSVI_FAMILY_MEANFIELD && GEO == 0),
+                  "the Gaussian head: mean-field, run-time geometry");
     using Geo = NetGeo<GEO>;
     const Geo g(a);
     constexpr int kUL = Geo::kUnroll;  // layer loops: fully unrolled for a fixed geometry
@@ -1028,7 +1040,23 @@ chunk_top:// a backward jump only when MLOOP (no loop at all in the other instan
             float* Xn = (head ? sm + g.ldl() : sm + g.lx(l + 1)) + r0 * (head ? g.lddl() : g.ldx(l + 1));
             const float* Bv = sm + g.lb(l);
             const int ldn = head ? g.lddl() : g.ldx(l + 1), jend = min((dout + 15) & ~15, ldn);
-            if (head && fuse_head) {
+            if (LIK == PSVI_LIK_GAUSSIAN && head && fuse_head) {
+                // Gaussian head (C = 1: the output f on lane j = 0 of the row's
+                // 16): NLL = tau / 2 (f - z)^2 + c, dlogit = w tau (f - z)
+                auto epi = [&](int m, int j, floatx4 v, int rot) {
+                    const float b = Bv[0];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = m + ((r + rot) & 3), rg = r0 + row;
+                        const float d = v[r] + b - zw[rg];
+                        const float wr = zw[Mp + rg];
+                        const bool ok = rg < mcnt && j == 0;
+                        if (j < jend) Xn[row * ldn + j] = ok ? wr * (a.lik_tau * d) : 0.f;
+                        if (ok) part += wr * (0.5f * a.lik_tau * d * d + a.lik_c);
+                    }
+                };
+                row_gemm<true, true>(dout, din, X, g.ldx(l), sm + g.lw(l), g.ldw(l), epi);
+            } else if (head && fuse_head) {
                 // the row's logits sit on lanes j < C of its 16: the reductions
                 // span the smallest power of two >= C (the fixed geometry: C = 2,
                 // one lane exchange) -- a row of 16 otherwise
@@ -1071,7 +1099,29 @@ chunk_top:// a backward jump only when MLOOP (no loop at all in the other instan
         }
         // ---- loss head on VALU (C > 16, the outer objective): lanes 0..15
         // take the tile's rows, logits -> weighted NLL, dlogits in place
-        if (!fuse_head && !(a.abl & 4) && lane < 16 && r0 + lane < mcnt) {
+        if (LIK == PSVI_LIK_GAUSSIAN && !fuse_head && !(a.abl & 4) && lane < 16 &&
+            r0 + lane < mcnt) {
+            // Gaussian head on VALU (the outer objective): the output f in column 0
+            const int m = r0 + lane, mg = m0 + m;
+            float* row = sm + g.ldl() + m * g.lddl();
+            const float f = row[0], d = f - zw[m];
+            const float nll = 0.5f * a.lik_tau * d * d + a.lik_c;
+            if (a.outer == 1) {
+                a.nll_rows[(size_t)s * a.M + mg] = nll;
+                // evaluate: the raw output of the data rows [S][M - n_pseudo][1]
+                if (a.prob_rows && mg >= a.n_pseudo)
+                    a.prob_rows[(size_t)s * (a.M - a.n_pseudo) + mg - a.n_pseudo] = f;
+            } else {
+                const float wm = zw[Mp + m] * (mg < a.n_pseudo ? cp : cd);
+                const float dl = wm * (a.lik_tau * d);
+                part += wm * nll;
+                row[0] = dl;
+                // d NLL / d z = -d NLL / d f (the role that owns layer 0 writes)
+                if (a.outer == 2 && a.dz_part && own_lo == 0 && mg < a.n_pseudo)
+                    a.dz_part[(size_t)s * a.n_pseudo + mg] = -dl;
+            }
+        } else if (LIK != PSVI_LIK_GAUSSIAN && !fuse_head && !(a.abl & 4) && lane < 16 &&
+                   r0 + lane < mcnt) {
             const int m = r0 + lane;
             const int ldl = g.lddl();
             float* row = sm + g.ldl() + m * ldl;
@@ -1426,6 +1476,9 @@ void net_set_lds_limit() {
     // gfx950: up to 160 KiB of LDS per workgroup
     (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_MEANFIELD, false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_GAUSSIAN>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, true>,
@@ -1491,6 +1544,15 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
         a.ck = outer->ck;
         a.du_part = outer->du_part;
         a.prob_rows = outer->prob_rows;
+        a.dz_part = outer->dz_part;
+    }
+    if (p.lik == PSVI_LIK_GAUSSIAN) {
+        if (p.family != PSVI_FAMILY_MEANFIELD || p.lay[p.L - 1].dout != 1)
+            return hipErrorInvalidValue;
+        a.lik_tau = p.lik_tau;
+        a.lik_c = (float)(0.5 * std::log(2.0 * 3.14159265358979323846 / (double)p.lik_tau));
+    } else if (a.dz_part) {
+        return hipErrorInvalidValue;
     }
     a.inv_s0sq = 1.f / (p.d.prior_sd * p.d.prior_sd);
     a.rn_out = rn_out;  // 16-byte aligned (workspace buffers)
@@ -1596,7 +1658,11 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
         a.rn_rem0 = (int)(c0 % nper);
         a.rn_spare = g_net_draw_spare_off ? 0 : 1;
     }
-    if (p.family == PSVI_FAMILY_MEANFIELD)
+    if (p.family == PSVI_FAMILY_MEANFIELD && p.lik == PSVI_LIK_GAUSSIAN)
+        hipLaunchKernelGGL(
+            (net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_GAUSSIAN>), grid,
+            block, p.net_lds, st, a);
+    else if (p.family == PSVI_FAMILY_MEANFIELD)
         hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_MEANFIELD, false>), grid, block, p.net_lds, st, a);
     else if (fn2 && loop && p.world > 1)
         hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, true, true, true, 2>), grid, block, p.net_lds, st, a);

@@ -303,6 +303,52 @@ __global__ __launch_bounds__(256) void eval_predict_kernel(OuterArgs a, const fl
 
 static void fill(const psvi_plan& p, OuterArgs& a);
 
+// Gaussian plans (PSVI_regressor.evaluate, psvi_classes.py:2221-2264): one
+// thread per test row, y_pred = sum_s W_s (f_s y_std + y_mean) in sample
+// order, then the squared error and log N(y; y_pred, 1 / sqrt(tau)) in doubles
+__global__ __launch_bounds__(256) void eval_regress_kernel(int S, int nt, const float* W,
+                                                           const float* f, const float* y,
+                                                           float y_mean, float y_std, float tau,
+                                                           float* pred_out, double* out) {
+    __shared__ double red[16];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    double se = 0.0, ll = 0.0;
+    if (j < nt) {
+        float p = 0.f;
+        for (int s = 0; s < S; ++s) p = fmaf(W[s], f[(size_t)s * nt + j] * y_std + y_mean, p);
+        if (pred_out) pred_out[j] = p;
+        const double d = (double)p - (double)y[j];
+        se = d * d;
+        ll = -0.5 * (double)tau * d * d - 0.5 * log(2.0 * 3.14159265358979323846 / (double)tau);
+    }
+    se = block_sum_all(se, red);
+    ll = block_sum_all(ll, red);
+    if (threadIdx.x == 0) {
+        atomicAdd(out + 2, se);
+        atomicAdd(out + 3, ll);
+    }
+}
+
+hipError_t launch_eval_regression(const psvi_plan& p, int n_pseudo, const float* params,
+                                  const float* y, const double* stats, const float* f,
+                                  int correction, float y_mean, float y_std, float* W,
+                                  float* pred_out, double* out, hipStream_t st) {
+    if (p.d.S > kOuterMaxS) return hipErrorInvalidValue;
+    OuterArgs a{};
+    fill(p, a);
+    // the reference's pseudo term is summed over the samples too -- one scalar,
+    // which the softmax over samples drops: W = softmax_s(sampled_nkl_s)
+    a.n_pseudo = 0;
+    a.params = params;
+    a.stats = const_cast<double*>(stats);
+    hipLaunchKernelGGL(eval_weights_kernel, dim3(1), dim3(1024), 0, st, a, correction, W, out);
+    const int nt = p.d.M - n_pseudo;
+    if (nt > 0)
+        hipLaunchKernelGGL(eval_regress_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, p.d.S,
+                           nt, W, f, y, y_mean, y_std, p.lik_tau, pred_out, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_eval(const psvi_plan& p, int n_pseudo, const float* params, const float* w,
                        const int32_t* z, const float* nll, const double* stats,
                        const float* prob, int correction, float* W, float* probs_out,
@@ -421,6 +467,23 @@ hipError_t launch_outer_finish(const psvi_plan& p, int n_pseudo, const float* pa
     const int nu = grad_u ? n_pseudo * plan_in_dim(p) : 0;
     const int n = p.n_tot + nu;
     hipLaunchKernelGGL(outer_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a, nu);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void sample_sum_kernel(int S, int n,
+                                                         const float* __restrict__ part,
+                                                         float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float g = 0.f;
+    for (int s = 0; s < S; ++s) g += part[(size_t)s * n + i];
+    out[i] = g;
+}
+
+hipError_t launch_sample_sum(int S, int n, const float* part, float* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sample_sum_kernel, dim3((n + 255) / 256), dim3(256), 0, st, S, n, part,
+                       out);
     return hipGetLastError();
 }
 

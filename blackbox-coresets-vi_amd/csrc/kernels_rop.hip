@@ -60,6 +60,12 @@ struct RopArgs {
     float* du;         // [S][M][D]
     float* nlld;       // [S][M]
     unsigned long long* stamps;  // diagnostics: 16 phase-clock sums per workgroup (nullptr)
+    // Gaussian plans (C = 1): z holds the fp32 targets' bits; delta = w tau (f - z),
+    // delta_dot = w tau f_dot; dzd (nullable) [S][M] <- -delta_dot, the mixed
+    // product's per-sample share w.r.t. the targets
+    int lik;
+    float tau;
+    float* dzd;
 };
 
 unsigned long long* g_rop_stamps = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_ROP_STAMPS, buf)
@@ -297,8 +303,17 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
         for (int m = tid; m < rc; m += nt) {
             const float* lg = sm + a.lh[L] + m * C;
             const float* ld = sm + a.lhd[L] + m * C;
-            const int zm = a.z[m0 + m];
             const float wm = a.w[m0 + m];
+            if (a.lik == PSVI_LIK_GAUSSIAN) {
+                const float d = a.tau * (lg[0] - __int_as_float(a.z[m0 + m]));
+                const float dd = wm * (a.tau * ld[0]);
+                Dl[m * a.maxd] = wm * d;
+                DDl[m * a.maxd] = dd;
+                if (a.nlld) a.nlld[(int64_t)s * a.M + m0 + m] = d * ld[0];
+                if (a.dzd) a.dzd[(int64_t)s * a.M + m0 + m] = -dd;
+                continue;
+            }
+            const int zm = a.z[m0 + m];
             float mx = -INFINITY;
             for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
             float se = 0.f;
@@ -845,8 +860,18 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
     for (int m = tid; m < rc; m += nt) {
         float* lg = sm + a.mxo[L] + m * a.ldxm[L];
         float* ld = lg + a.kx[L];
-        const int zm = a.z[m0 + m];
         const float wm = a.w[m0 + m];
+        if (a.lik == PSVI_LIK_GAUSSIAN) {
+            const float fd = ld[0];
+            const float d = a.tau * (lg[0] - __int_as_float(a.z[m0 + m]));
+            const float dd = wm * (a.tau * fd);
+            lg[0] = wm * d;
+            ld[0] = dd;
+            if (a.nlld) a.nlld[(int64_t)s * a.M + m0 + m] = d * fd;
+            if (a.dzd) a.dzd[(int64_t)s * a.M + m0 + m] = -dd;
+            continue;
+        }
+        const int zm = a.z[m0 + m];
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
         float se = 0.f;
@@ -1220,6 +1245,8 @@ static void rop_fill(const psvi_plan& p, RopArgs& a) {
     a.S = p.d.S;
     a.n_tot = p.n_tot;
     a.family = p.family;
+    a.lik = p.lik;
+    a.tau = p.lik_tau;
     for (int l = 0; l < p.L; ++l) {
         a.din[l] = p.lay[l].din;
         a.dout[l] = p.lay[l].dout;
@@ -1232,7 +1259,8 @@ static void rop_fill(const psvi_plan& p, RopArgs& a) {
 hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
                           const float* x, const float* xd, const float* params, const float* vec,
                           const float* eps, float* G, float* Gd, float* du, float* nlld,
-                          hipStream_t st, bool sum_slots) {
+                          hipStream_t st, bool sum_slots, float* dzd) {
+    if (dzd && p.lik != PSVI_LIK_GAUSSIAN) return hipErrorInvalidValue;
     static bool once = [] {
         (void)hipFuncSetAttribute((const void*)net_rop_kernel,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRopLds);
@@ -1254,7 +1282,7 @@ hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, 
         if (g_rop_valu != 1 && lds <= kRopLds) {
             a.u = u; a.z = z; a.w = w; a.x = x; a.xd = xd;
             a.params = params; a.vec = vec; a.eps = eps;
-            a.G = G; a.Gd = Gd; a.du = du; a.nlld = nlld;
+            a.G = G; a.Gd = Gd; a.du = du; a.nlld = nlld; a.dzd = dzd;
             a.stamps = g_rop_stamps;
             a.single = 1;
             const dim3 grid(p.d.S, a.nsplit), block(512);
@@ -1282,7 +1310,7 @@ hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, 
     a.single = single ? 1 : 0;
     a.u = u; a.z = z; a.w = w; a.x = x; a.xd = xd;
     a.params = params; a.vec = vec; a.eps = eps;
-    a.G = G; a.Gd = Gd; a.du = du; a.nlld = nlld;
+    a.G = G; a.Gd = Gd; a.du = du; a.nlld = nlld; a.dzd = dzd;
     a.stamps = g_rop_stamps;
     hipLaunchKernelGGL(net_rop_kernel, dim3(p.d.S, a.nsplit), dim3(512), lds, st, a);
     if (a.nsplit > 1 && sum_slots) {

@@ -442,12 +442,18 @@ struct NetOuter {
     const float* ck;      // mode 2: [S] d loss / d nkl_s
     float* du_part;       // mode 2, nullable: [S][n_pseudo][D] input gradient
     float* prob_rows;     // mode 1, nullable: [S][M - n_pseudo][C] softmax of the data rows
+                          // (Gaussian plans: the raw output f, C = 1)
+    float* dz_part;       // mode 2, nullable, Gaussian plans: [S][n_pseudo] d loss_s / d z_m
 };
 
 }  // namespace psvi
 
 struct psvi_plan {
     int family = 0;
+    // observation model (psvi_plan_create_lik): PSVI_LIK_GAUSSIAN plans are
+    // mean-field, C = 1, world 1; z / z_all then point to fp32 targets
+    int lik = PSVI_LIK_CATEGORICAL;
+    float lik_tau = 1.f;
     psvi_net_desc d{};
     int world = 1, rank = 0;
     int L = 0;
@@ -656,6 +662,16 @@ hipError_t launch_outer_gradw(const psvi_plan& p, int n_pseudo, const float* nll
 hipError_t launch_outer_finish(const psvi_plan& p, int n_pseudo, const float* params,
                                const float* sck, float* grad, const float* du_part,
                                float* grad_u, hipStream_t st);
+// out[m] = sum_s part[s][m] in sample order (one writer per element): the
+// target gradients of the outer backward and of the R-op
+hipError_t launch_sample_sum(int S, int n, const float* part, float* out, hipStream_t st);
+// psvi_evaluate_regression: W = softmax_s(sampled_nkl_s) (correction 0: 1 / S),
+// y_pred_j = sum_s W_s (f_sj y_std + y_mean); out[2] += sum_j (y_pred_j - y_j)^2,
+// out[3] += sum_j log N(y_j; y_pred_j, 1 / sqrt(tau))
+hipError_t launch_eval_regression(const psvi_plan& p, int n_pseudo, const float* params,
+                                  const float* y, const double* stats, const float* f,
+                                  int correction, float y_mean, float y_std, float* W,
+                                  float* pred_out, double* out, hipStream_t st);
 // LeNet (kernels_lenet.hip): scratch carve of the plan-owned buffer
 struct LenetWs {
     float *wsamp, *dws, *p1, *x2, *h1, *h2, *d, *dh2, *dh1, *dx2, *part;
@@ -704,7 +720,7 @@ int rop_splits(const psvi_plan& p);  // row blocks per sample: G / G_dot slots
 hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
                           const float* x, const float* xd, const float* params, const float* vec,
                           const float* eps, float* G, float* Gd, float* du, float* nlld,
-                          hipStream_t st, bool sum_slots = true);
+                          hipStream_t st, bool sum_slots = true, float* dzd = nullptr);
 hipError_t launch_hvp_assemble(const psvi_plan& p, const float* params, const float* vec,
                                const float* eps, const float* G, const float* Gd, const float* du,
                                const float* nlld, float* hv, float* d_u, float* d_w,

@@ -20,8 +20,12 @@ def _psvi(cls):
     return lambda *a, **kw: cls(*a, **kw).run_psvi(*a, **kw)
 
 
-# flow_psvi.py:306-354 (the regression variants and the selection baselines --
-# sparsevi, giga, opsvi, random, sparsebbvi -- are not on the HIP path)
+# flow_psvi.py:306-354.  Not wired here: the regression variants -- their
+# classes run on the HIP path (psvi.inference.PSVI_regressor,
+# PSVILearnV_regressor, PSVIAV_regressor), but the reference's regression
+# datasets are remote downloads and read_dataset returns no y_mean / y_std --
+# and the selection baselines (sparsevi, giga, opsvi, random, sparsebbvi),
+# which are not on the HIP path
 inf_dict = {
     "psvi": _psvi(PSVI),
     "psvi_ablated": _psvi(PSVI_Ablated),

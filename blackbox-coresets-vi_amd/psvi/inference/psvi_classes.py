@@ -55,6 +55,13 @@ What runs where
     label (its 2-d logits broadcast in Categorical.log_prob) -- reproduced as
     the standard objective over M*C expanded rows.
 
+  * The regressors (psvi_classes.py:1940-2335) ``PSVI_regressor``,
+    ``PSVILearnV_regressor`` and ``PSVIAV_regressor`` run on Gaussian-likelihood
+    plans (one output, fixed precision tau, real targets z learned with u):
+    the same objectives and ``nested_step`` with the targets' gradients
+    (``psvi_outer_elbo_grad_ex``, ``psvi_hvp_ex``'s dz), ``evaluate`` ->
+    (rmse, test_ll) on ``psvi_evaluate_regression``.
+
 ``inner_elbo`` is differentiable (first order) w.r.t. the parameters and,
 as the reference's autograd, w.r.t. u and v / alpha where they require grad
 (the row node ``HipInnerRows``); the trainers carry the hypergradients of u, v
@@ -76,12 +83,13 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from ..models.neural_net import (VILinear, VILinearMultivariateNormal, categorical_fn,
-                                 make_fc2net, make_fcnet, make_lenet, model_spec)
+                                 gaussian_fn, make_fc2net, make_fcnet, make_lenet,
+                                 make_regressor_net, model_spec)
 from ..runtime import InnerLoopPlan, adam_adjoint_, adam_update_, nonfinite_, randn_
 
 __all__ = ["PSVI", "PSVILearnV", "PSVIAV", "PSVIFreeV", "PSVI_No_Rescaling", "PSVI_Ablated",
-           "PSVI_No_IW", "PSVIFixedU", "PSVIAFixedU", "HipInnerELBO", "HipInnerRows",
-           "HipOuterELBO"]
+           "PSVI_No_IW", "PSVIFixedU", "PSVIAFixedU", "PSVI_regressor", "PSVILearnV_regressor",
+           "PSVIAV_regressor", "HipInnerELBO", "HipInnerRows", "HipOuterELBO"]
 
 class HipInnerELBO(torch.autograd.Function):
     """Negative inner ELBO as an autograd node over one psvi_elbo_grad call
@@ -1446,6 +1454,424 @@ class PSVIAFixedU(PSVILearnV):
     def evaluate(self, **kwargs):
         """psvi_classes.py:1761-1768: records alpha, then PSVI.evaluate."""
         self.results.setdefault("alpha", []).append(self.alpha.clone().cpu().detach().numpy())
+        return super().evaluate(**kwargs)
+
+
+# ------------------------------------------------------------- regression
+class HipInnerRowsZ(torch.autograd.Function):
+    """HipInnerRows of a Gaussian plan: the row pass also delivers the
+    gradient w.r.t. the pseudo targets z (dNLL/dz = -dNLL/df)."""
+
+    @staticmethod
+    def forward(ctx, u_g, w_g, z_g, rows_fn, dtype):
+        ctx.rows_fn = rows_fn
+        ctx.meta = [(t.shape, t.dtype) for t in (u_g, w_g, z_g)]
+        return torch.zeros((), dtype=dtype, device=u_g.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        gs = ctx.rows_fn()
+        out = [(gout * g).reshape(s).to(t) if need else None
+               for g, (s, t), need in zip(gs, ctx.meta, ctx.needs_input_grad)]
+        return out[0], out[1], out[2], None, None
+
+
+class HipOuterELBOZ(torch.autograd.Function):
+    """HipOuterELBO of a Gaussian plan: psvi_outer_elbo_grad_ex, whose
+    backward also reaches the pseudo targets z."""
+
+    @staticmethod
+    def forward(ctx, pvec, u, wp, zp, plan, xb, yb, w_data, eps):
+        Mu = u.shape[0]
+        x_all = torch.cat([u.detach().reshape(Mu, -1), xb]).to(torch.float32).contiguous()
+        z_all = torch.cat([zp.detach().reshape(-1).to(torch.float32), yb]).contiguous()
+        w_all = torch.cat([wp.detach().to(torch.float32), w_data]).contiguous()
+        out = plan.outer_elbo_grad(Mu, x_all, z_all, w_all, eps, pvec.detach().contiguous(),
+                                   grad=True, grad_u=True, grad_w=True, grad_z=True)
+        ctx.save_for_backward(out["grad"], out["grad_u"].reshape(u.shape), out["grad_w"],
+                              out["grad_z"].reshape(zp.shape))
+        ctx.dtypes = (pvec.dtype, u.dtype, wp.dtype, zp.dtype)
+        return out["loss"].to(pvec.dtype).reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        gs = [(gout * g).to(t) for g, t in zip(ctx.saved_tensors, ctx.dtypes)]
+        return gs[0], gs[1], gs[2], gs[3], None, None, None, None, None
+
+
+class PSVI_regressor(PSVI):
+    """PSVI for regression (psvi_classes.py:1940-2264): one network output f,
+    observation model Normal(f, 1 / sqrt(tau)), real-valued pseudo targets z
+    that are learned with u (``learn_z``, Adam ``optim_z``).  Runs on
+    Gaussian-likelihood HIP plans: mean-field models with one output
+    (make_regressor_net), world 1.  Keyword names follow the reference.
+
+    ``inner_elbo`` / ``psvi_elbo`` carry first-order gradients to the
+    parameters, u, v / alpha and z; ``nested_step`` is the reference's trainer
+    (T higher-Adam steps, the outer objective, reverse mode through the steps
+    with psvi_adam_adjoint + psvi_hvp_ex and its mixed products du, dw, dz);
+    ``evaluate`` returns (rmse, test_ll) in the targets' original units
+    (``y_mean`` / ``y_std``)."""
+
+    _steps_scheduler = False   # only PSVIAV_regressor.nested_step steps the net's scheduler
+
+    def __init__(self, u=None, z=None, train_dataset=None, val_dataset=None, test_dataset=None,
+                 y_mean=None, y_std=None, N=None, D=None, optim=None, optim_u=None,
+                 optim_net=None, optim_v=None, optim_z=None, register_elbos=False,
+                 num_pseudo=None, seed=0, compute_weights_entropy=True, mc_samples=None,
+                 learn_v=False, f=lambda *x: x[0], dnm=None, nc=1, init_dataset=None,
+                 parameterised=False, learn_z=True, lr0alpha=1e-3, tau=0.1,
+                 logistic_regression=False, world=1, **kwargs):
+        if int(world) > 1:
+            raise NotImplementedError("the regressors run on one GPU (Gaussian plans: world 1)")
+        if not float(tau) > 0:
+            raise ValueError("tau must be positive")
+        super().__init__(u=u, z=z, N=N, D=D, num_pseudo=num_pseudo, seed=seed,
+                         mc_samples=mc_samples, learn_v=learn_v, f=f, nc=nc,
+                         register_elbos=register_elbos, learn_z=learn_z,
+                         compute_weights_entropy=compute_weights_entropy,
+                         train_dataset=train_dataset, test_dataset=test_dataset,
+                         init_dataset=init_dataset, lr0alpha=lr0alpha, **kwargs)
+        self.val_dataset, self.dnm = val_dataset, dnm
+        self.logistic_regression, self.parameterised = logistic_regression, parameterised
+        self.tau = float(tau)
+        self.distr_fn = functools.partial(gaussian_fn, scale=1.0 / self.tau ** 0.5)
+        self.y_mean, self.y_std = y_mean, y_std
+        for k, o in (("optim", optim), ("optim_u", optim_u), ("optim_net", optim_net),
+                     ("optim_v", optim_v), ("optim_z", optim_z)):
+            if o is not None:
+                setattr(self, k, o)
+        self._make_plan = functools.partial(InnerLoopPlan, likelihood=("gaussian", self.tau))
+
+    # ------------------------------------------------------------ helpers
+    def _spec(self, model):
+        fam, layers, prior_sd, S = model_spec(model)
+        if fam != "meanfield":
+            raise NotImplementedError(f"the regressors run mean-field models on the HIP path, "
+                                      f"not {fam!r} ones")
+        if layers[-1][1] != 1:
+            raise NotImplementedError("the Gaussian likelihood is built for one network output")
+        if self.mc_samples is not None and S != self.mc_samples:
+            raise ValueError(f"model mc_samples {S} != PSVI mc_samples {self.mc_samples}")
+        return fam, layers, prior_sd, S
+
+    def _plan(self, model):
+        fam, layers, prior_sd, S = self._spec(model)
+        key = (fam, tuple(layers), S, int(self.u.shape[0]), prior_sd)
+        if key not in self._plans:
+            self._plans[key] = self._new_plan(fam, layers, S, key[3], prior_sd, outer=False)
+        return self._plans[key]
+
+    def _outer_plan(self, model, Nx, n_pseudo=None):
+        self._spec(model)
+        return super()._outer_plan(model, Nx, n_pseudo)
+
+    def _targets(self, y):
+        return y.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+
+    def _data(self, plan):
+        M0 = int(self.u.shape[0])
+        u = self.u.detach().to(self.device, torch.float32).reshape(M0, plan.in_features)
+        z = self._targets(self.z)
+        if z.numel() != M0:
+            raise ValueError(f"z holds {z.numel()} targets for {M0} pseudopoints")
+        return u.contiguous(), z, self.coreset_weights()
+
+    def _rows_graph(self, plan):
+        M0 = int(self.u.shape[0])
+        return self.u.reshape(M0, plan.in_features), (self.N * self.f(self.v, 0)).reshape(-1)
+
+    def _row_grad_fn(self, model, plan, u, z, w, eps, pvec):
+        """() -> (d/du, d/dw, d/dz) of sum_s sum_m w_m NLL_sm: the outer kernel
+        in coefficient mode with pseudo coefficient 1 for every sample."""
+        from ..runtime.sharded import pack_coef
+
+        def fn():
+            op = self._outer_plan(model, 0)
+            S = op.S
+            one, zero = torch.ones(S, dtype=torch.float64), torch.zeros(S, dtype=torch.float64)
+            g = op.outer_grad_coef(plan.M, u, z, w, eps, pvec,
+                                   pack_coef(one, zero, zero, 0, S).to(pvec.device), grad_z=True)
+            return g["grad_u"], g["grad_w"], g["grad_z"]
+        return fn
+
+    # ---------------------------------------------------------- objectives
+    def inner_elbo(self, model=None, params=None, hyperopt=False, eps=None):
+        """Negative inner ELBO (psvi_classes.py:2051-2056), a 0-dim tensor:
+        sum_s sum_m N f(v)_m NLL_sm + KL with the Gaussian NLL.  Differentiable
+        (first order) w.r.t. the parameters, u, v / alpha and z."""
+        model = self.model if model is None else model
+        plan = self._plan(model)
+        plist = list(params) if (hyperopt and params is not None) else list(model.parameters())
+        pvec = nn.utils.parameters_to_vector(plist)
+        if pvec.numel() != plan.param_count:
+            raise ValueError(f"{pvec.numel()} parameters, plan expects {plan.param_count}")
+        u, z, w = self._data(plan)
+        eps = self._draw_eps(plan) if eps is None else eps
+        p = pvec.detach().to(torch.float32).contiguous()
+        elbo, grad = plan.elbo_grad(u, z, w, eps, p)
+        out = HipInnerELBO.apply(pvec, elbo, grad)
+        u_g, w_g = self._rows_graph(plan)
+        if u_g.requires_grad or w_g.requires_grad or self.z.requires_grad:
+            out = out + HipInnerRowsZ.apply(u_g, w_g, self.z,
+                                            self._row_grad_fn(model, plan, u, z, w, eps, p),
+                                            out.dtype)
+        return out
+
+    def psvi_elbo(self, xbatch, ybatch, model=None, params=None, hyperopt=False, eps=None):
+        """Negative PSVI-ELBO (psvi_classes.py:2034-2048), a 0-dim tensor;
+        differentiable (first order) w.r.t. the parameters, u, v / alpha
+        (through N f(v)) and z."""
+        model = self.model if model is None else model
+        S = self._spec(model)[3]
+        assert self.mc_samples is None or self.mc_samples > 1   # psvi_classes.py:2035
+        if S < 2:
+            raise ValueError("psvi_elbo needs mc_samples > 1 (psvi_classes.py:2035)")
+        plist = list(params) if (hyperopt and params is not None) else list(model.parameters())
+        pvec = nn.utils.parameters_to_vector(plist)
+        xb, yb, w_data = self._outer_rows(xbatch, ybatch, 1)
+        plan = self._outer_plan(model, int(xb.shape[0]))
+        if pvec.numel() != plan.param_count:
+            raise ValueError(f"{pvec.numel()} parameters, plan expects {plan.param_count}")
+        wp = (self.N * self.f(self.v, 0)).to(torch.float32).reshape(-1)
+        if eps is None:
+            eps = self._draw_eps(plan)
+        return HipOuterELBOZ.apply(pvec, self.u, wp, self.z, plan, xb, yb, w_data, eps)
+
+    def _outer_rows(self, xbatch, ybatch, C):
+        xb = xbatch.detach().to(self.device, torch.float32).reshape(xbatch.shape[0], -1)
+        Nx = int(xb.shape[0])
+        yb = self._targets(ybatch)
+        if yb.numel() != Nx:
+            raise ValueError(f"{yb.numel()} targets for {Nx} data rows")
+        return xb.contiguous(), yb, torch.full((Nx,), float(self.N) / max(Nx, 1),
+                                               device=self.device)
+
+    # -------------------------------------------------------------- trainer
+    @_trainer_step
+    def nested_step(self, xbatch, ybatch, eps_inner=None, eps_outer=None):
+        """psvi_classes.py:2059-2092 (PSVIAV_regressor: 2303-2335): T =
+        self.inner_it higher-Adam steps on the inner objective from the model's
+        parameters with a fresh Adam state, the outer objective at the result,
+        its gradient w.r.t. u, v (alpha) and z through the unrolled steps --
+        per step back one psvi_adam_adjoint and one psvi_hvp_ex, whose mixed
+        products du, dw, dz accumulate onto the outer objective's direct
+        gradients -- then the steps of optim_u, optim_v (clamped at 0 unless
+        parameterised), optim_alpha and optim_z (learn_z).  The final
+        parameters are written into the model; returns the outer loss.
+        ``eps_inner`` (T draws) / ``eps_outer`` (1 draw): optional replay in
+        the library's eps layout; default this instance's Philox stream."""
+        self._zero_hparam_grads()
+        self.optim_net.zero_grad()
+        if self.learn_z:
+            self.optim_z.zero_grad()
+        model = self.model
+        T = int(self.inner_it)
+        lr_net = self.optim_net.param_groups[0]["lr"]
+        plan = self._plan(model)
+        u, z, w = self._data(plan)
+        it_in = iter(eps_inner) if eps_inner is not None else None
+        plist = list(model.parameters())
+        with torch.no_grad():
+            p = nn.utils.parameters_to_vector(plist).detach().to(torch.float32).clone()
+        m = torch.zeros_like(p)
+        v2 = torch.zeros_like(p)
+        ws = plan.workspace(p.device)
+        hist, elbos = [], []
+        for t in range(T):
+            e = next(it_in) if it_in is not None else self._draw_eps(plan)
+            e = e.to(self.device, torch.float32).reshape(-1).contiguous()
+            elbo, g = plan.elbo_grad(u, z, w, e, p, ws=ws)
+            p_prev = p.clone()
+            adam_update_(p, g, m, v2, t + 1, lr_net, kind="higher")
+            hist.append((p_prev, m.clone(), v2.clone(), g, e))
+            elbos.append(elbo)
+        # the outer objective at the inner solution, and its direct gradients
+        xb, yb, w_data = self._outer_rows(xbatch, ybatch, 1)
+        oplan = self._outer_plan(model, int(xb.shape[0]))
+        eo = next(iter(eps_outer)) if eps_outer is not None else self._draw_eps(oplan)
+        eo = eo.to(self.device, torch.float32).reshape(-1).contiguous()
+        o = oplan.outer_elbo_grad(plan.M, torch.cat([u, xb]).contiguous(),
+                                  torch.cat([z, yb]).contiguous(),
+                                  torch.cat([w, w_data]).contiguous(), eo, p, grad_z=True)
+        if self.register_elbos:
+            host = torch.cat(elbos).cpu()
+            for t in range(0, T, self.log_every):
+                self.elbos.append((1, -float(host[t])))
+            self.elbos.append((0, -float(o["loss"].item())))
+        # reverse mode through the T Adam steps
+        lt = o["grad"].clone()
+        lm = torch.zeros_like(p)
+        lv = torch.zeros_like(p)
+        lg = torch.empty_like(p)
+        gu, gw, gz = o["grad_u"].clone(), o["grad_w"].clone(), o["grad_z"].clone()
+        hws = torch.empty(plan.hvp_ws_bytes, dtype=torch.uint8, device=p.device)
+        for t in range(T - 1, -1, -1):
+            p_prev, mt, vt, gt, e = hist[t]
+            adam_adjoint_(lt, lm, lv, mt, vt, gt, t + 1, lr_net, lg, kind="higher")
+            hv, du, dw, dz = plan.hvp(u, z, w, e, p_prev, lg, ws=hws)
+            lt += hv
+            gu += du
+            gw += dw
+            gz += dz
+        self._anomaly_check("nested_step", torch.cat(elbos), o["loss"], p, gu, gw, gz)
+        if self.learn_z:
+            self._add_grad(self.z, gz)
+        self._hparam_steps(gu, gw)
+        if self.learn_z:
+            self.optim_z.step()
+        if self._steps_scheduler and getattr(self, "scheduler_optim_net", None):
+            self.scheduler_optim_net.step()
+        with torch.no_grad():
+            nn.utils.vector_to_parameters(p.to(plist[0].dtype), plist)
+        return o["loss"].reshape(()).to(torch.float32)
+
+    def _unsupported(self, *args, **kwargs):
+        raise NotImplementedError("the regressors train with nested_step only, as the "
+                                  "reference's run_psvi (psvi_classes.py:2176-2178)")
+
+    hyper_step = joint_step = alternating_step = pred_on_grid = _unsupported
+
+    # ------------------------------------------------------------ evaluation
+    def evaluate(self, correction=True, eps=None, **kwargs):
+        """psvi_classes.py:2221-2264: (rmse, test_ll) over self.test_loader in
+        the targets' original units, one psvi_evaluate_regression per batch.
+        The reference's pseudo term is summed to one scalar, so its importance
+        weights are softmax_s(sampled_nkl_s) alone; the kernel reproduces that.
+        ``eps``: optional list of draws, one per batch."""
+        assert self.mc_samples is None or self.mc_samples > 1
+        model = self.model
+        it = iter(eps) if eps is not None else None
+        Mu = int(self.u.shape[0])
+        with torch.no_grad():
+            pvec = nn.utils.parameters_to_vector(model.parameters()).detach().to(
+                torch.float32).contiguous()
+        u = self.u.detach().to(self.device, torch.float32).reshape(Mu, -1)
+        z, w = self._targets(self.z), self.coreset_weights()
+        y_mean = 0.0 if self.y_mean is None else float(self.y_mean)
+        y_std = 1.0 if self.y_std is None else float(self.y_std)
+        stats, total = None, 0
+        for xt, yt in self.test_loader:
+            xt = xt.to(self.device, torch.float32).reshape(xt.shape[0], -1)
+            nt = int(xt.shape[0])
+            plan = self._outer_plan(model, nt)
+            e = next(it) if it is not None else self._draw_eps(plan)
+            e = e.to(self.device, torch.float32).reshape(-1).contiguous()
+            st, _ = plan.evaluate_regression(
+                Mu, torch.cat([u, xt]).contiguous(), torch.cat([z, self._targets(yt)]).contiguous(),
+                torch.cat([w, torch.zeros(nt, device=self.device)]).contiguous(), e, pvec,
+                y_mean, y_std, correction=correction)
+            stats = st if stats is None else stats + st
+            total += nt
+        return (stats[2] / float(total)).sqrt(), stats[3] / float(total)
+
+    # ------------------------------------------------------------ the driver
+    def set_up_model(self):
+        """psvi_classes.py:743-753: architecture 'regressor_net'."""
+        if self.architecture != "regressor_net":
+            raise NotImplementedError(f"architecture {self.architecture!r}: the regressors run "
+                                      "'regressor_net' (mean-field, one output) on the HIP path")
+        self.model = make_regressor_net(self.D, self.n_hidden, self.nc, linear_class=VILinear,
+                                        nonl_class=nn.ReLU, mc_samples=self.mc_samples,
+                                        init_sd=self.init_sd).to(self.device)
+        self._spec(self.model)
+
+    def pseudo_subsample_init(self):
+        """psvi_classes.py:2019-2031: u, z start on a random subset of the
+        training data."""
+        import random
+
+        idx = random.sample(range(len(self.train_dataset)), self.num_pseudo)
+        rows = [self.train_dataset[i] for i in idx]
+        with torch.no_grad():
+            self.u = torch.stack([torch.as_tensor(r[0]) for r in rows]).float().to(self.device)
+            self.z = torch.stack([torch.as_tensor(r[1]) for r in rows]).float().to(self.device)
+        self.u.requires_grad_(True), self.z.requires_grad_(True)
+
+    def run_psvi(self, init_args="subsample", trainer="nested", n_layers=1, n_hidden=None,
+                 architecture=None, log_every=10, inner_it=10, data_minibatch=None, lr0net=1e-3,
+                 lr0u=1e-3, lr0v=1e-2, lr0z=1e-2, init_sd=1e-3, num_epochs=1000,
+                 log_pseudodata=False, **kwargs):
+        """psvi_classes.py:2095-2218: trainer 'nested', init 'subsample',
+        architecture 'regressor_net'; evaluates every log_every outer steps.
+        Returns the results dict (rmses, lls, csizes, times, went, ness, vent,
+        vs; the reference leaves went / ness / vent empty)."""
+        from torch.utils.data import DataLoader
+
+        if trainer != "nested":
+            raise NotImplementedError(f"trainer={trainer!r}: the regressors train with 'nested'")
+        if init_args != "subsample":
+            raise NotImplementedError(f"init_args={init_args!r}: the regressors start from "
+                                      "'subsample'")
+        self.init_args, self.trainer = init_args, trainer
+        self.architecture, self.n_hidden = architecture, n_hidden
+        self.n_layers, self.init_sd = n_layers, init_sd
+        self.log_every, self.log_pseudodata = log_every, log_pseudodata
+        self.data_minibatch, self.inner_it, self.num_epochs = data_minibatch, inner_it, num_epochs
+        self.set_up_model()
+        self.train_loader = DataLoader(self.train_dataset, batch_size=data_minibatch, shuffle=True)
+        self.test_loader = DataLoader(self.test_dataset, batch_size=data_minibatch, shuffle=False)
+        if self.val_dataset is not None:
+            self.val_loader = DataLoader(self.val_dataset, batch_size=data_minibatch,
+                                         shuffle=False)
+        self.pseudo_subsample_init()
+        self.optim_net = torch.optim.Adam(list(self.model.parameters()), lr0net)
+        self.optim_u = torch.optim.Adam([self.u], lr0u)
+        if self.learn_v:
+            self.optim_v = torch.optim.Adam([self.v], lr0v)
+        if self.learn_z:
+            self.optim_z = torch.optim.Adam([self.z], lr0z)
+        self.scheduler_optim_net = None
+        rmses, lls, csizes, vs, us, zs, times = [], [], [], [], [], [], [0]
+        t_start = time.time()
+        for it in range(num_epochs):
+            xbatch, ybatch = next(iter(self.train_loader))
+            xbatch, ybatch = xbatch.to(self.device), ybatch.to(self.device)
+            if it % log_every == 0:
+                rmse, ll = self.evaluate(**kwargs)
+                with torch.no_grad():
+                    lls.append(ll.item())
+                    rmses.append(rmse.item())
+                    csizes.append(self.num_pseudo)
+                    times.append(times[-1] + time.time() - t_start)
+                    vs.append(self.f(self.v, 0).clone().cpu().detach().numpy())
+                    if log_pseudodata:
+                        us.append(self.u.clone().cpu().detach().numpy())
+                        zs.append(self.z.clone().cpu().detach().numpy())
+            self.nested_step(xbatch, ybatch)
+        self.results.update(rmses=rmses, lls=lls, csizes=csizes, times=times[1:], went=[],
+                            ness=[], vent=[], vs=vs)
+        return self.results
+
+
+class PSVILearnV_regressor(PSVI_regressor):
+    """Learnable v on the simplex: f = softmax, v initialised to 0
+    (psvi_classes.py:2268-2279)."""
+
+    def __init__(self, learn_v=True, parameterised=True, **kwargs):
+        super().__init__(**kwargs)
+        self.learn_v, self.parameterised = learn_v, parameterised
+        with torch.no_grad():
+            self.v = torch.zeros(self.num_pseudo, device=self.device)
+        self.v.requires_grad_(True)
+        self.f = torch.softmax
+
+
+class PSVIAV_regressor(PSVILearnV_regressor):
+    """Simplex weights times a learnable total evidence exp(alpha)
+    (psvi_classes.py:2283-2335); optim_alpha steps with optim_v."""
+
+    _steps_scheduler = True
+
+    def __init__(self, learn_v=True, **kwargs):
+        super().__init__(**kwargs)
+        _init_alpha(self)
+
+    def evaluate(self, **kwargs):
+        """psvi_classes.py:2294-2301: records alpha, then the regressors' evaluate."""
+        self.results["alpha"].append(self.alpha.clone().cpu().detach().numpy())
         return super().evaluate(**kwargs)
 
 

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 __all__ = [
     "VIMixin", "VILinear", "MultivariateNormalVIMixin", "VILinearMultivariateNormal",
-    "make_fcnet", "make_fc2net", "make_logreg", "set_mc_samples", "inverse_softplus",
+    "make_fcnet", "make_fc2net", "make_logreg", "make_regressor_net", "set_mc_samples", "inverse_softplus",
     "categorical_fn", "gaussian_fn", "vi_layers", "model_spec",
     "VIConv2d", "BatchMaxPool2d", "make_lenet", "LENET_LAYERS",
 ]
@@ -297,12 +297,13 @@ LENET_LAYERS = [(25, 6), (150, 16), (400, 120), (120, 84), (84, 10)]
 
 
 # ------------------------------------------------------------ builders
-def _stack(in_dim, h_dim, out_dim, n_layers, linear_class, nonl_class, mc_samples, kwargs):
+def _stack(in_dim, h_dim, out_dim, n_layers, linear_class, nonl_class, mc_samples, kwargs,
+           head="classifier"):
     net = nn.Sequential()
     for i in range(n_layers):
         net.add_module(f"lin{i}", linear_class(in_dim if i == 0 else h_dim, h_dim, **kwargs))
         net.add_module(f"nonl{i}", nonl_class())
-    net.add_module("classifier", linear_class(h_dim if n_layers else in_dim, out_dim, **kwargs))
+    net.add_module(head, linear_class(h_dim if n_layers else in_dim, out_dim, **kwargs))
     for m in net.modules():
         m.mc_samples = mc_samples
     return net
@@ -315,6 +316,18 @@ def make_fcnet(in_dim, h_dim, out_dim, n_layers=2, linear_class=None, nonl_class
         raise NotImplementedError("residual_fn is commented out in the reference builder too")
     return _stack(in_dim, h_dim, out_dim, n_layers, linear_class or VILinear,
                   nonl_class or nn.ReLU, mc_samples, kwargs)
+
+
+def make_regressor_net(in_dim, h_dim, out_dim=1, n_layers=2, linear_class=None, nonl_class=None,
+                       mc_samples=4, residual=False, **kwargs):
+    """Mean-field MLP with a linear ``regressor`` head ('regressor_net',
+    neural_net.py:300-331): modules lin{i}, nonl{i}, regressor.  With
+    out_dim = 1 ``model_spec`` gives the mean-field family with C = 1, the
+    shape the Gaussian-likelihood HIP plan runs."""
+    if residual:
+        raise NotImplementedError("residual_fn is commented out in the reference builder too")
+    return _stack(in_dim, h_dim, out_dim, n_layers, linear_class or VILinear,
+                  nonl_class or nn.ReLU, mc_samples, kwargs, head="regressor")
 
 
 def make_fc2net(in_dim, h_dim, out_dim, n_layers=2, linear_class=None, nonl_class=None,

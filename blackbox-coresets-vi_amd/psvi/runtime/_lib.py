@@ -20,6 +20,8 @@ LOOP_RESUME = 2
 ADAM_HIGHER = 0
 ADAM_HYPERGRAD = 1
 ADAM_TORCH = 2
+LIK_CATEGORICAL = 0
+LIK_GAUSSIAN = 1
 
 Q_PARAM_COUNT = 1
 Q_EPS_COUNT = 2
@@ -36,6 +38,7 @@ Q_OUTER_WS_BYTES = 12
 Q_HVP_WS_BYTES = 13
 Q_EVAL_WS_BYTES = 14
 Q_NET_PART_OK = 15
+Q_NET_MCHUNKS = 16
 
 ERRORS = {-1: "PSVI_EINVAL", -2: "PSVI_ENOSPC", -3: "PSVI_EUNSUP", -4: "PSVI_ESTATE"}
 
@@ -47,6 +50,13 @@ class NetDesc(ctypes.Structure):
         ("S", ctypes.c_int32),
         ("M", ctypes.c_int32),
         ("prior_sd", ctypes.c_float),
+    ]
+
+
+class Likelihood(ctypes.Structure):
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("tau", ctypes.c_float),
     ]
 
 
@@ -69,6 +79,8 @@ _U64 = ctypes.c_uint64
 _SZ = ctypes.c_size_t
 SIGNATURES = {
     "psvi_plan_create": (_I32, [_I32, ctypes.POINTER(NetDesc), _I32, _I32, ctypes.POINTER(_P)]),
+    "psvi_plan_create_lik": (_I32, [_I32, ctypes.POINTER(NetDesc), _I32, _I32,
+                                    ctypes.POINTER(Likelihood), ctypes.POINTER(_P)]),
     "psvi_plan_destroy": (_I32, [_P]),
     "psvi_plan_query": (_I32, [_P, _I32, ctypes.POINTER(_I64)]),
     "psvi_plan_shard_info": (_I32, [_P, _I32, ctypes.POINTER(_I64)]),
@@ -97,12 +109,19 @@ SIGNATURES = {
                                   ctypes.POINTER(AdamHP), _P, _P, _SZ, _I32, _P]),
     "psvi_outer_elbo_grad": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                     _SZ, _P]),
+    "psvi_outer_elbo_grad_ex": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _SZ, _P]),
     "psvi_outer_ablated_elbo_grad": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_outer_elbo_grad_coef": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                          _SZ, _P]),
+    "psvi_outer_elbo_grad_coef_ex": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                            _SZ, _P]),
+    "psvi_evaluate_regression": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, ctypes.c_float,
+                                        ctypes.c_float, _P, _P, _P, _SZ, _P]),
     "psvi_evaluate": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_adam_adjoint": (_I32, [_I64, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(AdamHP),
                                  _P]),
     "psvi_randn": (_I32, [_P, _I64, _U64, _U64, _P]),

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.graph import increment_version
 
 from . import _lib
-from ._lib import AdamHP, NetDesc, check
+from ._lib import AdamHP, Likelihood, NetDesc, check
 
 
 def _ptr(t):
@@ -69,10 +69,22 @@ class _Token:
 
 class InnerLoopPlan:
     """family: 'meanfield' (VILinear stack) or 'fullcov' (VILinearMultivariateNormal
-    stack); layers: [(in, out), ...]; S: global MC samples; M: pseudopoints."""
+    stack); layers: [(in, out), ...]; S: global MC samples; M: pseudopoints.
+    likelihood: None (categorical, class ids in an int32 z) or ("gaussian", tau):
+    Normal(f, 1 / sqrt(tau)) over the one network output, the regressors'
+    observation model -- every z / z_all is then a float32 tensor of targets."""
 
-    def __init__(self, family, layers, S, M, prior_sd=1.0, world=1, rank=0):
+    def __init__(self, family, layers, S, M, prior_sd=1.0, world=1, rank=0, likelihood=None):
         self.lib = _lib.load()
+        if likelihood is None:
+            self.likelihood, self.tau = "categorical", None
+        else:
+            kind, tau = likelihood
+            if kind != "gaussian":
+                raise ValueError(f"unknown likelihood {kind!r} (None or ('gaussian', tau))")
+            self.likelihood, self.tau = "gaussian", float(tau)
+        # dtype of every z / z_all argument
+        self._zdtype = torch.float32 if self.likelihood == "gaussian" else torch.int32
         self._resident = None  # inner_loop(keep=True)'s token
         self.family = family
         fam = {"meanfield": _lib.FAMILY_MEANFIELD, "fullcov": _lib.FAMILY_FULLCOV,
@@ -100,8 +112,14 @@ class InnerLoopPlan:
         d.S, d.M, d.prior_sd = self.S, self.M, float(prior_sd)
         self.desc = d
         h = ctypes.c_void_p()
-        check(self.lib.psvi_plan_create(fam, ctypes.byref(d), self.world, self.rank,
-                                        ctypes.byref(h)), "psvi_plan_create")
+        if self.likelihood == "gaussian":
+            lik = Likelihood(_lib.LIK_GAUSSIAN, self.tau)
+            check(self.lib.psvi_plan_create_lik(fam, ctypes.byref(d), self.world, self.rank,
+                                                ctypes.byref(lik), ctypes.byref(h)),
+                  "psvi_plan_create_lik")
+        else:
+            check(self.lib.psvi_plan_create(fam, ctypes.byref(d), self.world, self.rank,
+                                            ctypes.byref(h)), "psvi_plan_create")
         self.handle = h
         q = self._query
         self.param_count = q(_lib.Q_PARAM_COUNT)
@@ -119,6 +137,7 @@ class InnerLoopPlan:
         self.hvp_ws_bytes = q(_lib.Q_HVP_WS_BYTES)
         self.eval_ws_bytes = q(_lib.Q_EVAL_WS_BYTES)
         self.net_part_ok = bool(q(_lib.Q_NET_PART_OK))
+        self.net_mchunks = q(_lib.Q_NET_MCHUNKS)   # pseudopoint chunks of the network kernels
         self.eps_stride = (self.eps_count + 3) // 4 * 4   # Philox offset per loop step
         self.n_tot = sum(i * o + o for i, o in layers)
 
@@ -161,7 +180,7 @@ class InnerLoopPlan:
 
     def _inputs(self, u, z, w, eps):
         _need(u, "u", self.M * self.in_features)
-        _need(z, "z", self.M, torch.int32)
+        _need(z, "z", self.M, self._zdtype)
         _need(w, "w", self.M)
         _need(eps, "eps", self.eps_count)
 
@@ -205,7 +224,7 @@ class InnerLoopPlan:
         sample, where a plain call's last step takes the packed-out one:
         the same values up to fp32 rounding)."""
         _need(u, "u", self.M * self.in_features)
-        _need(z, "z", self.M, torch.int32)
+        _need(z, "z", self.M, self._zdtype)
         _need(w, "w", self.M)
         for t, n in ((params, "params"), (adam_m, "adam_m"), (adam_v, "adam_v")):
             _need(t, n, self.param_count)
@@ -263,16 +282,20 @@ class InnerLoopPlan:
         return elbo, grad
 
     def outer_elbo_grad(self, n_pseudo, x_all, z_all, w_all, eps, params, grad=True,
-                        grad_u=True, grad_w=True, sample_stats=False, ws=None):
+                        grad_u=True, grad_w=True, sample_stats=False, ws=None, grad_z=False):
         """Outer objective (PSVI.psvi_elbo) over this plan's M rows (pseudopoints
         first, n_pseudo of them) -- psvi_outer_elbo_grad.  Returns a dict of
         device tensors: loss (float64, 1), and as requested grad (P), grad_u
         (n_pseudo, D), grad_w (n_pseudo), samples (S, 4: pseudo, data, nkl,
-        weight; float64)."""
+        weight; float64).  grad_z=True (Gaussian plans; needs grad): also grad_z
+        (n_pseudo), the gradient of the pseudo rows' targets
+        (psvi_outer_elbo_grad_ex)."""
         D = self.in_features
         n_pseudo = int(n_pseudo)
+        if grad_z and self.likelihood != "gaussian":
+            raise ValueError("grad_z needs a Gaussian-likelihood plan")
         _need(x_all, "x_all", self.M * D)
-        _need(z_all, "z_all", self.M, torch.int32)
+        _need(z_all, "z_all", self.M, self._zdtype)
         _need(w_all, "w_all", self.M)
         _need(eps, "eps", self.eps_count)
         _need(params, "params", self.param_count)
@@ -286,13 +309,22 @@ class InnerLoopPlan:
             out["grad_w"] = torch.empty(n_pseudo, dtype=torch.float32, device=dev)
         if sample_stats:
             out["samples"] = torch.empty(self.S, 4, dtype=torch.float64, device=dev)
+        if grad and grad_z:
+            out["grad_z"] = torch.empty(n_pseudo, dtype=torch.float32, device=dev)
         if ws is None or ws.numel() < self.outer_ws_bytes:
             ws = torch.empty(self.outer_ws_bytes, dtype=torch.uint8, device=dev)
-        check(self.lib.psvi_outer_elbo_grad(
-            self.handle, n_pseudo, _ptr(x_all), _ptr(z_all), _ptr(w_all), _ptr(eps),
-            _ptr(params), _ptr(out["loss"]), _ptr(out.get("grad")), _ptr(out.get("grad_u")),
-            _ptr(out.get("grad_w")), _ptr(out.get("samples")), _ptr(ws), ws.numel(),
-            _stream()), "psvi_outer_elbo_grad")
+        if "grad_z" in out:
+            check(self.lib.psvi_outer_elbo_grad_ex(
+                self.handle, n_pseudo, _ptr(x_all), _ptr(z_all), _ptr(w_all), _ptr(eps),
+                _ptr(params), _ptr(out["loss"]), _ptr(out.get("grad")), _ptr(out.get("grad_u")),
+                _ptr(out.get("grad_w")), _ptr(out["grad_z"]), _ptr(out.get("samples")), _ptr(ws),
+                ws.numel(), _stream()), "psvi_outer_elbo_grad_ex")
+        else:
+            check(self.lib.psvi_outer_elbo_grad(
+                self.handle, n_pseudo, _ptr(x_all), _ptr(z_all), _ptr(w_all), _ptr(eps),
+                _ptr(params), _ptr(out["loss"]), _ptr(out.get("grad")), _ptr(out.get("grad_u")),
+                _ptr(out.get("grad_w")), _ptr(out.get("samples")), _ptr(ws), ws.numel(),
+                _stream()), "psvi_outer_elbo_grad")
         _wrote(ws)
         return out
 
@@ -303,7 +335,7 @@ class InnerLoopPlan:
         a dict: loss (float64, 1), grad (P) when requested, samples (S, 4)."""
         D = self.in_features
         _need(x_all, "x_all", self.M * D)
-        _need(z_all, "z_all", self.M, torch.int32)
+        _need(z_all, "z_all", self.M, self._zdtype)
         _need(w_all, "w_all", self.M)
         _need(eps, "eps", self.eps_count)
         _need(params, "params", self.param_count)
@@ -323,16 +355,19 @@ class InnerLoopPlan:
         return out
 
     def outer_grad_coef(self, n_pseudo, x_all, z_all, w_all, eps, params, coef, grad_u=True,
-                        grad_w=True, ws=None):
+                        grad_w=True, ws=None, grad_z=False):
         """Backward of the outer objective with caller-given per-sample
         coefficients coef = [rowcoef (S, 2) | ck (S) | sck] (float32, 3S + 1)
         -- psvi_outer_elbo_grad_coef, the second pass of the sample-sharded
         outer objective (sharded.ShardedOuter).  Returns grad (P), grad_u
-        (n_pseudo, D) and grad_w (n_pseudo) as requested."""
+        (n_pseudo, D) and grad_w (n_pseudo) as requested; grad_z (n_pseudo) on
+        Gaussian plans (psvi_outer_elbo_grad_coef_ex)."""
         D = self.in_features
         n_pseudo = int(n_pseudo)
+        if grad_z and self.likelihood != "gaussian":
+            raise ValueError("grad_z needs a Gaussian-likelihood plan")
         _need(x_all, "x_all", self.M * D)
-        _need(z_all, "z_all", self.M, torch.int32)
+        _need(z_all, "z_all", self.M, self._zdtype)
         _need(w_all, "w_all", self.M)
         _need(eps, "eps", self.eps_count)
         _need(params, "params", self.param_count)
@@ -345,6 +380,15 @@ class InnerLoopPlan:
             out["grad_w"] = torch.empty(n_pseudo, dtype=torch.float32, device=dev)
         if ws is None or ws.numel() < self.outer_ws_bytes:
             ws = torch.empty(self.outer_ws_bytes, dtype=torch.uint8, device=dev)
+        if grad_z:
+            out["grad_z"] = torch.empty(n_pseudo, dtype=torch.float32, device=dev)
+            check(self.lib.psvi_outer_elbo_grad_coef_ex(
+                self.handle, n_pseudo, _ptr(x_all), _ptr(z_all), _ptr(w_all), _ptr(eps),
+                _ptr(params), _ptr(coef), _ptr(out["grad"]), _ptr(out.get("grad_u")),
+                _ptr(out.get("grad_w")), _ptr(out["grad_z"]), _ptr(ws), ws.numel(), _stream()),
+                "psvi_outer_elbo_grad_coef_ex")
+            _wrote(ws)
+            return out
         check(self.lib.psvi_outer_elbo_grad_coef(
             self.handle, n_pseudo, _ptr(x_all), _ptr(z_all), _ptr(w_all), _ptr(eps),
             _ptr(params), _ptr(coef), _ptr(out["grad"]), _ptr(out.get("grad_u")),
@@ -361,7 +405,7 @@ class InnerLoopPlan:
         probs ([M - n_pseudo, C]) when requested."""
         D, C = self.in_features, self.layers[-1][1]
         _need(x_all, "x_all", self.M * D)
-        _need(z_all, "z_all", self.M, torch.int32)
+        _need(z_all, "z_all", self.M, self._zdtype)
         _need(w_all, "w_all", self.M)
         _need(eps, "eps", self.eps_count)
         _need(params, "params", self.param_count)
@@ -377,12 +421,41 @@ class InnerLoopPlan:
         _wrote(ws)
         return stats, pr
 
+    def evaluate_regression(self, n_pseudo, x_all, y_all, w_all, eps, params, y_mean=0.0,
+                            y_std=1.0, correction=True, pred=False, ws=None):
+        """The regressors' predictive evaluation of the data rows of this plan's
+        M rows (psvi_evaluate_regression, Gaussian plans): y_all holds the
+        pseudo targets, then the test targets in original units.  Returns
+        (stats, pred): stats a float64 device tensor [entropy of W, normalised
+        ESS, summed squared error, summed test log-likelihood]; pred
+        ([M - n_pseudo], the de-normalised predictive mean) when requested."""
+        if self.likelihood != "gaussian":
+            raise ValueError("evaluate_regression needs a Gaussian-likelihood plan")
+        _need(x_all, "x_all", self.M * self.in_features)
+        _need(y_all, "y_all", self.M)
+        _need(w_all, "w_all", self.M)
+        _need(eps, "eps", self.eps_count)
+        _need(params, "params", self.param_count)
+        dev = params.device
+        stats = torch.empty(4, dtype=torch.float64, device=dev)
+        pr = torch.empty(self.M - int(n_pseudo), dtype=torch.float32, device=dev) if pred else None
+        if ws is None or ws.numel() < self.eval_ws_bytes:
+            ws = torch.empty(self.eval_ws_bytes, dtype=torch.uint8, device=dev)
+        check(self.lib.psvi_evaluate_regression(
+            self.handle, int(n_pseudo), _ptr(x_all), _ptr(y_all), _ptr(w_all), _ptr(eps),
+            _ptr(params), int(bool(correction)), float(y_mean), float(y_std), _ptr(pr),
+            _ptr(stats), _ptr(ws), ws.numel(), _stream()), "psvi_evaluate_regression")
+        _wrote(ws)
+        return stats, pr
+
     def hvp(self, u, z, w, eps, params, vec, mixed=True, out=None, ws=None, include_kl=True):
         """Hessian-vector product of the negative inner ELBO at fixed eps
         (psvi_hvp).  Returns (hv, d_u, d_w): H vec and, with mixed=True, the
         mixed products d/du and d/dw of vec . grad (else None, None).
         include_kl=False: this plan's samples' share without the KL Hessian
-        (psvi_hvp_partial, one rank of a sample-sharded product)."""
+        (psvi_hvp_partial, one rank of a sample-sharded product).  On a Gaussian
+        plan mixed=True returns (hv, d_u, d_w, d_z), d_z the mixed product w.r.t.
+        the targets (psvi_hvp_ex); mixed=False (hv, None, None, None)."""
         self._inputs(u, z, w, eps)
         _need(params, "params", self.param_count)
         _need(vec, "vec", self.param_count)
@@ -393,6 +466,14 @@ class InnerLoopPlan:
         dw = torch.empty(self.M, dtype=torch.float32, device=dev) if mixed else None
         if ws is None or ws.numel() < self.hvp_ws_bytes:
             ws = torch.empty(self.hvp_ws_bytes, dtype=torch.uint8, device=dev)
+        if self.likelihood == "gaussian":
+            dz = torch.empty(self.M, dtype=torch.float32, device=dev) if mixed else None
+            check(self.lib.psvi_hvp_ex(self.handle, _ptr(u), _ptr(z), _ptr(w), _ptr(eps),
+                                       _ptr(params), _ptr(vec), int(bool(include_kl)), _ptr(hv),
+                                       _ptr(du), _ptr(dw), _ptr(dz), _ptr(ws), ws.numel(),
+                                       _stream()), "psvi_hvp_ex")
+            _wrote(ws)
+            return hv, du, dw, dz
         check(self.lib.psvi_hvp_partial(self.handle, _ptr(u), _ptr(z), _ptr(w), _ptr(eps),
                                         _ptr(params), _ptr(vec), int(bool(include_kl)), _ptr(hv),
                                         _ptr(du), _ptr(dw), _ptr(ws), ws.numel(), _stream()),
@@ -474,7 +555,7 @@ class InnerLoopPlan:
         (s_begin, s_count): only those local samples (psvi_mvn_phase_net_part),
         with part draw_part[0] of draw_part[1] of the draw."""
         _need(u, "u", self.M * self.in_features)
-        _need(z, "z", self.M, torch.int32)
+        _need(z, "z", self.M, self._zdtype)
         _need(w, "w", self.M)
         _need(x_recv, "x_recv", self.xrecv_count)
         _need(g_send, "g_send", self.xrecv_count)

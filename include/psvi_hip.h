@@ -38,6 +38,11 @@
  *     count of the plan; every rank passes the full eps.
  *   - z holds int32 class ids; w holds the coreset weights N*f(v) (M floats,
  *     psvi_classes.py:505).
+ *   - On a plan created with a Gaussian likelihood (psvi_plan_create_lik,
+ *     PSVI_LIK_GAUSSIAN) every z / z_all argument of every entry point points
+ *     to fp32 regression targets instead: the caller casts its const float*
+ *     to the declared const int32_t*; the kernels read the same 32 bits as
+ *     floats.
  *   - Scalar objective outputs (elbo_out, nll_out, kl_out) are DOUBLE device
  *     accumulators: the kernels add thousands of per-block partials into them
  *     and fp32 accumulation would bias the sum (rounding of similar-size adds
@@ -128,6 +133,8 @@ typedef struct psvi_plan psvi_plan;       /* opaque, immutable after create */
 #define PSVI_Q_EVAL_WS_BYTES 14 /* workspace bytes for psvi_evaluate                  */
 #define PSVI_Q_NET_PART_OK   15 /* full-cov: 1 if psvi_mvn_phase_net_part takes sample
                                    ranges (no per-chunk gradient slots), else 0    */
+#define PSVI_Q_NET_MCHUNKS   16 /* pseudopoint chunks the network kernels split this
+                                   plan's M rows into (1: one workgroup sees all)  */
 
 /* Create a plan for `family` over `world` ranks, this process being `rank`.
  * Samples are split in contiguous blocks; for FULLCOV at world > 1 the rows
@@ -137,6 +144,33 @@ typedef struct psvi_plan psvi_plan;       /* opaque, immutable after create */
  * psvi_plan_shard_runs). */
 int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world,
                      int32_t rank, psvi_plan** out);
+
+/* Observation models.  PSVI_LIK_CATEGORICAL: Categorical(logits), the class
+ * ids in z (every plan of psvi_plan_create).  PSVI_LIK_GAUSSIAN: Normal(f,
+ * 1 / sqrt(tau)) over ONE network output f with fixed precision tau -- the
+ * reference's regressors (PSVI_regressor, psvi_classes.py:1940-2335, distr_fn
+ * = gaussian_fn(scale = 1 / sqrt(tau)), make_regressor_net neural_net.py:300-331).
+ * For a row with output f, target z and weight w:
+ *   NLL = tau / 2 (f - z)^2 + log(2 pi / tau) / 2,  d NLL / d f = tau (f - z),
+ *   d NLL / d z = -d NLL / d f. */
+#define PSVI_LIK_CATEGORICAL 0
+#define PSVI_LIK_GAUSSIAN    1
+typedef struct psvi_likelihood {
+    int32_t kind;      /* PSVI_LIK_*                                      */
+    float   tau;       /* PSVI_LIK_GAUSSIAN: the precision, > 0           */
+} psvi_likelihood;
+
+/* psvi_plan_create with an observation model.  lik == NULL or a categorical
+ * lik: exactly psvi_plan_create.  A Gaussian lik needs family ==
+ * PSVI_FAMILY_MEANFIELD and world == 1 (PSVI_EUNSUP otherwise), dims[n_layers]
+ * == 1 and a finite tau > 0 (PSVI_EINVAL otherwise).  On such a plan
+ * psvi_inner_step, psvi_elbo_grad, psvi_inner_loop(_ex), the mean-field
+ * phases, psvi_outer_elbo_grad(_coef)(_ex), psvi_hvp(_partial / _ex) and
+ * psvi_evaluate_regression run with fp32 targets (see Conventions);
+ * psvi_evaluate returns PSVI_ESTATE and psvi_outer_ablated_elbo_grad
+ * PSVI_EUNSUP (the reference has no ablated regressor). */
+int psvi_plan_create_lik(int32_t family, const psvi_net_desc* d, int32_t world,
+                         int32_t rank, const psvi_likelihood* lik, psvi_plan** out);
 int psvi_plan_destroy(psvi_plan* plan);
 int psvi_plan_query(const psvi_plan* plan, int32_t key, int64_t* value);
 /* rows (full-cov) and samples owned by rank `r` of the plan's world:
@@ -331,6 +365,20 @@ int psvi_outer_elbo_grad(const psvi_plan* plan, int32_t n_pseudo, const float* x
                          float* grad_u, float* grad_w, double* sample_out, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* psvi_outer_elbo_grad plus the gradient of the pseudo rows' targets on a
+ * Gaussian-likelihood plan (PSVI_regressor.psvi_elbo, psvi_classes.py:2034-2048,
+ * with learn_z):
+ *   grad_z (n_pseudo floats, nullable; needs grad_params) <- d loss / d z_m =
+ *       -sum_s dlogit_sm, dlogit the head's coefficient-scaled d / d f, summed
+ *       in sample order (one writer per element, no float atomics).
+ * A non-NULL grad_z on a categorical plan returns PSVI_ESTATE.
+ * psvi_outer_elbo_grad == psvi_outer_elbo_grad_ex(grad_z = NULL). */
+int psvi_outer_elbo_grad_ex(const psvi_plan* plan, int32_t n_pseudo, const float* x_all,
+                            const int32_t* z_all, const float* w_all, const float* eps,
+                            const float* params, double* loss_out, float* grad_params,
+                            float* grad_u, float* grad_w, float* grad_z, double* sample_out,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* PSVI_Ablated.psvi_elbo (psvi/inference/psvi_classes.py:1397-1408; also
  * PSVI_No_IW's, 1411): the outer objective without importance weighting,
  * over the data batch only (x_all = xbatch, the plan's M = Nx rows, w_all =
@@ -366,6 +414,15 @@ int psvi_outer_elbo_grad_coef(const psvi_plan* plan, int32_t n_pseudo, const flo
                               float* grad_u, float* grad_w, void* ws, size_t ws_bytes,
                               void* stream);
 
+/* psvi_outer_elbo_grad_coef with grad_z as psvi_outer_elbo_grad_ex (Gaussian
+ * plans; coefficient 1 on every sample's pseudo term gives the target
+ * gradient of the inner objective's weighted NLL). */
+int psvi_outer_elbo_grad_coef_ex(const psvi_plan* plan, int32_t n_pseudo, const float* x_all,
+                                 const int32_t* z_all, const float* w_all, const float* eps,
+                                 const float* params, const float* coef, float* grad_params,
+                                 float* grad_u, float* grad_w, float* grad_z, void* ws,
+                                 size_t ws_bytes, void* stream);
+
 /* Importance-weighted predictive evaluation of one test batch: PSVI.evaluate
  * (psvi_classes.py:1031-1108) and pred_on_grid (1130-1175), world == 1,
  * 2 <= S <= 2048.  Rows as psvi_outer_elbo_grad: x_all = cat(u, xtest), the
@@ -382,6 +439,26 @@ int psvi_evaluate(const psvi_plan* plan, int32_t n_pseudo, const float* x_all,
                   const int32_t* z_all, const float* w_all, const float* eps,
                   const float* params, int32_t correction, float* probs_out,
                   double* stats_out, void* ws, size_t ws_bytes, void* stream);
+
+/* The regressors' predictive evaluation of one test batch
+ * (PSVI_regressor.evaluate, psvi_classes.py:2221-2264) on a Gaussian plan,
+ * 2 <= S <= 2048.  Rows as psvi_evaluate: x_all = cat(u, xtest); y_all (fp32)
+ * the pseudo targets, then the test targets in ORIGINAL units; w_all is not
+ * read.  The reference sums its pseudo term over the samples as well, so
+ * its weights are W = softmax_s(sampled_nkl_s) alone -- reproduced;
+ * correction = 0: W = 1 / S.
+ *   y_pred_j = sum_s W_s (f_sj y_std + y_mean)
+ *   pred_out ([M - n_pseudo], nullable) <- y_pred
+ *   stats_out[4] (double, written) <- entropy of W, normalised ESS, sum_j
+ *     (y_pred_j - y_j)^2, sum_j log N(y_j; y_pred_j, 1 / sqrt(tau)).  The two
+ *     sums are added per 256-row block with double atomics (as psvi_evaluate's):
+ *     with more than 256 test rows their last bits may differ run to run.
+ * A categorical plan returns PSVI_ESTATE.  ws: PSVI_Q_EVAL_WS_BYTES. */
+int psvi_evaluate_regression(const psvi_plan* plan, int32_t n_pseudo, const float* x_all,
+                             const float* y_all, const float* w_all, const float* eps,
+                             const float* params, int32_t correction, float y_mean,
+                             float y_std, float* pred_out, double* stats_out, void* ws,
+                             size_t ws_bytes, void* stream);
 
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's
@@ -413,6 +490,17 @@ int psvi_hvp_partial(const psvi_plan* plan, const float* u, const int32_t* z, co
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,
                      size_t ws_bytes, void* stream);
+
+/* psvi_hvp_partial plus the mixed product w.r.t. the targets of a Gaussian
+ * plan (the regressors' learn_z):
+ *   dz_out (M floats, nullable) <- d/dz (vec . d elbo / d params) =
+ *       -sum_s delta_dot_sm, delta_dot = w tau f_dot, summed in sample order.
+ * A non-NULL dz_out on a categorical plan returns PSVI_ESTATE.
+ * psvi_hvp_partial == psvi_hvp_ex(dz_out = NULL). */
+int psvi_hvp_ex(const psvi_plan* plan, const float* u, const int32_t* z, const float* w,
+                const float* eps, const float* params, const float* vec, int32_t include_kl,
+                float* hv_out, float* du_out, float* dw_out, float* dz_out, void* ws,
+                size_t ws_bytes, void* stream);
 
 /* Reverse of one Adam step (either variant) for the nested trainer's
  * reverse-mode pass through the unrolled inner loop (PSVI.nested_step,
