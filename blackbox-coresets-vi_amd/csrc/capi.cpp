@@ -1069,40 +1069,91 @@ static void drop_resident(const psvi_plan* p) {
     if (p) p->resident.valid = false;
 }
 
+// The entry points' plan check.  families: the allowed PSVI_FAMILY_* as a bit
+// mask, with `what` the message for a plan outside it (the phase entry points
+// report a null plan the same way); without them a null plan is the error.
+constexpr unsigned kFullCov = 1u << PSVI_FAMILY_FULLCOV, kNotFullCov = ~kFullCov;
+static int check_plan(const psvi_plan* p, unsigned families = ~0u, const char* what = nullptr) {
+    if (!p && !what) return fail(PSVI_EINVAL, "null plan");
+    if (!p || !(families >> p->family & 1u)) return fail(PSVI_ESTATE, what);
+    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    return 0;
+}
+static const char kNotMf[] = "not a mean-field plan", kNotFc[] = "not a full-cov plan";
+
+// The Adam hyper-parameters of an entry point that steps (required; the
+// gradient-only calls pass false and may leave hp null).
+static int check_adam(const psvi_adam_hp* hp, bool required = true) {
+    if (!required) return 0;
+    if (hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
+    if (hp->kind < 0 || hp->kind > 2) return fail(PSVI_EINVAL, "unknown adam kind");
+    return 0;
+}
+
+// The ABI's `const int32_t* z`: labels, or a Gaussian plan's fp32 targets in
+// the same 4-byte slots.
+static Targets abi_targets(const psvi_plan* p, const int32_t* z) {
+    return p->lik == PSVI_LIK_GAUSSIAN ? Targets::values(reinterpret_cast<const float*>(z))
+                                       : Targets::labels(z);
+}
+
 static int check_step(const psvi_plan* p, const void* u, const void* z, const void* w,
                       const void* eps, size_t ws_bytes, const void* ws) {
-    if (!p) return fail(PSVI_EINVAL, "null plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p)) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "fused step needs world == 1 (use phases)");
     if (!u || !z || !w || !eps) return fail(PSVI_EINVAL, "null input pointer");
     if (!ws || ws_bytes < p->ws_bytes) return fail(PSVI_ENOSPC, "workspace too small");
     return 0;
 }
 
-static int step_impl(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
+// the network launch on the rows (u, z, w), its NLL added into nll_out
+static NetLaunch net_rows(const float* u, Targets z, const float* w, double* nll_out) {
+    NetLaunch n;
+    n.u = u; n.targets = z; n.w = w; n.nll_out = nll_out;
+    return n;
+}
+
+// the full-cov update's Adam step on g_shard, its KL added into kl_out
+static MvnUpdate mvn_step(const float* eps, const float* g_shard, float* params, float* m,
+                          float* v, const psvi_adam_hp* hp, double* kl_out, int include_kl) {
+    MvnUpdate up;
+    up.eps = eps; up.g_shard = g_shard; up.params = params; up.m = m; up.v = v; up.hp = hp;
+    up.kl_out = kl_out; up.include_kl = include_kl ? 1 : 0;
+    return up;
+}
+
+static int step_impl(const psvi_plan* p, const float* u, Targets z, const float* w,
                      const float* eps, float* params, float* m, float* v,
                      const psvi_adam_hp* hp, double* elbo_out, float* grad_out,
                      int include_kl, void* ws, hipStream_t st) {
     HIP_TRY(hipMemsetAsync(elbo_out, 0, sizeof(double), st));
     char* wsb = (char*)ws;
-    if (p->family == PSVI_FAMILY_LENET) {
-        float* acc = (float*)wsb;
-        HIP_TRY(launch_lenet(*p, u, z, w, params, eps, acc, elbo_out, p->d_lenet_ws, st));
-        HIP_TRY(launch_mf_update(*p, acc, params, m, v, hp, elbo_out, grad_out, include_kl, st));
-    } else if (p->family == PSVI_FAMILY_MEANFIELD) {
-        // per-(sample, chunk) gradient slots, summed in a fixed order by the update
-        HIP_TRY(launch_net(*p, u, z, w, params, eps, p->d_mf_slots, nullptr, nullptr, elbo_out,
-                           st));
-        HIP_TRY(launch_mf_update(*p, nullptr, params, m, v, hp, elbo_out, grad_out, include_kl,
-                                 st, eps));
+    NetLaunch n = net_rows(u, z, w, elbo_out);
+    if (p->family != PSVI_FAMILY_FULLCOV) {
+        MfUpdate up;
+        up.params = params; up.m = m; up.v = v; up.hp = hp;
+        up.kl_out = elbo_out; up.grad_out = grad_out; up.include_kl = include_kl;
+        if (p->family == PSVI_FAMILY_LENET) {
+            float* acc = (float*)wsb;
+            HIP_TRY(launch_lenet(*p, u, z.slots(), w, params, eps, acc, elbo_out, p->d_lenet_ws, st));
+            up.acc = acc;
+        } else {
+            // per-(sample, chunk) gradient slots, summed in a fixed order by the update
+            n.params = params; n.eps = eps; n.mf_slots = p->d_mf_slots;
+            HIP_TRY(launch_net(*p, n, st));
+            up.slot_eps = eps;
+        }
+        HIP_TRY(launch_mf_update(*p, up, st));
     } else {
         const size_t xs = sizeof(float) * (size_t)p->d.S * p->rows_tot[0];
         float* x = (float*)wsb;
         float* g = (float*)(wsb + align256(xs));
         HIP_TRY(launch_mvn_fwd(*p, eps, params, x, st));
-        HIP_TRY(launch_net(*p, u, z, w, nullptr, nullptr, nullptr, x, g, elbo_out, st));
-        HIP_TRY(launch_mvn_update(*p, eps, g, params, m, v, hp, elbo_out, grad_out, include_kl,
-                                  nullptr, nullptr, st));
+        n.xrecv = x; n.gsend = g;
+        HIP_TRY(launch_net(*p, n, st));
+        MvnUpdate up = mvn_step(eps, g, params, m, v, hp, elbo_out, include_kl);
+        up.grad_out = grad_out;
+        HIP_TRY(launch_mvn_update(*p, up, st));
     }
     return 0;
 }
@@ -1115,10 +1166,9 @@ int psvi_inner_step(const psvi_plan* p, const float* u, const int32_t* z, const 
     if (int rc = check_step(p, u, z, w, eps, ws_bytes, ws)) return rc;
     if (!params || !adam_m || !adam_v || !hp || !elbo_out)
         return fail(PSVI_EINVAL, "null state pointer");
-    if (hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (hp->kind < 0 || hp->kind > 2) return fail(PSVI_EINVAL, "unknown adam kind");
-    return step_impl(p, u, z, w, eps, params, adam_m, adam_v, hp, elbo_out, nullptr, 1, ws,
-                     as_stream(stream));
+    if (int rc = check_adam(hp)) return rc;
+    return step_impl(p, u, abi_targets(p, z), w, eps, params, adam_m, adam_v, hp, elbo_out,
+                     nullptr, 1, ws, as_stream(stream));
 }
 
 int psvi_elbo_grad(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
@@ -1127,16 +1177,16 @@ int psvi_elbo_grad(const psvi_plan* p, const float* u, const int32_t* z, const f
     drop_resident(p);
     if (int rc = check_step(p, u, z, w, eps, ws_bytes, ws)) return rc;
     if (!params || !elbo_out || !grad_out) return fail(PSVI_EINVAL, "null pointer");
-    return step_impl(p, u, z, w, eps, const_cast<float*>(params), nullptr, nullptr, nullptr,
-                     elbo_out, grad_out, include_kl ? 1 : 0, ws, as_stream(stream));
+    return step_impl(p, u, abi_targets(p, z), w, eps, const_cast<float*>(params), nullptr,
+                     nullptr, nullptr, elbo_out, grad_out, include_kl ? 1 : 0, ws,
+                     as_stream(stream));
 }
 
 int psvi_mf_phase_accumulate(const psvi_plan* p, const float* u, const int32_t* z,
                              const float* w, const float* eps, const float* params, float* acc,
                              double* nll_out, void* stream) {
     drop_resident(p);
-    if (!p || p->family == PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a mean-field plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kNotFullCov, kNotMf)) return rc;
     if (!u || !z || !w || !eps || !params || !acc || !nll_out)
         return fail(PSVI_EINVAL, "null pointer");
     hipStream_t st = as_stream(stream);
@@ -1144,7 +1194,9 @@ int psvi_mf_phase_accumulate(const psvi_plan* p, const float* u, const int32_t* 
         HIP_TRY(launch_lenet(*p, u, z, w, params, eps, acc, nll_out, p->d_lenet_ws, st));
         return 0;
     }
-    HIP_TRY(launch_net(*p, u, z, w, params, eps, p->d_mf_slots, nullptr, nullptr, nll_out, st));
+    NetLaunch n = net_rows(u, abi_targets(p, z), w, nll_out);
+    n.params = params; n.eps = eps; n.mf_slots = p->d_mf_slots;
+    HIP_TRY(launch_net(*p, n, st));
     HIP_TRY(launch_mf_slot_acc(*p, eps, acc, st));
     return 0;
 }
@@ -1153,22 +1205,21 @@ int psvi_mf_phase_update(const psvi_plan* p, const float* acc, float* params, fl
                          float* adam_v, const psvi_adam_hp* hp, double* kl_out,
                          float* grad_out, int32_t include_kl, void* stream) {
     drop_resident(p);
-    if (!p || p->family == PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a mean-field plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kNotFullCov, kNotMf)) return rc;
     if (!acc || !params) return fail(PSVI_EINVAL, "null pointer");
     if (!grad_out && (!adam_m || !adam_v || !hp)) return fail(PSVI_EINVAL, "null adam state");
-    if (!grad_out && hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (!grad_out && (hp->kind < 0 || hp->kind > 2)) return fail(PSVI_EINVAL, "unknown adam kind");
-    HIP_TRY(launch_mf_update(*p, acc, params, adam_m, adam_v, hp, kl_out, grad_out,
-                             include_kl ? 1 : 0, as_stream(stream)));
+    if (int rc = check_adam(hp, !grad_out)) return rc;
+    MfUpdate up;
+    up.acc = acc; up.params = params; up.m = adam_m; up.v = adam_v; up.hp = hp;
+    up.kl_out = kl_out; up.grad_out = grad_out; up.include_kl = include_kl ? 1 : 0;
+    HIP_TRY(launch_mf_update(*p, up, as_stream(stream)));
     return 0;
 }
 
 int psvi_mvn_phase_sample(const psvi_plan* p, const float* eps, const float* params,
                           float* x_shard, void* stream) {
     drop_resident(p);
-    if (!p || p->family != PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a full-cov plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kFullCov, kNotFc)) return rc;
     // a rank that owns no rows (fewer bands than ranks) has an empty x shard
     if (!eps || !params || (!x_shard && p->rows_tot[p->rank] > 0))
         return fail(PSVI_EINVAL, "null pointer");
@@ -1179,14 +1230,14 @@ int psvi_mvn_phase_sample(const psvi_plan* p, const float* eps, const float* par
 int psvi_mvn_phase_net(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                        const float* x_recv, float* g_send, double* nll_out, void* stream) {
     drop_resident(p);
-    if (!p || p->family != PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a full-cov plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kFullCov, kNotFc)) return rc;
     // a rank without samples (S < world) has empty x / g blocks
     const bool none = p->s_cnt[p->rank] == 0;
     if (!u || !z || !w || (!none && (!x_recv || !g_send)) || !nll_out)
         return fail(PSVI_EINVAL, "null pointer");
-    hipStream_t st = as_stream(stream);
-    HIP_TRY(launch_net(*p, u, z, w, nullptr, nullptr, nullptr, x_recv, g_send, nll_out, st));
+    NetLaunch n = net_rows(u, Targets::labels(z), w, nll_out);
+    n.xrecv = x_recv; n.gsend = g_send;
+    HIP_TRY(launch_net(*p, n, as_stream(stream)));
     return 0;
 }
 
@@ -1194,17 +1245,17 @@ int psvi_mvn_phase_net_draw(const psvi_plan* p, const float* u, const int32_t* z
                             const float* x_recv, float* g_send, double* nll_out, float* eps_out,
                             int64_t n, uint64_t seed, uint64_t offset, void* stream) {
     drop_resident(p);
-    if (!p || p->family != PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a full-cov plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kFullCov, kNotFc)) return rc;
     const bool none = p->s_cnt[p->rank] == 0;  // S < world: empty x / g blocks
     if (!u || !z || !w || (!none && (!x_recv || !g_send)) || !nll_out || !eps_out || n < 0)
         return fail(PSVI_EINVAL, "null pointer or bad count");
     if (offset % 4) return fail(PSVI_EINVAL, "randn offset must be a multiple of 4");
     if (reinterpret_cast<uintptr_t>(eps_out) % 16)
         return fail(PSVI_EINVAL, "eps_out must be 16-byte aligned");
-    hipStream_t st = as_stream(stream);
-    HIP_TRY(launch_net(*p, u, z, w, nullptr, nullptr, nullptr, x_recv, g_send, nll_out, st, eps_out, n,
-                       seed, offset));
+    NetLaunch nl = net_rows(u, Targets::labels(z), w, nll_out);
+    nl.xrecv = x_recv; nl.gsend = g_send;
+    nl.draw.out = eps_out; nl.draw.n = n; nl.draw.seed = seed; nl.draw.offset = offset;
+    HIP_TRY(launch_net(*p, nl, as_stream(stream)));
     return 0;
 }
 
@@ -1213,8 +1264,7 @@ int psvi_mvn_phase_net_part(const psvi_plan* p, const float* u, const int32_t* z
                             int32_t s_count, float* eps_out, int64_t n, uint64_t seed,
                             uint64_t offset, int32_t part, int32_t nparts, void* stream) {
     drop_resident(p);
-    if (!p || p->family != PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a full-cov plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kFullCov, kNotFc)) return rc;
     const int S_loc = p->s_cnt[p->rank];
     if (s_begin < 0 || s_count < 0 || s_begin + s_count > S_loc)
         return fail(PSVI_EINVAL, "sample range outside the rank's samples");
@@ -1227,10 +1277,12 @@ int psvi_mvn_phase_net_part(const psvi_plan* p, const float* u, const int32_t* z
         return fail(PSVI_EINVAL, "eps_out must be 16-byte aligned");
     if (p->mchunks > 1 && !p->net_mloop && (s_begin != 0 || s_count != S_loc))
         return fail(PSVI_EUNSUP, "per-chunk gradient slots: whole sample launches only");
-    hipStream_t st = as_stream(stream);
-    HIP_TRY(launch_net(*p, u, z, w, nullptr, nullptr, nullptr, x_recv, g_send, nll_out, st,
-                       n > 0 ? eps_out : nullptr, n, seed, offset, nullptr, nullptr, s_begin, s_count,
-                       part, nparts));
+    NetLaunch nl = net_rows(u, Targets::labels(z), w, nll_out);
+    nl.xrecv = x_recv; nl.gsend = g_send;
+    nl.s_begin = s_begin; nl.s_count = s_count;
+    nl.draw.out = n > 0 ? eps_out : nullptr; nl.draw.n = n; nl.draw.seed = seed; nl.draw.offset = offset;
+    nl.draw.part = part; nl.draw.nparts = nparts;
+    HIP_TRY(launch_net(*p, nl, as_stream(stream)));
     return 0;
 }
 
@@ -1238,15 +1290,14 @@ int psvi_mvn_phase_update(const psvi_plan* p, const float* eps, const float* g_s
                           float* params, float* adam_m, float* adam_v, const psvi_adam_hp* hp,
                           double* kl_out, float* grad_out, int32_t include_kl, void* stream) {
     drop_resident(p);
-    if (!p || p->family != PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a full-cov plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kFullCov, kNotFc)) return rc;
     if (!eps || (!g_shard && p->rows_tot[p->rank] > 0) || !params)
         return fail(PSVI_EINVAL, "null pointer");
     if (!grad_out && (!adam_m || !adam_v || !hp)) return fail(PSVI_EINVAL, "null adam state");
-    if (!grad_out && hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (!grad_out && (hp->kind < 0 || hp->kind > 2)) return fail(PSVI_EINVAL, "unknown adam kind");
-    HIP_TRY(launch_mvn_update(*p, eps, g_shard, params, adam_m, adam_v, hp, kl_out, grad_out,
-                              include_kl ? 1 : 0, nullptr, nullptr, as_stream(stream)));
+    if (int rc = check_adam(hp, !grad_out)) return rc;
+    MvnUpdate up = mvn_step(eps, g_shard, params, adam_m, adam_v, hp, kl_out, include_kl);
+    up.grad_out = grad_out;
+    HIP_TRY(launch_mvn_update(*p, up, as_stream(stream)));
     return 0;
 }
 
@@ -1255,16 +1306,15 @@ int psvi_mvn_phase_update_sample(const psvi_plan* p, const float* eps, const flo
                                  const psvi_adam_hp* hp, double* kl_out, int32_t include_kl,
                                  const float* eps_next, float* x_next, void* stream) {
     drop_resident(p);
-    if (!p || p->family != PSVI_FAMILY_FULLCOV) return fail(PSVI_ESTATE, "not a full-cov plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p, kFullCov, kNotFc)) return rc;
     const bool rows = p->rows_tot[p->rank] > 0;  // no rows: empty G and x shards
     if (!eps || !params || !eps_next || (rows && (!g_shard || !x_next)))
         return fail(PSVI_EINVAL, "null pointer");
     if (!adam_m || !adam_v || !hp) return fail(PSVI_EINVAL, "null adam state");
-    if (hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (hp->kind < 0 || hp->kind > 2) return fail(PSVI_EINVAL, "unknown adam kind");
-    HIP_TRY(launch_mvn_update(*p, eps, g_shard, params, adam_m, adam_v, hp, kl_out, nullptr,
-                              include_kl ? 1 : 0, eps_next, x_next, as_stream(stream)));
+    if (int rc = check_adam(hp)) return rc;
+    MvnUpdate up = mvn_step(eps, g_shard, params, adam_m, adam_v, hp, kl_out, include_kl);
+    up.next.eps = eps_next; up.next.x = x_next;
+    HIP_TRY(launch_mvn_update(*p, up, as_stream(stream)));
     return 0;
 }
 
@@ -1321,10 +1371,10 @@ int psvi_mvn_phase_update_tiled(const psvi_plan* p, const float* eps, const floa
     if (!eps || !g_shard || !params || !adam_m || !adam_v || !tstate || !hp)
         return fail(PSVI_EINVAL, "null pointer");
     if (!eps_next != !x_next) return fail(PSVI_EINVAL, "eps_next and x_next go together");
-    if (hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (hp->kind < 0 || hp->kind > 2) return fail(PSVI_EINVAL, "unknown adam kind");
-    HIP_TRY(launch_mvn_update(*p, eps, g_shard, params, adam_m, adam_v, hp, kl_out, nullptr,
-                              include_kl ? 1 : 0, eps_next, x_next, as_stream(stream), tstate));
+    if (int rc = check_adam(hp)) return rc;
+    MvnUpdate up = mvn_step(eps, g_shard, params, adam_m, adam_v, hp, kl_out, include_kl);
+    up.next.eps = eps_next; up.next.x = x_next; up.tstate = tstate;
+    HIP_TRY(launch_mvn_update(*p, up, as_stream(stream)));
     return 0;
 }
 
@@ -1342,26 +1392,28 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
                        void* ws, size_t ws_bytes, int32_t flags, void* stream) {
     if (!p) return fail(PSVI_EINVAL, "null plan");
     if (flags & ~(PSVI_LOOP_KEEP | PSVI_LOOP_RESUME)) return fail(PSVI_EINVAL, "unknown loop flags");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p)) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "inner loop needs world == 1 (use phases)");
     if (!u || !z || !w || !params || !adam_m || !adam_v || !hp || !elbo_out)
         return fail(PSVI_EINVAL, "null pointer");
     if (T < 0) return fail(PSVI_EINVAL, "T must be >= 0");
-    if (hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (hp->kind < 0 || hp->kind > 2) return fail(PSVI_EINVAL, "unknown adam kind");
+    if (int rc = check_adam(hp)) return rc;
     if (!eps && offset % 4) return fail(PSVI_EINVAL, "randn offset must be a multiple of 4");
     if (!ws || ws_bytes < loop_ws_bytes(p)) return fail(PSVI_ENOSPC, "workspace too small");
     hipStream_t st = as_stream(stream);
     char* wsb = (char*)ws;
     const int64_t es = eps_stride(p);
+    const Targets zt = abi_targets(p, z);
     float* ebuf[2] = {(float*)(wsb + align256(p->ws_bytes)),
                       (float*)(wsb + align256(p->ws_bytes) + loop_ebuf_bytes(p))};
     // eps of step t: the caller's [T][EPS_COUNT] array, or Philox (seed, offset + t * stride)
+    RandnLaunch rn;  // the draw of one step's eps from the loop's stream
+    rn.n = p->Peps; rn.seed = seed;
     auto eps_t = [&](int t) -> const float* {
         if (eps) return eps + (size_t)t * p->Peps;
-        float* b = ebuf[t & 1];
-        return launch_randn(b, p->Peps, seed, offset + (uint64_t)t * es, st) == hipSuccess ? b
-                                                                                         : nullptr;
+        RandnLaunch r = rn;
+        r.out = ebuf[t & 1]; r.offset = offset + (uint64_t)t * es;
+        return launch_randn(r, st) == hipSuccess ? r.out : nullptr;
     };
     // eps of step 0 with the ELBO accumulators cleared: Philox mode folds the
     // clear into the draw's launch
@@ -1371,9 +1423,9 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
                        ? eps
                        : nullptr;
         }
-        return launch_randn(ebuf[0], p->Peps, seed, offset, st, elbo_out, T) == hipSuccess
-                   ? ebuf[0]
-                   : nullptr;
+        RandnLaunch r = rn;
+        r.out = ebuf[0]; r.offset = offset; r.zero = elbo_out; r.nzero = T;
+        return launch_randn(r, st) == hipSuccess ? ebuf[0] : nullptr;
     };
     psvi_adam_hp h = *hp;
     if (p->family == PSVI_FAMILY_MEANFIELD) {
@@ -1387,11 +1439,15 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
             h.step = hp->step + t;
             const bool draw = !eps && t + 1 < T;
             float* en_buf = draw ? ebuf[(t + 1) & 1] : nullptr;
-            HIP_TRY(launch_net(*p, u, z, w, params, e, p->d_mf_slots, nullptr, nullptr,
-                               elbo_out + t, st, en_buf, draw ? p->Peps : 0, seed,
-                               offset + (uint64_t)(t + 1) * es));
-            HIP_TRY(launch_mf_update(*p, nullptr, params, adam_m, adam_v, &h, elbo_out + t,
-                                     nullptr, 1, st, e));
+            NetLaunch n = net_rows(u, zt, w, elbo_out + t);
+            n.params = params; n.eps = e; n.mf_slots = p->d_mf_slots;
+            n.draw.out = en_buf; n.draw.n = draw ? p->Peps : 0;
+            n.draw.seed = seed; n.draw.offset = offset + (uint64_t)(t + 1) * es;
+            HIP_TRY(launch_net(*p, n, st));
+            MfUpdate up;
+            up.slot_eps = e; up.params = params; up.m = adam_m; up.v = adam_v; up.hp = &h;
+            up.kl_out = elbo_out + t; up.include_kl = 1;
+            HIP_TRY(launch_mf_update(*p, up, st));
             e = t + 1 < T ? (eps ? eps + (size_t)(t + 1) * p->Peps : en_buf) : nullptr;
         }
         return 0;
@@ -1401,7 +1457,7 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
             const float* e = eps_t(t);
             if (!e) return fail(PSVI_EUNSUP, "randn launch failed");
             h.step = hp->step + t;
-            if (int rc = step_impl(p, u, z, w, e, params, adam_m, adam_v, &h, elbo_out + t,
+            if (int rc = step_impl(p, u, zt, w, e, params, adam_m, adam_v, &h, elbo_out + t,
                                    nullptr, 1, ws, st))
                 return rc;
         }
@@ -1449,7 +1505,9 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
         // ELBO accumulators cleared by the draw kernel's zero-fill with no draw
         // (a library kernel: hipMemsetAsync's first use in a process loads the
         // runtime's own fill kernels inside the caller's timed region)
-        HIP_TRY(launch_randn(ebuf[1 - bi(0)], 0, 0, 0, st, elbo_out, T));
+        RandnLaunch clear;
+        clear.out = ebuf[1 - bi(0)]; clear.zero = elbo_out; clear.nzero = T;
+        HIP_TRY(launch_randn(clear, st));
         e = ebuf[bi(0)];
     } else {
         // packed -> tiled state on the plan's conversion stream, behind x_0 and the
@@ -1465,7 +1523,10 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
         }
         if (pbuf[0]) {
             HIP_TRY(hipMemsetAsync(pbuf[0], 0, 2 * loop_pbuf_bytes(p), st));
-            HIP_TRY(launch_randn(ebuf[0], p->Peps, seed, offset, st, elbo_out, T, &p->eps_planes, pbuf[0]));
+            RandnLaunch r = rn;
+            r.out = ebuf[0]; r.offset = offset; r.zero = elbo_out; r.nzero = T;
+            r.planes_desc = &p->eps_planes; r.planes = pbuf[0];
+            HIP_TRY(launch_randn(r, st));
             e = ebuf[0];
         } else {
             e = first_eps();
@@ -1483,9 +1544,11 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
         uint16_t* en_pl = draw ? pbuf[bi(t + 1)] : nullptr;
         const bool tm = g_loop_every > 0 && t % g_loop_every == 0;
         if (tm) HIP_TRY(loop_event(0, st));
-        HIP_TRY(launch_net(*p, u, z, w, nullptr, nullptr, nullptr, x, g, elbo_out + t,
-                           st, en_buf, draw ? p->Peps : 0, seed, offset + (uint64_t)(t + 1) * es,
-                           nullptr, en_pl));
+        NetLaunch n = net_rows(u, zt, w, elbo_out + t);
+        n.xrecv = x; n.gsend = g;
+        n.draw.out = en_buf; n.draw.n = draw ? p->Peps : 0; n.draw.planes = en_pl;
+        n.draw.seed = seed; n.draw.offset = offset + (uint64_t)(t + 1) * es;
+        HIP_TRY(launch_net(*p, n, st));
         if (tm) HIP_TRY(loop_event(0, st));
         const float* en = !last ? (eps ? eps + (size_t)(t + 1) * p->Peps : en_buf) : (keep ? en_buf : nullptr);
         if (tm) HIP_TRY(loop_event(1, st));
@@ -1495,9 +1558,12 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
         }
         // the last step (no next sample) writes corr / m / v back to the packed
         // arrays; KEEP: it samples as every step, then the tiled state is copied out
-        HIP_TRY(launch_mvn_update(*p, e, g, params, adam_m, adam_v, &h, elbo_out + t, nullptr, 1,
-                                  en, en ? x : nullptr, st, ts, ts && !en, nullptr, padded,
-                                  pbuf[bi(t)], en ? en_pl : nullptr));
+        MvnUpdate up = mvn_step(e, g, params, adam_m, adam_v, &h, elbo_out + t, 1);
+        up.tstate = ts; up.packed_out = ts && !en; up.padded = padded; up.eps_planes = pbuf[bi(t)];
+        if (en) {
+            up.next.eps = en; up.next.x = x; up.next.planes = en_pl;
+        }
+        HIP_TRY(launch_mvn_update(*p, up, st));
         if (tm) HIP_TRY(loop_event(1, st));
         e = en;
     }
@@ -1513,20 +1579,20 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
 // Otherwise [rowcoef (S x 2) | ck (S) | sck (1)] replace the combine: the
 // backward of a caller-formed softmax over samples (sample-sharded outer).
 static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
-                      const int32_t* z_all, const float* w_all, const float* eps,
+                      const int32_t* z_abi, const float* w_all, const float* eps,
                       const float* params, double* loss_out, float* grad_params,
                       float* grad_u, float* grad_w, double* sample_out,
                       const float* ext_coef, void* ws, size_t ws_bytes, void* stream,
                       int ablated = 0, float* grad_z = nullptr) {
     drop_resident(p);
-    if (!p) return fail(PSVI_EINVAL, "null plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p)) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "the outer objective needs world == 1");
     if (p->d.S < 1) return fail(PSVI_EINVAL, "S must be >= 1");
     if (p->d.S > 2048) return fail(PSVI_EUNSUP, "the outer objective supports S <= 2048");
     if (n_pseudo < 0 || n_pseudo > p->d.M) return fail(PSVI_EINVAL, "n_pseudo out of [0, M]");
-    if (!x_all || !z_all || !w_all || !eps || !params || (!loss_out && !ext_coef))
+    if (!x_all || !z_abi || !w_all || !eps || !params || (!loss_out && !ext_coef))
         return fail(PSVI_EINVAL, "null pointer");
+    const Targets z_all = abi_targets(p, z_abi);
     if (grad_u && !grad_params)
         return fail(PSVI_EINVAL, "grad_u needs grad_params (one backward pass gives both)");
     if (grad_z && p->lik != PSVI_LIK_GAUSSIAN)
@@ -1553,12 +1619,13 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
     if (!ext_coef) HIP_TRY(launch_outer_stats(*p, params, eps, x, o.stats, st));
     // 1. forward: every row's NLL
     NetOuter fw{1, n_pseudo, o.nll, nullptr, nullptr, nullptr};
+    NetLaunch n = net_rows(x_all, z_all, w_all, nullptr);
+    n.params = params; n.eps = eps; n.xrecv = x; n.outer = &fw;
     if (p->family == PSVI_FAMILY_LENET)
-        HIP_TRY(launch_lenet(*p, x_all, z_all, w_all, params, eps, nullptr, nullptr,
+        HIP_TRY(launch_lenet(*p, x_all, z_all.slots(), w_all, params, eps, nullptr, nullptr,
                              p->d_lenet_ws, st, &fw));
     else
-        HIP_TRY(launch_net(*p, x_all, z_all, w_all, params, eps, nullptr, x, nullptr, nullptr,
-                           st, nullptr, 0, 0, 0, &fw));
+        HIP_TRY(launch_net(*p, n, st));
     if (!ext_coef) {
         // 2. per-sample terms, softmax over samples, loss, backward coefficients
         HIP_TRY(launch_outer_combine(*p, n_pseudo, params, w_all, o.nll, o.stats, loss_out,
@@ -1577,22 +1644,29 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
     // 3. backward through the network with the row coefficients (+ sampled-KL path)
     NetOuter bw{2, n_pseudo, nullptr, o.rowcoef, o.ck, grad_u ? o.du : nullptr, nullptr,
                 grad_z ? o.dz : nullptr};
+    NetLaunch b = net_rows(x_all, z_all, w_all, nullptr);
+    b.outer = &bw;
     if (p->family == PSVI_FAMILY_FULLCOV) {
-        HIP_TRY(launch_net(*p, x_all, z_all, w_all, nullptr, nullptr, nullptr, x, g, nullptr, st,
-                           nullptr, 0, 0, 0, &bw));
+        b.xrecv = x; b.gsend = g;
+        HIP_TRY(launch_net(*p, b, st));
         // 4. reparameterised backward (no KL term: the sampled KL came in through G)
-        HIP_TRY(launch_mvn_update(*p, eps, g, const_cast<float*>(params), nullptr, nullptr,
-                                  nullptr, nullptr, grad_params, 0, nullptr, nullptr, st));
-    } else if (p->family == PSVI_FAMILY_LENET) {
-        HIP_TRY(launch_lenet(*p, x_all, z_all, w_all, params, eps, acc, nullptr, p->d_lenet_ws,
-                             st, &bw));
-        HIP_TRY(launch_mf_update(*p, acc, const_cast<float*>(params), nullptr, nullptr, nullptr,
-                                 nullptr, grad_params, 0, st));
+        MvnUpdate up;
+        up.eps = eps; up.g_shard = g; up.params = const_cast<float*>(params);
+        up.grad_out = grad_params;
+        HIP_TRY(launch_mvn_update(*p, up, st));
     } else {
-        HIP_TRY(launch_net(*p, x_all, z_all, w_all, params, eps, p->d_mf_slots, nullptr, nullptr,
-                           nullptr, st, nullptr, 0, 0, 0, &bw));
-        HIP_TRY(launch_mf_update(*p, nullptr, const_cast<float*>(params), nullptr, nullptr,
-                                 nullptr, nullptr, grad_params, 0, st, eps));
+        MfUpdate up;
+        up.params = const_cast<float*>(params); up.grad_out = grad_params;
+        if (p->family == PSVI_FAMILY_LENET) {
+            HIP_TRY(launch_lenet(*p, x_all, z_all.slots(), w_all, params, eps, acc, nullptr,
+                                 p->d_lenet_ws, st, &bw));
+            up.acc = acc;
+        } else {
+            b.params = params; b.eps = eps; b.mf_slots = p->d_mf_slots;
+            HIP_TRY(launch_net(*p, b, st));
+            up.slot_eps = eps;
+        }
+        HIP_TRY(launch_mf_update(*p, up, st));
     }
     // 5. explicit log-det term on the scales; d loss / d u
     HIP_TRY(launch_outer_finish(*p, n_pseudo, params, o.sck, grad_params, o.du, grad_u, st));
@@ -1656,8 +1730,7 @@ int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, cons
                   const float* w_all, const float* eps, const float* params, int32_t correction,
                   float* probs_out, double* stats_out, void* ws, size_t ws_bytes, void* stream) {
     drop_resident(p);
-    if (!p) return fail(PSVI_EINVAL, "null plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p)) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "evaluate needs world == 1");
     if (p->lik != PSVI_LIK_CATEGORICAL)
         return fail(PSVI_ESTATE, "a Gaussian-likelihood plan evaluates with "
@@ -1681,12 +1754,13 @@ int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, cons
     }
     HIP_TRY(launch_outer_stats(*p, params, eps, x, o.stats, st));
     NetOuter fw{1, n_pseudo, o.nll, nullptr, nullptr, nullptr, prob};
+    NetLaunch n = net_rows(x_all, Targets::labels(z_all), w_all, nullptr);
+    n.params = params; n.eps = eps; n.xrecv = x; n.outer = &fw;
     if (p->family == PSVI_FAMILY_LENET)
         HIP_TRY(launch_lenet(*p, x_all, z_all, w_all, params, eps, nullptr, nullptr,
                              p->d_lenet_ws, st, &fw));
     else
-        HIP_TRY(launch_net(*p, x_all, z_all, w_all, params, eps, nullptr, x, nullptr, nullptr,
-                           st, nullptr, 0, 0, 0, &fw));
+        HIP_TRY(launch_net(*p, n, st));
     HIP_TRY(launch_eval(*p, n_pseudo, params, w_all, z_all, o.nll, o.stats, prob,
                         correction ? 1 : 0, W, probs_out, stats_out, st));
     return 0;
@@ -1698,8 +1772,7 @@ int psvi_evaluate_regression(const psvi_plan* p, int32_t n_pseudo, const float* 
                              float* pred_out, double* stats_out, void* ws, size_t ws_bytes,
                              void* stream) {
     drop_resident(p);
-    if (!p) return fail(PSVI_EINVAL, "null plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p)) return rc;
     if (p->lik != PSVI_LIK_GAUSSIAN)
         return fail(PSVI_ESTATE, "psvi_evaluate_regression needs a Gaussian-likelihood plan");
     if (p->d.S < 2) return fail(PSVI_EINVAL, "evaluate needs S > 1 (psvi_classes.py:2229)");
@@ -1716,8 +1789,9 @@ int psvi_evaluate_regression(const psvi_plan* p, int32_t n_pseudo, const float* 
                         align256(sizeof(float) * (size_t)p->d.S * p->d.M));
     HIP_TRY(launch_outer_stats(*p, params, eps, nullptr, o.stats, st));
     NetOuter fw{1, n_pseudo, o.nll, nullptr, nullptr, nullptr, f};
-    HIP_TRY(launch_net(*p, x_all, reinterpret_cast<const int32_t*>(y_all), w_all, params, eps,
-                       nullptr, nullptr, nullptr, nullptr, st, nullptr, 0, 0, 0, &fw));
+    NetLaunch n = net_rows(x_all, Targets::values(y_all), w_all, nullptr);
+    n.params = params; n.eps = eps; n.outer = &fw;
+    HIP_TRY(launch_net(*p, n, st));
     HIP_TRY(launch_eval_regression(*p, n_pseudo, params, y_all + n_pseudo, o.stats, f,
                                    correction ? 1 : 0, y_mean, y_std, W, pred_out, stats_out, st));
     return 0;
@@ -1736,8 +1810,7 @@ int psvi_hvp_ex(const psvi_plan* p, const float* u, const int32_t* z, const floa
                 float* hv_out, float* du_out, float* dw_out, float* dz_out, void* ws,
                 size_t ws_bytes, void* stream) {
     drop_resident(p);
-    if (!p) return fail(PSVI_EINVAL, "null plan");
-    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    if (int rc = check_plan(p)) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "psvi_hvp needs world == 1");
     if (!u || !z || !w || !eps || !params || !vec || !hv_out)
         return fail(PSVI_EINVAL, "null pointer");
@@ -1767,16 +1840,28 @@ int psvi_hvp_ex(const psvi_plan* p, const float* u, const int32_t* z, const floa
     const bool two = rop_splits(*p) == 2 &&
                      (p->family != PSVI_FAMILY_FULLCOV || mvn_grad_takes_slots(*p));
     const int64_t slot2 = two ? (int64_t)p->d.S * p->n_tot : 0;
-    HIP_TRY(launch_net_rop(*p, u, z, w, x, o.xd, params, vec, eps, o.G, o.Gd,
-                           du_out ? o.du : nullptr, dw_out ? o.nlld : nullptr, st, !two,
-                           dz_out ? o.dzd : nullptr));
-    if (p->family == PSVI_FAMILY_FULLCOV)  // J^T G_dot (mean, sd, corr; + the corr KL block)
-        HIP_TRY(launch_mvn_update(*p, eps, o.Gd, const_cast<float*>(params), nullptr, nullptr,
-                                  nullptr, nullptr, hv_out, 0, nullptr, nullptr, st, nullptr,
-                                  false, include_kl ? vec : nullptr, false, nullptr, nullptr,
-                                  two ? o.Gd + slot2 : nullptr));
-    HIP_TRY(launch_hvp_assemble(*p, params, vec, eps, o.G, o.Gd, o.du, o.nlld, hv_out, du_out,
-                                dw_out, st, include_kl != 0, slot2));
+    HvpAssemble asm_req;
+    asm_req.params = params; asm_req.vec = vec; asm_req.eps = eps;
+    asm_req.G = o.G; asm_req.Gd = o.Gd; asm_req.du = o.du; asm_req.nlld = o.nlld;
+    asm_req.hv = hv_out; asm_req.d_u = du_out; asm_req.d_w = dw_out;
+    asm_req.include_kl = include_kl != 0; asm_req.slot2 = slot2;
+    NetRop rop;
+    rop.u = u; rop.targets = abi_targets(p, z); rop.w = w; rop.x = x; rop.xd = o.xd;
+    rop.params = params; rop.vec = vec; rop.eps = eps; rop.G = o.G; rop.Gd = o.Gd;
+    if (du_out) rop.du = o.du;
+    if (dw_out) rop.nlld = o.nlld;
+    if (dz_out) rop.dzd = o.dzd;
+    rop.sum_slots = !two;
+    HIP_TRY(launch_net_rop(*p, rop, st));
+    if (p->family == PSVI_FAMILY_FULLCOV) {  // J^T G_dot (mean, sd, corr; + the corr KL block)
+        MvnUpdate up;
+        up.eps = eps; up.g_shard = o.Gd; up.params = const_cast<float*>(params);
+        up.grad_out = hv_out;
+        if (include_kl) up.kl_vec = vec;
+        if (two) up.g_shard2 = o.Gd + slot2;
+        HIP_TRY(launch_mvn_update(*p, up, st));
+    }
+    HIP_TRY(launch_hvp_assemble(*p, asm_req, st));
     // d/dz_m (vec . d elbo / d params) = -sum_s delta_dot_sm, in sample order
     if (dz_out) HIP_TRY(launch_sample_sum(p->d.S, p->d.M, o.dzd, dz_out, st));
     return 0;
@@ -1812,7 +1897,9 @@ int psvi_nonfinite(const void* data, int64_t n, int32_t dtype, int32_t* flag, vo
 int psvi_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
     if (!out || n < 0) return fail(PSVI_EINVAL, "bad randn arguments");
     if (offset % 4) return fail(PSVI_EINVAL, "randn offset must be a multiple of 4");
-    HIP_TRY(launch_randn(out, n, seed, offset, as_stream(stream)));
+    RandnLaunch r;
+    r.out = out; r.n = n; r.seed = seed; r.offset = offset;
+    HIP_TRY(launch_randn(r, as_stream(stream)));
     return 0;
 }
 
@@ -1820,8 +1907,7 @@ int psvi_adam_update(int64_t n, float* params, const float* grad, float* adam_m,
                      const psvi_adam_hp* hp, void* stream) {
     if (n < 0 || !params || !grad || !adam_m || !adam_v || !hp)
         return fail(PSVI_EINVAL, "bad adam arguments");
-    if (hp->step < 1) return fail(PSVI_EINVAL, "adam step must be >= 1");
-    if (hp->kind < 0 || hp->kind > 2) return fail(PSVI_EINVAL, "unknown adam kind");
+    if (int rc = check_adam(hp)) return rc;
     HIP_TRY(launch_adam(n, params, grad, adam_m, adam_v, hp, as_stream(stream)));
     return 0;
 }

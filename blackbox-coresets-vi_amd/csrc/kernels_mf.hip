@@ -284,32 +284,29 @@ hipError_t launch_mf_slot_acc(const psvi_plan& p, const float* eps, float* acc, 
     return hipGetLastError();
 }
 
-hipError_t launch_mf_update(const psvi_plan& p, const float* acc, float* params, float* m,
-                            float* v, const psvi_adam_hp* hp, double* kl_out,
-                            float* grad_out, int include_kl, hipStream_t st,
-                            const float* slot_eps) {
-    const bool slots = acc == nullptr;
-    if (slots && (!p.d_mf_slots || !slot_eps)) return hipErrorInvalidValue;
+hipError_t launch_mf_update(const psvi_plan& p, const MfUpdate& r, hipStream_t st) {
+    const bool slots = r.acc == nullptr;
+    if (slots && (!p.d_mf_slots || !r.slot_eps)) return hipErrorInvalidValue;
     MfUpdArgs a{};
-    mf_slot_args(p, slot_eps, a);
+    mf_slot_args(p, r.slot_eps, a);
     a.woff[p.L] = p.n_tot;
-    a.acc = acc;
+    a.acc = r.acc;
     a.n_tot = p.n_tot;
-    a.params = params;
-    a.m = m;
-    a.v = v;
-    a.grad_out = grad_out;
-    a.kl_out = kl_out;
-    a.include_kl = include_kl;
+    a.params = r.params;
+    a.m = r.m;
+    a.v = r.v;
+    a.grad_out = r.grad_out;
+    a.kl_out = r.kl_out;
+    a.include_kl = r.include_kl;
     a.kl_mask = p.family == PSVI_FAMILY_LENET ? 0x1Cu : 0xFFu;
     const float s0 = p.d.prior_sd;
     a.inv_s0sq = 1.f / (s0 * s0);
     a.log_s0 = logf(s0);
-    if (hp) a.adam = make_adam(hp);
+    if (r.hp) a.adam = make_adam(r.hp);
     const int nb = slots ? (p.n_tot + kSlotGroups - 1) / kSlotGroups : (p.n_tot + 255) / 256;
-    if (grad_out && slots)
+    if (r.grad_out && slots)
         hipLaunchKernelGGL((mf_update_kernel<true, true>), dim3(nb), dim3(256), 0, st, a);
-    else if (grad_out)
+    else if (r.grad_out)
         hipLaunchKernelGGL((mf_update_kernel<true, false>), dim3(nb), dim3(256), 0, st, a);
     else if (slots)
         hipLaunchKernelGGL((mf_update_kernel<false, true>), dim3(nb), dim3(256), 0, st, a);
@@ -368,22 +365,24 @@ __global__ __launch_bounds__(256) void randn_planes_kernel(float* __restrict__ o
     for (int64_t q = q_lo + gid; q < q_hi; q += gs) randn_quad_planes(out, n, seed, offset, q, P, planes);
 }
 
-hipError_t launch_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st,
-                        double* zero, int64_t nzero, const EpsPlanes* planes_desc, uint16_t* planes,
-                        int64_t q_lo, int64_t q_hi) {
-    if (n <= 0 && nzero <= 0) return hipSuccess;
-    if (!zero) nzero = 0;
+hipError_t launch_randn(const RandnLaunch& r, hipStream_t st) {
+    float* const out = r.out;
+    const int64_t n = r.n;
+    const uint64_t seed = r.seed, offset = r.offset;
+    double* const zero = r.zero;
+    if (n <= 0 && r.nzero <= 0) return hipSuccess;
+    const int64_t nzero = zero ? r.nzero : 0;
     // the quads drawn: all of [0, ceil(n / 4)), or the caller's part of them
     const int64_t nqa = (std::max<int64_t>(n, 0) + 3) / 4;
-    q_hi = q_hi < 0 ? nqa : std::min(q_hi, nqa);
-    q_lo = std::max<int64_t>(q_lo, 0);
+    const int64_t q_hi = r.q_hi < 0 ? nqa : std::min(r.q_hi, nqa);
+    const int64_t q_lo = std::max<int64_t>(r.q_lo, 0);
     if (q_hi <= q_lo && nzero <= 0) return hipSuccess;
     const int64_t nb = std::max<int64_t>(
         1, std::min<int64_t>(std::max(std::max<int64_t>(q_hi - q_lo, 0), nzero) / 256 + 1, 4096));
-    if (planes && planes_desc) {
+    if (r.planes && r.planes_desc) {
         if ((uintptr_t)out & 15) return hipErrorInvalidValue;
         hipLaunchKernelGGL(randn_planes_kernel, dim3((unsigned)nb), dim3(256), 0, st, out, n, seed,
-                           offset, zero, nzero, *planes_desc, planes, q_lo, q_hi);
+                           offset, zero, nzero, *r.planes_desc, r.planes, q_lo, q_hi);
         return hipGetLastError();
     }
     if (((uintptr_t)out & 15) == 0)

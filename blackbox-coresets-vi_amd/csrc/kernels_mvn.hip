@@ -3245,8 +3245,9 @@ hipError_t launch_mvn_fwd_pair(const psvi_plan& p, const float* eps, const float
     return hipGetLastError();
 }
 
-template <int NS>
-static void launch_stream_ns(int kind, dim3 g, dim3 bl, hipStream_t st, const StrArgs& b, bool pad) {
+// the streaming update on four 32-sample groups (S = 128)
+static void launch_stream(int kind, dim3 g, dim3 bl, hipStream_t st, const StrArgs& b, bool pad) {
+    constexpr int NS = 4;
     if (pad && kind == PSVI_ADAM_HIGHER)
         hipLaunchKernelGGL((mvn_stream_kernel<NS, PSVI_ADAM_HIGHER, false, true, true>), g, bl, 0, st, b);
     else if (pad)
@@ -3262,90 +3263,84 @@ static void launch_stream_ns(int kind, dim3 g, dim3 bl, hipStream_t st, const St
 static bool stream_ok(int S, int kind) {
     return S == 128 && (kind == PSVI_ADAM_HIGHER || kind == PSVI_ADAM_HYPERGRAD);
 }
-static void launch_stream(int ns, int kind, dim3 g, dim3 bl, hipStream_t st, const StrArgs& b,
-                          bool pad) {
-    (void)ns;
-    launch_stream_ns<4>(kind, g, bl, st, b, pad);
-}
-
 bool mvn_grad_takes_slots(const psvi_plan& p) {
     return p.n_kwg > 0 && !g_ks_off && !g_ks_bf_off;
 }
 
-hipError_t launch_mvn_update(const psvi_plan& p, const float* eps, const float* g_shard,
-                             float* params, float* m, float* v, const psvi_adam_hp* hp,
-                             double* kl_out, float* grad_out, int include_kl,
-                             const float* eps_next, float* x_next, hipStream_t st,
-                             float* tstate, bool packed_out, const float* kl_vec, bool padded,
-                             const uint16_t* eps_planes, const uint16_t* eps_next_planes,
-                             const float* g_shard2) {
-    UpdArgs a{};
-    a.kl_vec = kl_vec;
-    a.chunks = p.d_upd;
-    a.eps = eps;
-    a.g = g_shard;
+// the fields UpdArgs, StrArgs and KsArgs share by name
+template <class Args>
+static void fill_update(const psvi_plan& p, const MvnUpdate& r, Args& a) {
+    a.eps = r.eps;
+    a.g = r.g_shard;
     a.ldg = p.rows_tot[p.rank];
     a.S = p.d.S;
     a.g_total = (int64_t)p.d.S * p.rows_tot[p.rank];
     a.e_total = p.Peps;
-    a.params = params;
-    a.m = m;
-    a.v = v;
-    a.grad_out = grad_out;
-    a.kl_out = kl_out;
-    a.include_kl = include_kl;
-    a.abl = g_upd_ablation;
+    a.params = r.params;
+    a.m = r.m;
+    a.v = r.v;
+    a.kl_out = r.kl_out;
+    a.include_kl = r.include_kl;
     a.stamps = g_upd_stamps;
-    a.pcount = p.P;
     const float s0 = p.d.prior_sd;
     a.inv_s0sq = 1.f / (s0 * s0);
     a.log_s0 = logf(s0);
-    if (hp) a.adam = make_adam(hp);
+    if (r.hp) a.adam = make_adam(r.hp);
     fill_layers(p, a.lay);
+}
+
+// x_next = mean' + softplus(sd') eps_next + the sum of each row block's partial slots
+static hipError_t launch_next_reduce(const psvi_plan& p, const MvnUpdate& r, const FwdRowBlock* rbs,
+                                     int nrb, const float* part, hipStream_t st) {
+    FwdArgs f{};
+    f.params = r.params;
+    f.eps = r.next.eps;
+    f.ldx = p.rows_tot[p.rank];
+    f.S = p.d.S;
+    fill_layers(p, f.lay);
+    constexpr int spb = kRedSpb;
+    hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(nrb, (f.S + spb - 1) / spb), dim3(256), 0, st,
+                       rbs, part, f, r.next.x);
+    return hipGetLastError();
+}
+
+hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t st) {
+    UpdArgs a{};
+    fill_update(p, r, a);
+    a.kl_vec = r.kl_vec;
+    a.chunks = p.d_upd;
+    a.grad_out = r.grad_out;
+    a.abl = g_upd_ablation;
+    a.pcount = p.P;
     if (p.n_upd == 0) return hipSuccess;
     const dim3 grid(p.n_upd), block(256);
     const int mode = a.S > USB ? 2 : a.S > UEH ? 1 : 0;  // samples per LDS pass
-    if (tstate) {
+    if (r.tstate) {
         // tiled state (psvi_inner_loop on a fusable plan): corr / m / v in tstate
         const int64_t tf = p.tiles_total * 4096;
-        a.tp = tstate;
-        a.tm = tstate + tf;
-        a.tv = tstate + 2 * tf;
-        if (eps_next && p.n_str > 0 && g_stream_off != 1 && stream_ok(a.S, a.adam.kind)) {
+        a.tp = r.tstate;
+        a.tm = r.tstate + tf;
+        a.tv = r.tstate + 2 * tf;
+        if (r.next.eps && p.n_str > 0 && g_stream_off != 1 && stream_ok(a.S, a.adam.kind)) {
             StrArgs b{};
+            fill_update(p, r, b);
             b.ranges = p.d_str;
-            b.eps = eps;
-            b.eps_next = eps_next;
-            b.g = g_shard;
-            b.ldg = a.ldg;
-            b.S = a.S;
-            b.g_total = a.g_total;
-            b.e_total = a.e_total;
-            b.params = params;
-            b.m = m;
-            b.v = v;
+            b.eps_next = r.next.eps;
             b.tp = a.tp;
             b.tm = a.tm;
             b.tv = a.tv;
             b.part = p.d_str_part;
-            b.kl_out = kl_out;
-            b.include_kl = include_kl;
-            b.stamps = g_upd_stamps;
-            b.inv_s0sq = a.inv_s0sq;
-            b.log_s0 = a.log_s0;
-            b.adam = a.adam;
             for (int l = 0; l < p.L; ++l) {
                 b.xcol[l] = p.xcol_l[p.rank][l];
                 b.nb[l] = p.lay[l].nb;
             }
-            fill_layers(p, b.lay);
             const dim3 sg(p.n_str);
-            const bool bf = eps_planes && eps_next_planes && p.bf_stream && padded && !g_stream_bf_off;
+            const bool bf = r.eps_planes && r.next.planes && p.bf_stream && r.padded && !g_stream_bf_off;
             if (bf) {
                 b.stamps = g_bf_stamps;
                 // both products on the bf16 matrix cores (fp32-faithful pieces)
-                b.ep = eps_planes;
-                b.enp = eps_next_planes;
+                b.ep = r.eps_planes;
+                b.enp = r.next.planes;
                 b.pl = p.eps_planes.pl;
                 for (int l = 0; l < p.L; ++l) {
                     b.ppoff[l] = p.eps_planes.poff[l];
@@ -3356,7 +3351,7 @@ hipError_t launch_mvn_update(const psvi_plan& p, const float* eps, const float* 
                 b.rbs = p.d_sfrb;
                 b.bcnt = p.d_str_cnt;
                 b.bms = p.d_str_bms;
-                b.x = x_next;
+                b.x = r.next.x;
                 b.ldx = p.rows_tot[p.rank];
                 if (fold && b.stamps && b.adam.kind == PSVI_ADAM_HIGHER)
                     hipLaunchKernelGGL((mvn_stream_bf2_kernel<PSVI_ADAM_HIGHER, true, true>), sg, b8, 0, st, b);
@@ -3372,33 +3367,16 @@ hipError_t launch_mvn_update(const psvi_plan& p, const float* eps, const float* 
             } else if (b.stamps && a.S == 128 && b.adam.kind == PSVI_ADAM_HIGHER)
                 hipLaunchKernelGGL((mvn_stream_kernel<4, PSVI_ADAM_HIGHER, true>), sg, block, 0, st, b);
             else
-                launch_stream(a.S / 32, b.adam.kind, sg, block, st, b, padded);
-            FwdArgs f{};
-            f.params = params;
-            f.eps = eps_next;
-            f.ldx = p.rows_tot[p.rank];
-            f.S = p.d.S;
-            fill_layers(p, f.lay);
-            constexpr int spb = kRedSpb;
-            hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_sfrb, (f.S + spb - 1) / spb),
-                               dim3(256), 0, st, p.d_sfrb, p.d_str_part, f, x_next);
-            return hipGetLastError();
+                launch_stream(b.adam.kind, sg, block, st, b, r.padded);
+            return launch_next_reduce(p, r, p.d_sfrb, p.n_sfrb, p.d_str_part, st);
         }
-        if (eps_next) {
-            a.eps_next = eps_next;
+        if (r.next.eps) {
+            a.eps_next = r.next.eps;
             a.part = p.d_upd_part;
             if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<false, 1, true, true>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((mvn_update_kernel<false, 0, true, true>), grid, block, 0, st, a);
-            FwdArgs f{};
-            f.params = params;
-            f.eps = eps_next;
-            f.ldx = p.rows_tot[p.rank];
-            f.S = p.d.S;
-            fill_layers(p, f.lay);
-            constexpr int spb = kRedSpb;
-            hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_ufrb, (f.S + spb - 1) / spb),
-                               dim3(256), 0, st, p.d_ufrb, p.d_upd_part, f, x_next);
-        } else if (packed_out) {
+            return launch_next_reduce(p, r, p.d_ufrb, p.n_ufrb, p.d_upd_part, st);
+        } else if (r.packed_out) {
             if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<false, 1, false, true, true>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((mvn_update_kernel<false, 0, false, true, true>), grid, block, 0, st, a);
         } else {
@@ -3408,74 +3386,50 @@ hipError_t launch_mvn_update(const psvi_plan& p, const float* eps, const float* 
         return hipGetLastError();
     }
     // gradient mode (the HVP's J^T G_dot) at any S on the bf16-piece K-split kernel
-    const bool ks_grad = grad_out && mvn_grad_takes_slots(p);
-    if (g_shard2 && !ks_grad) return hipErrorInvalidValue;
-    if ((mode == 2 && !grad_out && p.n_kwg > 0 && g_ks_off != 1) || ks_grad) {
+    const bool ks_grad = r.grad_out && mvn_grad_takes_slots(p);
+    if (r.g_shard2 && !ks_grad) return hipErrorInvalidValue;
+    if ((mode == 2 && !r.grad_out && p.n_kwg > 0 && g_ks_off != 1) || ks_grad) {
         // K = S > 128: the K-split streaming update (then the next step's
         // sample from the new parameters when asked)
         KsArgs k{};
+        fill_update(p, r, k);
         k.tiles = p.d_ks_tiles;
         k.segs = p.d_ks_segs;
         k.seg_off = p.d_ks_off;
         k.slots = p.d_ks_slots;
         k.cnt = p.d_ks_cnt;
         k.slot_bytes = (int64_t)sizeof(float) * std::max(1, p.n_ks_slots) * kKsSlotFloats;
-        k.eps = eps;
-        k.g = g_shard;
-        k.ldg = a.ldg;
-        k.S = a.S;
-        k.g_total = a.g_total;
-        k.e_total = a.e_total;
-        k.params = params;
-        k.m = m;
-        k.v = v;
-        k.kl_out = kl_out;
         k.pcount = p.P;
-        k.include_kl = include_kl;
-        k.inv_s0sq = a.inv_s0sq;
-        k.log_s0 = a.log_s0;
-        k.adam = a.adam;
-        k.stamps = g_upd_stamps;
-        k.grad_out = grad_out;
-        k.kl_vec = kl_vec;
-        k.g2 = g_shard2;
-        fill_layers(p, k.lay);
+        k.grad_out = r.grad_out;
+        k.kl_vec = r.kl_vec;
+        k.g2 = r.g_shard2;
         if (ks_grad)
             hipLaunchKernelGGL((mvn_kstream_kernel<true, true>), dim3(p.n_kwg), block, 0, st, k);
         else if (g_ks_bf_off || k.stamps)
             hipLaunchKernelGGL(mvn_kstream_kernel<false>, dim3(p.n_kwg), block, 0, st, k);
         else
             hipLaunchKernelGGL(mvn_kstream_kernel<true>, dim3(p.n_kwg), block, 0, st, k);
-        if (eps_next) {
+        if (r.next.eps) {
             const hipError_t e = hipGetLastError();
-            return e != hipSuccess ? e : launch_mvn_fwd(p, eps_next, params, x_next, st);
+            return e != hipSuccess ? e : launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
         }
         return hipGetLastError();
     }
-    if (eps_next && !grad_out) {
+    if (r.next.eps && !r.grad_out) {
         if (!(p.fuse_sample && mode < 2)) {
             // no fusion for this plan: update, then sample from the new params
-            hipError_t e = launch_mvn_update(p, eps, g_shard, params, m, v, hp, kl_out, nullptr,
-                                             include_kl, nullptr, nullptr, st, nullptr);
-            return e != hipSuccess ? e : launch_mvn_fwd(p, eps_next, params, x_next, st);
+            MvnUpdate plain = r;
+            plain.next = MvnUpdate::Next{};
+            const hipError_t e = launch_mvn_update(p, plain, st);
+            return e != hipSuccess ? e : launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
         }
-        a.eps_next = eps_next;
+        a.eps_next = r.next.eps;
         a.part = p.d_upd_part;
         if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<false, 1, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((mvn_update_kernel<false, 0, true>), grid, block, 0, st, a);
-        // x_next = mean' + softplus(sd') eps_next + sum of the band's chunk slots
-        FwdArgs f{};
-        f.params = params;
-        f.eps = eps_next;
-        f.ldx = p.rows_tot[p.rank];
-        f.S = p.d.S;
-        fill_layers(p, f.lay);
-        constexpr int spb = kRedSpb;
-        hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_ufrb, (f.S + spb - 1) / spb), dim3(256),
-                           0, st, p.d_ufrb, p.d_upd_part, f, x_next);
-        return hipGetLastError();
+        return launch_next_reduce(p, r, p.d_ufrb, p.n_ufrb, p.d_upd_part, st);
     }
-    if (grad_out) {
+    if (r.grad_out) {
         if (mode == 2) hipLaunchKernelGGL((mvn_update_kernel<true, 2>), grid, block, 0, st, a);
         else if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<true, 1>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((mvn_update_kernel<true, 0>), grid, block, 0, st, a);

@@ -1472,33 +1472,68 @@ uint16_t* g_net_draw_planes = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_NET_DRAW_
 int g_net_draw_role1 = 17;  // psvi_debug_set(PSVI_DBG_NET_DRAW_ROLE1, n): role 1's 32nds of the fused draw
 int g_net_draw_spare_off = 0;  // psvi_debug_set(PSVI_DBG_NET_DRAW_SPARE_OFF, 1): the whole draw at the end (A/B)
 
+// Every net_kernel instantiation, once.  Mean-field plans take the Gaussian
+// or the categorical head; full-cov plans are keyed by (several source ranks,
+// float4 x loads, pseudopoint chunks looped in the workgroup, fixed fn2
+// geometry), and the fn2 geometry comes only with float4 loads (NetGeo 1 for
+// one source, 2 for several) and the chunk loop only with float4 loads.
+struct NetVariant {
+    int family, lik;
+    bool multi, vec, loop, fn2;
+    void (*kernel)(NetArgs);
+};
+static const NetVariant kNetVariants[] = {
+    {PSVI_FAMILY_MEANFIELD, PSVI_LIK_CATEGORICAL, false, false, false, false,
+     net_kernel<PSVI_FAMILY_MEANFIELD, false>},
+    {PSVI_FAMILY_MEANFIELD, PSVI_LIK_GAUSSIAN, false, false, false, false,
+     net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_GAUSSIAN>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, false, false, false, false,
+     net_kernel<PSVI_FAMILY_FULLCOV, false>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, true, false, false, false,
+     net_kernel<PSVI_FAMILY_FULLCOV, true>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, false, true, false, false,
+     net_kernel<PSVI_FAMILY_FULLCOV, false, true>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, true, true, false, false,
+     net_kernel<PSVI_FAMILY_FULLCOV, true, true>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, false, true, true, false,
+     net_kernel<PSVI_FAMILY_FULLCOV, false, true, true>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, true, true, true, false,
+     net_kernel<PSVI_FAMILY_FULLCOV, true, true, true>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, false, true, false, true,
+     net_kernel<PSVI_FAMILY_FULLCOV, false, true, false, 1>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, true, true, false, true,
+     net_kernel<PSVI_FAMILY_FULLCOV, true, true, false, 2>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, false, true, true, true,
+     net_kernel<PSVI_FAMILY_FULLCOV, false, true, true, 1>},
+    {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, true, true, true, true,
+     net_kernel<PSVI_FAMILY_FULLCOV, true, true, true, 2>},
+};
+
+// The variant a launch takes, in this order of precedence: the Gaussian
+// mean-field kernel, the mean-field kernel (neither reads the other keys),
+// then for full-cov plans fn2 x loop x world > 1, loop x world > 1 and
+// vec x world > 1 (fn2 and loop hold only where float4 loads do).
+static const NetVariant* net_variant(int family, int lik, bool multi, bool vec, bool loop, bool fn2) {
+    if (family == PSVI_FAMILY_MEANFIELD) {
+        multi = vec = loop = fn2 = false;
+        if (lik != PSVI_LIK_GAUSSIAN) lik = PSVI_LIK_CATEGORICAL;
+    } else {
+        family = PSVI_FAMILY_FULLCOV;
+        lik = PSVI_LIK_CATEGORICAL;
+        vec = vec || loop || fn2;
+    }
+    for (const NetVariant& v : kNetVariants)
+        if (v.family == family && v.lik == lik && v.multi == multi && v.vec == vec &&
+            v.loop == loop && v.fn2 == fn2)
+            return &v;
+    return nullptr;
+}
+
 void net_set_lds_limit() {
     // gfx950: up to 160 KiB of LDS per workgroup
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_MEANFIELD, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(
-        (const void*)net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_GAUSSIAN>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, true, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, false, true, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, true, true, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, false, true, false, 1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, true, true, false, 2>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, false, true, true, 1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)net_kernel<PSVI_FAMILY_FULLCOV, true, true, true, 2>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const NetVariant& v : kNetVariants)
+        (void)hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024);
 }
 
 // The fixed fn2 geometry (NetGeo<1 / 2>) applies: the 64 -> 40 -> 40 -> 2
@@ -1521,20 +1556,18 @@ static bool net_vec_ok(const psvi_plan& p) {
     return true;
 }
 
-hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
-                      const float* params, const float* eps, float* mf_slots,
-                      const float* xrecv, float* gsend, double* nll_out, hipStream_t st,
-                      float* rn_out, int64_t rn_n, uint64_t rn_seed, uint64_t rn_off,
-                      const NetOuter* outer, uint16_t* rn_planes, int s_begin, int s_count,
-                      int rn_part, int rn_nparts) {
+hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
     NetArgs a{};
     const int S_loc = p.s_cnt[p.rank];
-    if (s_count < 0) s_count = S_loc - s_begin;
-    if (s_begin < 0 || s_count < 0 || s_begin + s_count > S_loc || rn_nparts < 1 || rn_part < 0 ||
-        rn_part >= rn_nparts)
+    const NetLaunch::Draw& d = r.draw;
+    const NetOuter* outer = r.outer;
+    const int s_begin = r.s_begin, s_count = r.s_count < 0 ? S_loc - s_begin : r.s_count;
+    if (s_begin < 0 || s_count < 0 || s_begin + s_count > S_loc || d.nparts < 1 || d.part < 0 ||
+        d.part >= d.nparts)
         return hipErrorInvalidValue;
     a.s_begin = s_begin;
-    if (!rn_planes && g_net_draw_planes && rn_out && p.family == PSVI_FAMILY_FULLCOV)
+    uint16_t* rn_planes = d.planes;
+    if (!rn_planes && g_net_draw_planes && d.out && p.family == PSVI_FAMILY_FULLCOV)
         rn_planes = g_net_draw_planes;  // diagnostics: the planes of a draw that asked for none
     if (outer) {
         a.outer = outer->mode;
@@ -1555,10 +1588,10 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
         return hipErrorInvalidValue;
     }
     a.inv_s0sq = 1.f / (p.d.prior_sd * p.d.prior_sd);
-    a.rn_out = rn_out;  // 16-byte aligned (workspace buffers)
-    a.rn_n = rn_n;
-    a.rn_seed = rn_seed;
-    a.rn_off = rn_off;
+    a.rn_out = d.out;  // 16-byte aligned (workspace buffers)
+    a.rn_n = d.n;
+    a.rn_seed = d.seed;
+    a.rn_off = d.offset;
     a.rn_P = p.d_eps_planes;
     a.rn_planes = rn_planes && p.d_eps_planes ? rn_planes : nullptr;
     if (rn_planes && !p.d_eps_planes) return hipErrorInvalidValue;
@@ -1580,9 +1613,10 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
         a.eoff[l] = p.lay[l].eoff;
     }
     net_lds_floats(p, p.mc, &a);
-    a.u = u; a.z = z; a.w = w; a.nll_out = nll_out;
-    a.params = params; a.eps = eps; a.mf_slots = mf_slots; a.slot_ld = p.n_tot;
-    a.xrecv = xrecv; a.gsend = gsend;
+    // the targets' 4-byte slots: labels, or fp32 values the Gaussian head reads as such
+    a.u = r.u; a.z = r.targets.slots(); a.w = r.w; a.nll_out = r.nll_out;
+    a.params = r.params; a.eps = r.eps; a.mf_slots = r.mf_slots; a.slot_ld = p.n_tot;
+    a.xrecv = r.xrecv; a.gsend = r.gsend;
     if (p.family == PSVI_FAMILY_FULLCOV) {
         const int S_local = p.s_cnt[p.rank];
         a.nsrc = p.world;
@@ -1620,18 +1654,21 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
     // (every rank passes the same global eps to its update): the draw on its
     // own (the whole of it when this is its only part)
     // this launch's part of the draw's quads
-    const int64_t nqa = rn_out && rn_n > 0 ? (rn_n + 3) / 4 : 0;
-    a.rn_q0 = nqa / rn_nparts * rn_part + nqa % rn_nparts * rn_part / rn_nparts;
-    a.rn_q1 = nqa / rn_nparts * (rn_part + 1) + nqa % rn_nparts * (rn_part + 1) / rn_nparts;
+    const int64_t nqa = d.out && d.n > 0 ? (d.n + 3) / 4 : 0;
+    a.rn_q0 = nqa / d.nparts * d.part + nqa % d.nparts * d.part / d.nparts;
+    a.rn_q1 = nqa / d.nparts * (d.part + 1) + nqa % d.nparts * (d.part + 1) / d.nparts;
     if (s_count == 0) {
         if (a.rn_q1 <= a.rn_q0) return hipSuccess;
-        return launch_randn(rn_out, rn_n, rn_seed, rn_off, st, nullptr, 0,
-                            rn_planes ? &p.eps_planes : nullptr, rn_planes, a.rn_q0, a.rn_q1);
+        RandnLaunch rn;
+        rn.out = d.out; rn.n = d.n; rn.seed = d.seed; rn.offset = d.offset;
+        rn.planes_desc = rn_planes ? &p.eps_planes : nullptr; rn.planes = rn_planes;
+        rn.q_lo = a.rn_q0; rn.q_hi = a.rn_q1;
+        return launch_randn(rn, st);
     }
     // per-chunk slots are summed over all the rank's samples: whole launches only
     if (a.gslot && a.outer != 1 && (s_begin != 0 || s_count != S_loc)) return hipErrorInvalidValue;
     // (the fixed geometry places the draw's planes with 32-bit indices)
-    const bool fn2 = net_vec_ok(p) && net_fn2_geo(p) && rn_n < (int64_t(1) << 31);
+    const bool fn2 = net_vec_ok(p) && net_fn2_geo(p) && d.n < (int64_t(1) << 31);
     if (fn2 && p.world > 1 && a.nbands != kFn2Bands) return hipErrorInvalidValue;
     if (fn2 && a.rn_planes) {  // Fn2PlaneMap is the plan's EpsPlanes
         const EpsPlanes& E = p.eps_planes;
@@ -1658,35 +1695,12 @@ hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, cons
         a.rn_rem0 = (int)(c0 % nper);
         a.rn_spare = g_net_draw_spare_off ? 0 : 1;
     }
-    if (p.family == PSVI_FAMILY_MEANFIELD && p.lik == PSVI_LIK_GAUSSIAN)
-        hipLaunchKernelGGL(
-            (net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_GAUSSIAN>), grid,
-            block, p.net_lds, st, a);
-    else if (p.family == PSVI_FAMILY_MEANFIELD)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_MEANFIELD, false>), grid, block, p.net_lds, st, a);
-    else if (fn2 && loop && p.world > 1)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, true, true, true, 2>), grid, block, p.net_lds, st, a);
-    else if (fn2 && loop)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, false, true, true, 1>), grid, block, p.net_lds, st, a);
-    else if (fn2 && p.world > 1)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, true, true, false, 2>), grid, block, p.net_lds, st, a);
-    else if (fn2)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, false, true, false, 1>), grid, block, p.net_lds, st, a);
-    else if (loop && p.world > 1)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, true, true, true>), grid, block, p.net_lds, st, a);
-    else if (loop)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, false, true, true>), grid, block, p.net_lds, st, a);
-    else if (p.world > 1 && net_vec_ok(p))
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, true, true>), grid, block, p.net_lds, st, a);
-    else if (p.world > 1)
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, true>), grid, block, p.net_lds, st, a);
-    else if (net_vec_ok(p))
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, false, true>), grid, block, p.net_lds, st, a);
-    else
-        hipLaunchKernelGGL((net_kernel<PSVI_FAMILY_FULLCOV, false>), grid, block, p.net_lds, st, a);
+    const NetVariant* nv = net_variant(p.family, p.lik, p.world > 1, net_vec_ok(p), loop, fn2);
+    if (!nv) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nv->kernel, grid, block, p.net_lds, st, a);
     if (a.gslot && a.outer != 1) {
         hipLaunchKernelGGL(net_slot_sum_kernel, dim3((unsigned)((a.gsz + 255) / 256)), dim3(256), 0,
-                           st, (const float*)a.gslot, p.mchunks, a.gsz, gsend);
+                           st, (const float*)a.gslot, p.mchunks, a.gsz, r.gsend);
     }
     return hipGetLastError();
 }

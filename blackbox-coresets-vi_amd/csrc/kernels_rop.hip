@@ -1256,11 +1256,8 @@ static void rop_fill(const psvi_plan& p, RopArgs& a) {
     }
 }
 
-hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
-                          const float* x, const float* xd, const float* params, const float* vec,
-                          const float* eps, float* G, float* Gd, float* du, float* nlld,
-                          hipStream_t st, bool sum_slots, float* dzd) {
-    if (dzd && p.lik != PSVI_LIK_GAUSSIAN) return hipErrorInvalidValue;
+hipError_t launch_net_rop(const psvi_plan& p, const NetRop& r, hipStream_t st) {
+    if (r.dzd && p.lik != PSVI_LIK_GAUSSIAN) return hipErrorInvalidValue;
     static bool once = [] {
         (void)hipFuncSetAttribute((const void*)net_rop_kernel,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRopLds);
@@ -1273,6 +1270,11 @@ hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, 
     RopArgs a{};
     rop_fill(p, a);
     a.nsplit = rop_splits(p);
+    // the targets' 4-byte slots: labels, or fp32 values the Gaussian head reads as such
+    a.u = r.u; a.z = r.targets.slots(); a.w = r.w; a.x = r.x; a.xd = r.xd;
+    a.params = r.params; a.vec = r.vec; a.eps = r.eps;
+    a.G = r.G; a.Gd = r.Gd; a.du = r.du; a.nlld = r.nlld; a.dzd = r.dzd;
+    a.stamps = g_rop_stamps;
     {
         // the matrix-core form when a row block fits the LDS in one pass
         // rows padded to a 16-multiple: the rows past a block's own are zero
@@ -1280,10 +1282,6 @@ hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, 
         const int rows = (((p.d.M + a.nsplit - 1) / a.nsplit) + 15) & ~15;
         const size_t lds = rop_mfma_carve(p, rows, &a) * 4;
         if (g_rop_valu != 1 && lds <= kRopLds) {
-            a.u = u; a.z = z; a.w = w; a.x = x; a.xd = xd;
-            a.params = params; a.vec = vec; a.eps = eps;
-            a.G = G; a.Gd = Gd; a.du = du; a.nlld = nlld; a.dzd = dzd;
-            a.stamps = g_rop_stamps;
             a.single = 1;
             const dim3 grid(p.d.S, a.nsplit), block(512);
             const bool fc = p.family == PSVI_FAMILY_FULLCOV;
@@ -1291,10 +1289,10 @@ hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, 
                 hipLaunchKernelGGL((net_rop_mfma_kernel<true>), grid, block, lds, st, a);
             else
                 hipLaunchKernelGGL((net_rop_mfma_kernel<false>), grid, block, lds, st, a);
-            if (a.nsplit > 1 && sum_slots) {
+            if (a.nsplit > 1 && r.sum_slots) {
                 const int64_t n = (int64_t)p.d.S * p.n_tot;
                 hipLaunchKernelGGL(slot_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                                   G, Gd, n, a.nsplit);
+                                   r.G, r.Gd, n, a.nsplit);
             }
             return hipGetLastError();
         }
@@ -1308,34 +1306,30 @@ hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, 
     if (rc == 0) return hipErrorInvalidValue;
     const size_t lds = rop_carve(p, rc, &a, !single) * 4;
     a.single = single ? 1 : 0;
-    a.u = u; a.z = z; a.w = w; a.x = x; a.xd = xd;
-    a.params = params; a.vec = vec; a.eps = eps;
-    a.G = G; a.Gd = Gd; a.du = du; a.nlld = nlld; a.dzd = dzd;
-    a.stamps = g_rop_stamps;
     hipLaunchKernelGGL(net_rop_kernel, dim3(p.d.S, a.nsplit), dim3(512), lds, st, a);
-    if (a.nsplit > 1 && sum_slots) {
+    if (a.nsplit > 1 && r.sum_slots) {
         const int64_t n = (int64_t)p.d.S * p.n_tot;
-        hipLaunchKernelGGL(slot_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, G,
-                           Gd, n, a.nsplit);
+        hipLaunchKernelGGL(slot_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r.G,
+                           r.Gd, n, a.nsplit);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_hvp_assemble(const psvi_plan& p, const float* params, const float* vec,
-                               const float* eps, const float* G, const float* Gd, const float* du,
-                               const float* nlld, float* hv, float* d_u, float* d_w,
-                               hipStream_t st, bool include_kl, int64_t slot2) {
+hipError_t launch_hvp_assemble(const psvi_plan& p, const HvpAssemble& r, hipStream_t st) {
     RopArgs a{};
     rop_fill(p, a);
-    a.params = params; a.vec = vec; a.eps = eps;
-    a.G = const_cast<float*>(G);
-    a.Gd = const_cast<float*>(Gd);
+    a.params = r.params; a.vec = r.vec; a.eps = r.eps;
+    a.G = const_cast<float*>(r.G);
+    a.Gd = const_cast<float*>(r.Gd);
+    const float *du = r.du, *nlld = r.nlld;
+    float *hv = r.hv, *d_u = r.d_u, *d_w = r.d_w;
+    const int64_t slot2 = r.slot2;
     const float s0 = p.d.prior_sd;
     const int nbp = (int)((p.n_tot + 63) / 64), M = p.d.M, D = p.lay[0].din;
     const int64_t ndu = (int64_t)M * D;
     const int nbu = d_u ? (int)((ndu + 63) / 64) : 0, nbw = d_w ? (M + 63) / 64 : 0;
     const dim3 pg((unsigned)(nbp + nbu + nbw)), pb(64 * kAsmWaves);
-    const float is2 = 1.f / (s0 * s0), klw = include_kl ? 1.f : 0.f;
+    const float is2 = 1.f / (s0 * s0), klw = r.include_kl ? 1.f : 0.f;
     const bool fc = p.family == PSVI_FAMILY_FULLCOV;
     if (slot2 && fc)
         hipLaunchKernelGGL((hvp_assemble_kernel<true, true>), pg, pb, 0, st, a, hv, is2, klw, slot2, nbp, du, ndu, d_u, nbu, nlld, d_w);

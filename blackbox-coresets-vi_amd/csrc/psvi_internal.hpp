@@ -596,20 +596,62 @@ inline unsigned plan_nkl_mask(const psvi_plan& p) {
 }
 // the full-cov network kernel's x map and band table (kernels_net.hip)
 void net_xmap(const psvi_plan& p, std::vector<uint32_t>& xmap, std::vector<NetBand>& bands);
-// launchers (defined in the .hip translation units)
-hipError_t launch_net(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
-                      const float* params, const float* eps, float* mf_slots,
-                      const float* xrecv, float* gsend, double* nll_out, hipStream_t st,
-                      float* rn_out = nullptr, int64_t rn_n = 0, uint64_t rn_seed = 0,
-                      uint64_t rn_off = 0, const NetOuter* outer = nullptr,
-                      uint16_t* rn_planes = nullptr, int s_begin = 0, int s_count = -1,
-                      int rn_part = 0, int rn_nparts = 1);
+// Per-row targets of the loss head: class labels (categorical plans) or fp32
+// values (Gaussian plans), one 4-byte slot per row either way.
+struct Targets {
+    const void* p = nullptr;
+    static Targets labels(const int32_t* z) { return Targets{z}; }
+    static Targets values(const float* y) { return Targets{y}; }
+    // the slots as the kernels' argument structs declare them (`const int32_t*
+    // z`; the Gaussian head reads the same slots as fp32): the one cast
+    const int32_t* slots() const { return static_cast<const int32_t*>(p); }
+};
+
+// launchers (defined in the .hip translation units).  Those with optional
+// inputs take a request struct: every optional field defaults to "absent", a
+// caller assigns the fields it means.
+struct NetLaunch {
+    // rows
+    const float* u = nullptr;
+    Targets targets;
+    const float* w = nullptr;
+    // mean-field inputs (mf_slots: the plan's gradient slots)
+    const float* params = nullptr;
+    const float* eps = nullptr;
+    float* mf_slots = nullptr;
+    // full-cov inputs
+    const float* xrecv = nullptr;
+    float* gsend = nullptr;
+    double* nll_out = nullptr;
+    // fused draw of the next step's eps: normals [0, n) of the Philox stream
+    // (seed, offset) into out (and their bf16 planes), this launch drawing
+    // part `part` of `nparts` of its quads
+    struct Draw {
+        float* out = nullptr;
+        int64_t n = 0;
+        uint64_t seed = 0, offset = 0;
+        uint16_t* planes = nullptr;
+        int part = 0, nparts = 1;
+    } draw;
+    // the rank's local samples [s_begin, s_begin + s_count) (-1: to the last)
+    int s_begin = 0, s_count = -1;
+    const NetOuter* outer = nullptr;
+};
+hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st);
 // acc == nullptr: the accumulators come from the plan's mean-field gradient
 // slots, reduced in a fixed order against slot_eps (the step's eps)
-hipError_t launch_mf_update(const psvi_plan& p, const float* acc, float* params,
-                            float* m, float* v, const psvi_adam_hp* hp, double* kl_out,
-                            float* grad_out, int include_kl, hipStream_t st,
-                            const float* slot_eps = nullptr);
+struct MfUpdate {
+    const float* acc = nullptr;
+    const float* slot_eps = nullptr;
+    float* params = nullptr;
+    float* m = nullptr;
+    float* v = nullptr;
+    const psvi_adam_hp* hp = nullptr;
+    double* kl_out = nullptr;
+    float* grad_out = nullptr;  // gradient mode: no Adam step
+    int include_kl = 0;
+};
+hipError_t launch_mf_update(const psvi_plan& p, const MfUpdate& r, hipStream_t st);
 // acc = [sum_s dW_s | sum_s dW_s eps_s] from the plan's mean-field gradient slots
 hipError_t launch_mf_slot_acc(const psvi_plan& p, const float* eps, float* acc, hipStream_t st);
 // diag_of (HVP tangent sample): params is the direction, the diagonal
@@ -619,15 +661,30 @@ hipError_t launch_mvn_fwd(const psvi_plan& p, const float* eps, const float* par
 hipError_t launch_mvn_fwd_pair(const psvi_plan& p, const float* eps, const float* params,
                                float* x, const float* vec, float* x2, float* part2,
                                hipStream_t st);
-hipError_t launch_mvn_update(const psvi_plan& p, const float* eps, const float* g_shard,
-                             float* params, float* m, float* v, const psvi_adam_hp* hp,
-                             double* kl_out, float* grad_out, int include_kl,
-                             const float* eps_next, float* x_next, hipStream_t st,
-                             float* tstate = nullptr, bool packed_out = false,
-                             const float* kl_vec = nullptr, bool padded = false,
-                             const uint16_t* eps_planes = nullptr,
-                             const uint16_t* eps_next_planes = nullptr,
-                             const float* g_shard2 = nullptr);
+struct MvnUpdate {
+    const float* eps = nullptr;
+    const float* g_shard = nullptr;
+    const float* g_shard2 = nullptr;  // see mvn_grad_takes_slots
+    float* params = nullptr;
+    float* m = nullptr;
+    float* v = nullptr;
+    const psvi_adam_hp* hp = nullptr;
+    double* kl_out = nullptr;
+    float* grad_out = nullptr;  // gradient mode: no Adam step
+    int include_kl = 0;
+    const float* kl_vec = nullptr;  // gradient mode: + kl_vec / s0^2 on the corr entries
+    // the next step's sample x from the updated parameters (planes: eps as bf16 planes)
+    struct Next {
+        const float* eps = nullptr;
+        float* x = nullptr;
+        const uint16_t* planes = nullptr;
+    } next;
+    float* tstate = nullptr;  // tiled corr / m / v (psvi_inner_loop on a fusable plan)
+    bool packed_out = false;  // tiled state: write corr / m / v back to the packed arrays
+    bool padded = false;      // eps, next.eps and g_shard end in 64 zeroed floats
+    const uint16_t* eps_planes = nullptr;
+};
+hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t st);
 // the gradient-mode update takes a second G slot (g_shard2: added to g_shard at
 // staging, the R-op's row-block slots unsummed) when this holds
 bool mvn_grad_takes_slots(const psvi_plan& p);
@@ -635,10 +692,17 @@ bool mvn_grad_takes_slots(const psvi_plan& p);
 hipError_t launch_mvn_tile_convert(const psvi_plan& p, float* params, float* m, float* v,
                                    float* tstate, bool to_tiled, hipStream_t st,
                                    float* const* pads = nullptr);
-hipError_t launch_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t st,
-                        double* zero = nullptr, int64_t nzero = 0,
-                        const EpsPlanes* planes_desc = nullptr, uint16_t* planes = nullptr,
-                        int64_t q_lo = 0, int64_t q_hi = -1);  // quads [q_lo, q_hi) only (-1: all)
+struct RandnLaunch {
+    float* out = nullptr;
+    int64_t n = 0;
+    uint64_t seed = 0, offset = 0;
+    double* zero = nullptr;  // the same launch also clears zero[0, nzero)
+    int64_t nzero = 0;
+    const EpsPlanes* planes_desc = nullptr;  // with planes: the draw also as bf16 planes
+    uint16_t* planes = nullptr;
+    int64_t q_lo = 0, q_hi = -1;  // quads [q_lo, q_hi) only (-1: all)
+};
+hipError_t launch_randn(const RandnLaunch& r, hipStream_t st);
 hipError_t launch_adam(int64_t n, float* p, const float* g, float* m, float* v,
                        const psvi_adam_hp* hp, hipStream_t st);
 AdamC make_adam(const psvi_adam_hp* hp);
@@ -717,12 +781,36 @@ hipError_t launch_cg_update(int64_t n, double* x, double* p, float* p32, const d
 // Hessian-vector products (kernels_rop.hip)
 int rop_rows(const psvi_plan& p);
 int rop_splits(const psvi_plan& p);  // row blocks per sample: G / G_dot slots
-hipError_t launch_net_rop(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
-                          const float* x, const float* xd, const float* params, const float* vec,
-                          const float* eps, float* G, float* Gd, float* du, float* nlld,
-                          hipStream_t st, bool sum_slots = true, float* dzd = nullptr);
-hipError_t launch_hvp_assemble(const psvi_plan& p, const float* params, const float* vec,
-                               const float* eps, const float* G, const float* Gd, const float* du,
-                               const float* nlld, float* hv, float* d_u, float* d_w,
-                               hipStream_t st, bool include_kl = true, int64_t slot2 = 0);
+struct NetRop {
+    const float* u = nullptr;
+    Targets targets;
+    const float* w = nullptr;
+    const float* x = nullptr;   // full-cov: the sample and its tangent
+    const float* xd = nullptr;
+    const float* params = nullptr;
+    const float* vec = nullptr;
+    const float* eps = nullptr;
+    float* G = nullptr;
+    float* Gd = nullptr;
+    float* du = nullptr;        // nullable
+    float* nlld = nullptr;      // nullable
+    float* dzd = nullptr;       // nullable, Gaussian plans
+    bool sum_slots = true;      // add the row blocks' G / G_dot slots into the first
+};
+hipError_t launch_net_rop(const psvi_plan& p, const NetRop& r, hipStream_t st);
+struct HvpAssemble {
+    const float* params = nullptr;
+    const float* vec = nullptr;
+    const float* eps = nullptr;
+    const float* G = nullptr;
+    const float* Gd = nullptr;
+    const float* du = nullptr;
+    const float* nlld = nullptr;
+    float* hv = nullptr;
+    float* d_u = nullptr;  // nullable
+    float* d_w = nullptr;  // nullable
+    bool include_kl = true;
+    int64_t slot2 = 0;  // offset of the second G / G_dot slot (0: summed already)
+};
+hipError_t launch_hvp_assemble(const psvi_plan& p, const HvpAssemble& r, hipStream_t st);
 }  // namespace psvi

@@ -166,6 +166,40 @@ def test_plan_create_lik_geometry_and_default():
     assert counts[0] == counts[1] == counts[2]
 
 
+def test_targets_kind_refusals_at_the_abi():
+    """psvi_outer_elbo_grad_ex (with grad_z), psvi_evaluate and
+    psvi_evaluate_regression take their targets through the same `z` slot; a
+    plan of the wrong likelihood is refused with PSVI_ESTATE before anything
+    is launched.  A plan created without a HIP device is refused one check
+    earlier, with PSVI_ESTATE too, whatever its kind."""
+    from psvi.runtime import _lib
+
+    dims, S, M = [3, 10, 1], 3, 5
+    have_dev = torch.cuda.is_available()
+    no_dev = b"plan was created without a HIP device"
+    buf = (ctypes.c_float * (S * 64))()   # never read: every call is refused first
+    b = ctypes.addressof(buf)
+    for lik in (None, _lib.Likelihood(_lib.LIK_GAUSSIAN, 4.0)):
+        rc, _, h, lib = _create(_lib.FAMILY_MEANFIELD, dims, S, M, 1, lik)
+        assert rc == 0 and h.value
+        gauss = lik is not None
+        outer = lambda: lib.psvi_outer_elbo_grad_ex(h, 2, b, b, b, b, b, b, b, None, None, b, None,
+                                                    None, 0, None)
+        evalr = lambda: lib.psvi_evaluate_regression(h, 2, b, b, b, b, b, 0, 0.0, 1.0, None, b,
+                                                     None, 0, None)
+        evalc = lambda: lib.psvi_evaluate(h, 2, b, b, b, b, b, 0, None, b, None, 0, None)
+        if not have_dev:
+            calls = [(outer, no_dev), (evalr, no_dev), (evalc, no_dev)]
+        elif gauss:   # the right kind for outer / evalr: not called (they would go on)
+            calls = [(evalc, b"psvi_evaluate_regression")]
+        else:
+            calls = [(outer, b"grad_z needs a Gaussian-likelihood plan"),
+                     (evalr, b"needs a Gaussian-likelihood plan")]
+        for call, text in calls:
+            assert call() == -4 and text in lib.psvi_last_error(), (gauss, text)
+        lib.psvi_plan_destroy(h)
+
+
 def test_engine_likelihood_keyword():
     from psvi.runtime import InnerLoopPlan
 
