@@ -2,7 +2,8 @@
 //
 // Plans hold the immutable geometry of one (family, layer sizes, S, M, world,
 // rank) configuration: sample shards, nnz-balanced row shards of every
-// full-cov layer, and the device work lists of the packed-triangular kernels.
+// full-cov layer, and the device work lists of the packed-triangular kernels
+// (built on the host by plan_tables.cpp; uploaded and owned here).
 // Steps are pure stream-ordered kernel launches + hipMemsetAsync (graph
 // capturable: no allocation, no synchronisation).
 #include <algorithm>
@@ -17,7 +18,6 @@
 #include "psvi_internal.hpp"
 
 namespace psvi {
-size_t net_plan_geometry(psvi_plan& p);  // kernels_net.hip
 void net_set_lds_limit();                // kernels_net.hip
 extern int g_net_ablation;               // kernels_net.hip
 extern int g_net_scalar_loads;           // kernels_net.hip
@@ -35,7 +35,6 @@ extern int g_fwd_pair_bf;                  // kernels_mvn.hip
 extern int g_stream_fold_off;              // kernels_mvn.hip
 extern int g_fs_bf_off;                  // kernels_mvn.hip
 extern int g_ks_bf_off;                  // kernels_mvn.hip
-static int g_ks_wgs = 0;                 // psvi_debug_set(PSVI_DBG_KSTREAM_WGS): plan creation
 extern int g_lenet_abl;                  // kernels_lenet.hip
 extern int g_net_split_below;            // kernels_net.hip
 extern int g_net_threads;                // kernels_net.hip
@@ -54,10 +53,6 @@ using namespace psvi;
 namespace {
 
 thread_local std::string g_err;
-int g_stream_wgs = 0;       // psvi_debug_set(PSVI_DBG_STREAM_WGS, n): streaming-update workgroups (0 = 256)
-int g_stream_rr = 0;        // psvi_debug_set(PSVI_DBG_STREAM_RR, 1): runs dealt round-robin over XCDs (A/B)
-int g_stream_cost = -1;     // psvi_debug_set(PSVI_DBG_STREAM_COST, first% + 1000 diag%): tile cost weights (tuning)
-int g_upd_chunk_tiles = 0;  // psvi_debug_set(PSVI_DBG_UPD_CHUNK, n): c-blocks per update chunk (0 = auto)
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
@@ -75,80 +70,11 @@ int hip_fail(hipError_t e, const char* where) {
         if (e_ != hipSuccess) return hip_fail(e_, #expr);  \
     } while (0)
 
-constexpr int kFwdKChunk = 256;  // columns of L per forward work item
-constexpr int64_t kLenetRowFloats = 2 * 1176 + 400 * 2 + 120 * 2 + 84 * 2 + 10;  // per (s, m): P1, routed d P1, ...
-
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// Row shards.  World > 1 full-cov: whole 64-row bands, so that every rank's
-// update and sample work is whole 64 x 64 tiles of L (a band split between
-// two ranks would be computed by both).  Band b of a layer holds b + 1 tiles
-// (its strict-lower triangle); the bands of all layers are dealt largest
-// first to the least-loaded rank (ties: the lower rank), which balances the
-// tile counts to within one small band (C4 at 8 ranks: 151..153 of 1,215
-// tiles; a contiguous nnz split would make a rank compute up to 216 tiles
-// because its partial edge bands count whole).  A rank's rows are the union
-// of its bands -- runs of consecutive bands -- and its x-shard columns run
-// layer-major in row order.  World 1 (and the replicated mean-field / LeNet
-// rows): one run per layer.
-void assign_rows(psvi_plan& p) {
-    for (int q = 0; q < p.world; ++q) {
-        p.rows_tot[q] = 0;
-        p.runs[q].clear();
-    }
-    p.band_owner.clear();
-    p.band_coloff.clear();
-    int nbt = 0;
-    for (int l = 0; l < p.L; ++l) {
-        p.band_base[l] = nbt;
-        nbt += (p.lay[l].n - 1) / 64 + 1;
-    }
-    p.band_base[p.L] = nbt;
-    const bool banded = p.family == PSVI_FAMILY_FULLCOV && p.world > 1;
-    std::vector<int> owner(nbt, 0);
-    if (banded) {
-        std::vector<int> order(nbt);
-        std::vector<double> cost(nbt);
-        for (int l = 0; l < p.L; ++l)
-            for (int b = 0; b < p.band_base[l + 1] - p.band_base[l]; ++b)
-                cost[p.band_base[l] + b] = b + 1.0;
-        for (int i = 0; i < nbt; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-        std::vector<double> load(p.world, 0.0);
-        for (int i : order) {
-            const int q = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            owner[i] = q;
-            load[q] += cost[i];
-        }
-    }
-    p.band_coloff.assign(nbt, 0);
-    for (int q = 0; q < p.world; ++q)
-        for (int l = 0; l < p.L; ++l) {
-            const int n = p.lay[l].n;
-            p.xcol_l[q][l] = p.rows_tot[q];
-            for (int b = 0; 64 * b < n; ++b) {
-                const int gb = p.band_base[l] + b;
-                if (banded && owner[gb] != q) continue;
-                const int r0 = 64 * b, r1 = std::min(n, r0 + 64);
-                std::vector<ShardRun>& rv = p.runs[q];
-                if (!rv.empty() && rv.back().layer == l && rv.back().hi == r0)
-                    rv.back().hi = r1;
-                else
-                    rv.push_back(ShardRun{l, r0, r1, p.rows_tot[q]});
-                p.band_coloff[gb] = p.rows_tot[q] - r0;
-                p.rows_tot[q] += r1 - r0;
-            }
-        }
-    p.band_owner = owner;
-}
-
 template <class T>
-int upload(const std::vector<T>& v, T** dst) {
-    *dst = nullptr;
-    if (v.empty()) return 0;
-    HIP_TRY(hipMalloc((void**)dst, sizeof(T) * v.size()));
-    HIP_TRY(hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-    return 0;
+int upload(DevTable<T>& t) {
+    const char* what = "";
+    const hipError_t e = t.upload(&what);
+    return e == hipSuccess ? 0 : hip_fail(e, what);
 }
 
 int check_desc(const psvi_net_desc* d) {
@@ -163,442 +89,69 @@ int check_desc(const psvi_net_desc* d) {
     return 0;
 }
 
-// Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with
-// its own L2.  Keep every band's chunks on one XCD (its G slice and the eps
-// blocks it shares with neighbouring bands then stay in that L2): bands go
-// greedily, largest first, to the least-loaded XCD; each XCD's chunks run
-// largest first; the per-XCD queues are interleaved at stride 8 and padded
-// with empty chunks (k0 == k1, no work).
-static std::vector<UpdChunk> xcd_order(const std::vector<UpdChunk>& in) {
-    constexpr int kXcd = 8;
-    auto work = [](const UpdChunk& c) { return (c.k1 - c.k0) + c.diag; };
-    std::vector<std::vector<UpdChunk>> band;  // chunks of one (layer, r0)
-    for (const UpdChunk& c : in) {
-        if (band.empty() || band.back()[0].layer != c.layer || band.back()[0].r0 != c.r0)
-            band.emplace_back();
-        band.back().push_back(c);
-    }
-    std::vector<int> bw(band.size());
-    for (size_t i = 0; i < band.size(); ++i)
-        for (const UpdChunk& c : band[i]) bw[i] += work(c);
-    std::vector<size_t> idx(band.size());
-    for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return bw[a] > bw[b]; });
-    std::vector<std::vector<UpdChunk>> q(kXcd);
-    std::vector<long> load(kXcd, 0);
-    for (size_t i : idx) {
-        const int x = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        load[x] += bw[i];
-        q[x].insert(q[x].end(), band[i].begin(), band[i].end());
-    }
-    size_t len = 0;
-    for (auto& v : q) {
-        std::stable_sort(v.begin(), v.end(),
-                         [&](const UpdChunk& a, const UpdChunk& b) { return work(a) > work(b); });
-        len = std::max(len, v.size());
-    }
-    std::vector<UpdChunk> out;
-    out.reserve(len * kXcd);
-    const UpdChunk empty{0, 0, 0, 0, 0, 0, 0, 0, -1};
-    for (size_t j = 0; j < len; ++j)
-        for (int x = 0; x < kXcd; ++x) out.push_back(j < q[x].size() ? q[x][j] : empty);
-    return out;
-}
-
-// K-split streaming update tables (S > 128): the rank's tiles band-major
-// (the diagonal tile last in its band), units (tile, 128-sample pass) cut
-// into equal-cost contiguous runs -- a tile's last unit also carries its
-// Adam epilogue (about half a pass) -- one run per workgroup, two workgroups
-// per CU.  XCD-aware placement as the stream kernel: workgroup w runs on XCD
-// w % 8, so XCD x takes a contiguous eighth of the run list (its bands' G
-// slices and eps column blocks stay in that XCD's L2).
-void build_kstream(psvi_plan& p) {
-    const int r = p.rank, np = (p.d.S + kKsPass - 1) / kKsPass;
-    std::vector<KsTile>& tiles = p.h_ks_tiles;
-    tiles.clear();
-    for (const ShardRun& run : p.runs[r])
-        for (int b = run.lo / 64; 64 * b < run.hi; ++b)
-            for (int k = 0; k <= b; ++k)
-                tiles.push_back(KsTile{run.layer, 64 * b, k, k == b, 64 * b,
-                                       std::min(64 * b + 64, p.lay[run.layer].n), run.col - run.lo, -1});
-    const int T = (int)tiles.size();
-    p.h_ks_segs.clear();
-    p.h_ks_off.clear();
-    p.n_kwg = p.n_ks_slots = p.n_ks_cnt = 0;
-    if (T == 0) return;
-    const int64_t U = (int64_t)T * np;
-    int nwg = (int)std::min<int64_t>(U, g_ks_wgs > 0 ? g_ks_wgs : 512);
-    if (nwg >= 8) nwg -= nwg % 8;
-    // unit cost: 1 per pass, + 0.5 on a tile's last pass (its epilogue)
-    std::vector<double> cum(U + 1, 0.0);
-    for (int64_t u = 0; u < U; ++u) cum[u + 1] = cum[u] + 1.0 + (u % np == np - 1 ? 0.5 : 0.0);
-    std::vector<int64_t> cut(nwg + 1, 0);
-    cut[nwg] = U;
-    for (int w = 1; w < nwg; ++w) {
-        const double target = cum[U] * w / nwg;
-        int64_t t = (int64_t)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
-        cut[w] = std::max(cut[w - 1] + 1, std::min(t, U - (nwg - w)));
-    }
-    // contributors per tile
-    std::vector<int> ncon(T, 0);
-    for (int w = 0; w < nwg; ++w)
-        for (int64_t u = cut[w]; u < cut[w + 1];) {
-            const int t = (int)(u / np);
-            ++ncon[t];
-            u = std::min<int64_t>(cut[w + 1], (int64_t)(t + 1) * np);
-        }
-    std::vector<int> slot0(T, -1), seen(T, 0);
-    for (int t = 0; t < T; ++t)
-        if (ncon[t] > 1) {
-            slot0[t] = p.n_ks_slots;
-            p.n_ks_slots += ncon[t];
-            tiles[t].cnt = p.n_ks_cnt++;
-        }
-    std::vector<std::vector<KsSeg>> per(nwg);
-    for (int w = 0; w < nwg; ++w)
-        for (int64_t u = cut[w]; u < cut[w + 1];) {
-            const int t = (int)(u / np);
-            const int64_t ue = std::min<int64_t>(cut[w + 1], (int64_t)(t + 1) * np);
-            per[w].push_back(KsSeg{t, (int)(u - (int64_t)t * np), (int)(ue - (int64_t)t * np),
-                                   slot0[t], ncon[t], seen[t]++});
-            u = ue;
-        }
-    // XCD placement: workgroup w -> run (w % 8) * (nwg / 8) + w / 8
-    std::vector<int> run_of(nwg);
-    for (int w = 0; w < nwg; ++w)
-        run_of[w] = (nwg % 8 == 0) ? (w % 8) * (nwg / 8) + w / 8 : w;
-    p.h_ks_off.push_back(0);
-    for (int w = 0; w < nwg; ++w) {
-        const auto& v = per[run_of[w]];
-        p.h_ks_segs.insert(p.h_ks_segs.end(), v.begin(), v.end());
-        p.h_ks_off.push_back((int)p.h_ks_segs.size());
-    }
-    p.n_kwg = nwg;
-}
-
-// Segmented sample tables (S > 128): units (row block of 64, 128-sample pass,
-// 64-column block of L) ordered row block-major, then pass, then column block
-// (a run accumulates x over consecutive column blocks of one (row block,
-// pass)); equal-count contiguous runs, one per workgroup, two workgroups per
-// CU; a run's piece of one (row block, pass) is a segment writing its own
-// slot, and the reduce adds a (row block, pass)'s slots in segment order.
-// XCD placement as the K-split update: workgroup w -> run (w % 8) (nwg / 8) + w / 8.
-// One table for nwg_max workgroups (into segs / off / rbs and the counts).
-static void build_fseg_table(const psvi_plan& p, int nwg_max, std::vector<FsSeg>& segs,
-                             std::vector<int>& off, std::vector<FwdRowBlock>& rbs, int& n_wg,
-                             int& n_slots, int& n_rb) {
-    const int r = p.rank, np = (p.d.S + kKsPass - 1) / kKsPass;
-    struct Blk {
-        int layer, r0, r1, xcol, nkb;
-    };
-    std::vector<Blk> blks;
-    for (const ShardRun& run : p.runs[r]) {
-        const int n = p.lay[run.layer].n;
-        for (int r0 = run.lo; r0 < run.hi; r0 += kFwdRows) {
-            const int r1 = std::min(r0 + kFwdRows, run.hi);
-            const int kmax = std::max(0, std::min(r1 - 1, n - 2));
-            blks.push_back(Blk{run.layer, r0, r1, run.col + (r0 - run.lo), (kmax + 63) / 64});
-        }
-    }
-    segs.clear();
-    off.clear();
-    rbs.clear();
-    n_wg = n_slots = n_rb = 0;
-    const int B = (int)blks.size();
-    std::vector<int64_t> ub(B + 1, 0);
-    for (int b = 0; b < B; ++b) ub[b + 1] = ub[b] + (int64_t)blks[b].nkb * np;
-    const int64_t U = ub[B];
-    if (U == 0) return;
-    int nwg = (int)std::min<int64_t>(U, nwg_max);
-    if (nwg >= 8) nwg -= nwg % 8;
-    std::vector<int64_t> cut(nwg + 1);
-    for (int w = 0; w <= nwg; ++w) cut[w] = U * w / nwg;
-    // segments per workgroup; group g = b * np + pass
-    struct Piece {
-        int b, pass, kb0, kb1;
-    };
-    std::vector<std::vector<Piece>> per(nwg);
-    std::vector<int> nseg((size_t)B * np, 0);
-    for (int w = 0; w < nwg; ++w) {
-        int b = (int)(std::upper_bound(ub.begin(), ub.end(), cut[w]) - ub.begin()) - 1;
-        for (int64_t u = cut[w]; u < cut[w + 1];) {
-            while (u >= ub[b + 1]) ++b;
-            const int nkb = blks[b].nkb;
-            const int pass = (int)((u - ub[b]) / nkb), kb = (int)((u - ub[b]) % nkb);
-            const int64_t ue = std::min<int64_t>(cut[w + 1], ub[b] + (int64_t)(pass + 1) * nkb);
-            per[w].push_back(Piece{b, pass, kb, kb + (int)(ue - u)});
-            ++nseg[(size_t)b * np + pass];
-            u = ue;
-        }
-    }
-    std::vector<int> slot0((size_t)B * np), seen((size_t)B * np, 0);
-    for (int b = 0; b < B; ++b)
-        for (int q = 0; q < np; ++q) {
-            const size_t g = (size_t)b * np + q;
-            slot0[g] = n_slots;
-            n_slots += nseg[g];
-            rbs.push_back(FwdRowBlock{nseg[g] > 0 ? slot0[g] : 0, nseg[g], blks[b].r1 - blks[b].r0,
-                                            blks[b].xcol, blks[b].layer, blks[b].r0, kKsPass * q});
-        }
-    off.push_back(0);
-    for (int w = 0; w < nwg; ++w) {
-        const int run = (nwg % 8 == 0) ? (w % 8) * (nwg / 8) + w / 8 : w;
-        for (const Piece& pc : per[run]) {
-            const Blk& bk = blks[pc.b];
-            const size_t g = (size_t)pc.b * np + pc.pass;
-            segs.push_back(FsSeg{bk.layer, bk.r0, bk.r1, pc.pass, 64 * pc.kb0, 64 * pc.kb1,
-                                 slot0[g] + seen[g]++, 0});
-        }
-        off.push_back((int)segs.size());
-    }
-    n_wg = nwg;
-    n_rb = (int)rbs.size();
-}
-
-// The sample's table over 512 workgroups (two per CU), and the HVP pair's over
-// 256 (one eight-wave workgroup per CU: runs twice as long, fewer slots).
-void build_fseg(psvi_plan& p) {
-    build_fseg_table(p, 512, p.h_fs_segs, p.h_fs_off, p.h_fs_rb, p.n_fswg, p.n_fs_slots, p.n_fs_rb);
-    build_fseg_table(p, 256, p.h_fp_segs, p.h_fp_off, p.h_fp_rb, p.n_fpwg, p.n_fp_slots, p.n_fp_rb);
-}
-
-// make_lenet (neural_net.py:334-359): five mean-field-style layers, the first
-// two convolutions ("din" = in_channels * 25), the last one a single shared
-// sample.  Samples are sharded like the mean-field family.
-int build_lenet_plan(psvi_plan& p) {
-    static const int din[5] = {25, 150, 400, 120, 84}, dout[5] = {6, 16, 120, 84, 10};
+// The only device allocations of the library: a plan's immutable work lists
+// and its scratch, in a fixed order up to the first failure.
+int plan_to_device(psvi_plan& p) {
     const int S = p.d.S;
-    p.d.n_layers = 5;
-    p.d.dims[0] = 784;
-    for (int l = 0; l < 5; ++l) p.d.dims[l + 1] = dout[l];
-    p.L = 5;
-    int64_t po = 0, eo = 0;
-    int wo = 0;
-    for (int l = 0; l < 5; ++l) {
-        LayerInfo& li = p.lay[l];
-        li.din = din[l];
-        li.dout = dout[l];
-        li.n = din[l] * dout[l] + dout[l];
-        li.nc = 0;
-        li.poff = po;
-        li.eoff = eo;
-        li.woff = wo;
-        po += 2 * (int64_t)li.n;
-        eo += (l < 4 ? (int64_t)S : 1) * li.n;
-        wo += li.n;
+    const bool fullcov = p.family == PSVI_FAMILY_FULLCOV;
+    if (int rc = upload(p.fwd)) return rc;
+    if (int rc = upload(p.frb)) return rc;
+    if (int rc = upload(p.upd)) return rc;
+    // split-K scratch of the sample phase (plan-owned, reused every step)
+    if (p.fwd.n() > 0 && !p.fwd_part.alloc(sizeof(float) * (size_t)p.fwd.n() * S * kFwdRows))
+        return fail(PSVI_EUNSUP, "cannot allocate the sample-phase scratch");
+    if (p.fuse_sample && p.n_uslots > 0) {
+        if (int rc = upload(p.ufrb)) return rc;
+        if (!p.upd_part.alloc(sizeof(float) * (size_t)p.n_uslots * S * 64))
+            return fail(PSVI_EUNSUP, "cannot allocate the fused-sample scratch");
     }
-    p.P = po;
-    p.Peps = eo;
-    p.n_tot = wo;
-    for (int q = 0; q < p.world; ++q) {
-        const int base = S / p.world, rem = S % p.world;
-        p.s_cnt[q] = base + (q < rem ? 1 : 0);
-        p.s_off[q] = q * base + std::min(q, rem);
-        p.rows_tot[q] = 0;
+    if (p.str.n() > 0) {
+        if (int rc = upload(p.str)) return rc;
+        if (int rc = upload(p.sfrb)) return rc;
+        const size_t nb = (size_t)std::max(1, p.sfrb.n());
+        if (!p.str_part.alloc(sizeof(float) * (size_t)p.n_sslots * S * 64) ||
+            !p.str_cnt.alloc(sizeof(int) * nb, true) || !p.str_bms.alloc(sizeof(float) * 128 * nb))
+            return fail(PSVI_EUNSUP, "cannot allocate the streaming-update scratch");
     }
-    p.acc_count = 2 * (int64_t)p.n_tot;
-    p.ws_bytes = align256(sizeof(float) * (size_t)p.acc_count);
-    const int64_t kMaxOff = (int64_t(1) << 31) - 4096;
-    if (p.Peps > kMaxOff || (int64_t)p.s_cnt[p.rank] * p.d.M * kLenetRowFloats > kMaxOff * 4)
-        return fail(PSVI_EUNSUP, "LeNet scratch beyond the supported size");
-    return 0;
-}
-
-int build_plan(psvi_plan& p) {
-    if (p.family == PSVI_FAMILY_LENET) return build_lenet_plan(p);
-    const psvi_net_desc& d = p.d;
-    p.L = d.n_layers;
-    int64_t po = 0, eo = 0;
-    int wo = 0;
-    for (int l = 0; l < p.L; ++l) {
-        LayerInfo& li = p.lay[l];
-        li.din = d.dims[l];
-        li.dout = d.dims[l + 1];
-        li.n = li.din * li.dout + li.dout;
-        li.nc = (int64_t)(li.n - 1) * (li.n - 2) / 2;
-        li.poff = po;
-        li.eoff = eo;
-        li.woff = wo;
-        po += p.family == PSVI_FAMILY_MEANFIELD ? 2 * (int64_t)li.n : 2 * (int64_t)li.n + li.nc;
-        eo += (int64_t)d.S * li.n;
-        wo += li.n;
+    if (p.n_kwg() > 0) {
+        if (int rc = upload(p.ks_tiles)) return rc;
+        if (int rc = upload(p.ks_segs)) return rc;
+        if (int rc = upload(p.ks_off)) return rc;
+        if (!p.ks_slots.alloc(sizeof(float) * (size_t)std::max(1, p.n_ks_slots) * kKsSlotFloats) ||
+            !p.ks_cnt.alloc(sizeof(int) * std::max(1, p.n_ks_cnt), true))
+            return fail(PSVI_EUNSUP, "cannot allocate the K-split update's slots");
     }
-    p.P = po;
-    p.Peps = eo;
-    int64_t tb = 0;
-    for (int l = 0; l < p.L; ++l) {
-        LayerInfo& li = p.lay[l];
-        li.nb = p.family == PSVI_FAMILY_FULLCOV ? (li.n - 1) / 64 + 1 : 0;
-        li.tbase = tb;
-        tb += (int64_t)li.nb * (li.nb + 1) / 2;
+    if (p.n_fswg() > 0) {
+        if (int rc = upload(p.fs_segs)) return rc;
+        if (int rc = upload(p.fs_off)) return rc;
+        if (int rc = upload(p.fs_rb)) return rc;
+        if (int rc = upload(p.fp_segs)) return rc;
+        if (int rc = upload(p.fp_off)) return rc;
+        if (int rc = upload(p.fp_rb)) return rc;
+        // (the slots serve both tables)
+        if (!p.fs_part.alloc(sizeof(float) * (size_t)std::max({1, p.n_fs_slots, p.n_fp_slots}) *
+                             kKsPass * kFwdRows))
+            return fail(PSVI_EUNSUP, "cannot allocate the segmented sample's slots");
     }
-    p.tiles_total = tb;
-    p.n_tot = wo;
-    // sample shards
-    for (int q = 0; q < p.world; ++q) {
-        const int base = d.S / p.world, rem = d.S % p.world;
-        p.s_cnt[q] = base + (q < rem ? 1 : 0);
-        p.s_off[q] = q * base + std::min(q, rem);
+    if (fullcov) {
+        net_xmap(p, p.xmap.host, p.net_bands.host);
+        if (int rc = upload(p.xmap)) return rc;
+        if (int rc = upload(p.net_bands)) return rc;
     }
-    // row shards
-    assign_rows(p);
-    p.acc_count = 2 * (int64_t)p.n_tot;
-    net_plan_geometry(p);
-    if (p.net_lds > 160 * 1024)
-        return fail(PSVI_EUNSUP, "layer too wide for the per-sample LDS network kernel");
-    // the kernels address parameters, eps and the x / g shards with 32-bit offsets
-    const int64_t kMaxOff = (int64_t(1) << 31) - 4096;
-    int rows_max = 0;
-    for (int q = 0; q < p.world; ++q) rows_max = std::max(rows_max, p.rows_tot[q]);
-    if (p.P > kMaxOff || p.Peps > kMaxOff || (int64_t)d.S * rows_max > kMaxOff ||
-        (int64_t)d.S * p.n_tot > kMaxOff)
-        return fail(PSVI_EUNSUP, "buffers beyond 2^31 floats are not supported");
-
-    const int S = d.S, r = p.rank;
-    if (p.family == PSVI_FAMILY_FULLCOV) {
-        std::vector<FwdItem> fwd;
-        std::vector<UpdChunk> upd;
-        std::vector<FwdRowBlock> frb, ufrb;
-        int nslots = 0;
-        // c-blocks per update chunk: about one chunk per workgroup slot
-        // (256 CUs x 3 resident update workgroups), at least one
-        int tiles = 0;
-        for (const ShardRun& run : p.runs[r])
-            for (int b = run.lo / 64; 64 * b < run.hi; ++b) tiles += b + 1;
-        const int ch = g_upd_chunk_tiles > 0 ? g_upd_chunk_tiles : std::max(1, (tiles + 511) / 512);
-        for (const ShardRun& run : p.runs[r]) {
-            const int l = run.layer, n = p.lay[l].n, lo = run.lo, hi = run.hi;
-            const int xc = run.col;
-            for (int r0 = lo; r0 < hi; r0 += kFwdRows) {
-                const int r1 = std::min(r0 + kFwdRows, hi);
-                const int kmax = std::max(0, std::min(r1 - 1, n - 2));
-                const int nit = std::max(1, (kmax + kFwdKChunk - 1) / kFwdKChunk);
-                // even split, multiples of 64 columns (the kernel's LDS stage)
-                const int steps = (kmax + 63) / 64;
-                const int slot0 = (int)fwd.size();
-                for (int i = 0; i < nit; ++i) {
-                    const int k0 = std::min(kmax, 64 * (int)((int64_t)steps * i / nit));
-                    const int k1 = std::min(kmax, 64 * (int)((int64_t)steps * (i + 1) / nit));
-                    if (i > 0 && k0 >= k1) continue;
-                    fwd.push_back(FwdItem{l, r0, r1, k0, k1, xc + (r0 - lo), (int)fwd.size()});
-                }
-                frb.push_back(FwdRowBlock{slot0, (int)fwd.size() - slot0, r1 - r0, xc + (r0 - lo), l, r0});
-            }
-            // bands of 64 absolute rows; c-blocks 0..b, the last one diagonal.
-            // Each band is also a row block of the fused next-step sample: its
-            // chunks' partial slots are consecutive.
-            for (int b = lo / 64; 64 * b < hi; ++b) {
-                const int slot0 = nslots;
-                for (int k0 = 0; k0 <= b; k0 += ch) {
-                    const int k1 = std::min(b + 1, k0 + ch);
-                    upd.push_back(UpdChunk{l, 64 * b, k0, k1, lo, hi, xc - lo, k1 == b + 1, nslots++});
-                }
-                const int r0 = std::max(64 * b, lo), r1 = std::min(64 * b + 64, hi);
-                ufrb.push_back(FwdRowBlock{slot0, nslots - slot0, r1 - r0, xc + (r0 - lo), l, r0});
-            }
-        }
-        // longest forward items first
-        std::stable_sort(fwd.begin(), fwd.end(), [](const FwdItem& a, const FwdItem& b) {
-            return (a.k1 - a.k0) > (b.k1 - b.k0);
-        });
-        p.h_fwd = fwd;
-        p.h_frb = frb;
-        p.n_frb = (int)frb.size();
-        p.h_upd = xcd_order(upd);
-        // fusion needs band-aligned row blocks (rank row ranges start at 0) and
-        // one LDS pass of samples
-        p.fuse_sample = p.world == 1 && S <= 128;
-        p.h_ufrb = ufrb;
-        p.n_ufrb = (int)ufrb.size();
-        p.n_uslots = nslots;
-        // streaming fused update: the tile list (layer-major, band-major, the
-        // diagonal tile last in its band) cut into equal contiguous runs, one
-        // per workgroup (one workgroup per CU)
-        if (p.fuse_sample && S % 32 == 0 && p.world == 1) {
-            std::vector<uint32_t> tmap;
-            std::vector<int> tband;  // band id per tile
-            int nband = 0;
-            for (int l = 0; l < p.L; ++l)
-                for (int b = 0; b < p.lay[l].nb; ++b, ++nband)
-                    for (int k = 0; k <= b; ++k) {
-                        tmap.push_back((uint32_t)l << 28 | (uint32_t)b << 14 | (uint32_t)k);
-                        tband.push_back(nband);
-                    }
-            const int T = (int)tmap.size();
-            const int nwg = std::max(1, std::min(g_stream_wgs > 0 ? g_stream_wgs : 256, T));
-            // equal-cost runs: a band's diagonal (last) tile also updates the
-            // band's mean / sd, flushes its slot, drains and takes the band's
-            // ticket (and, for the last arriver, the combine after the walk); a
-            // band's first tile follows a G reload and split.  Weights 1.5 and
-            // 1.0 of a plain tile: the fastest of a sweep at C3
-            // (tools/stream_cost_sweep.py: 55.7 - 56.3 us per step against 58.4
-            // at the round-5 weights 0.35 / 0.4, which predate the in-kernel
-            // combine); workgroup stamps (tools/bf_stamps.py) show the slowest
-            // workgroups are the ones with band boundaries
-            std::vector<double> cum(T + 1, 0.0);
-            for (int t = 0; t < T; ++t) {
-                const uint32_t k = tmap[t] & 0x3fff, b = (tmap[t] >> 14) & 0x3fff;
-                const double wd = g_stream_cost >= 0 ? (g_stream_cost / 1000) * 0.01 : 1.5;
-                const double wf = g_stream_cost >= 0 ? (g_stream_cost % 1000) * 0.01 : 1.0;
-                cum[t + 1] = cum[t] + 1.0 + (k == b ? wd : 0.0) + (k == 0 ? wf : 0.0);
-            }
-            std::vector<int> cut(nwg + 1, 0);
-            cut[nwg] = T;
-            for (int w = 1; w < nwg; ++w) {
-                const double target = cum[T] * w / nwg;
-                int t = (int)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
-                cut[w] = std::max(cut[w - 1] + 1, std::min(t, T - (nwg - w)));
-            }
-            std::vector<std::vector<int>> band_slots(nband);
-            int ns = 0;
-            for (int w = 0; w < nwg; ++w) {
-                const int t0 = cut[w], t1 = cut[w + 1];
-                p.h_str.push_back(StreamRange{t0, t1, ns, t0 < T ? tmap[t0] : 0u});
-                int ends = 0;
-                for (int t = t0; t < t1; ++t)
-                    if (t == t0 || tband[t] != tband[t - 1]) {
-                        band_slots[tband[t]].push_back(ns++);
-                        ++ends;
-                    }
-                p.str_max_ends = std::max(p.str_max_ends, ends);
-            }
-            int bid = 0;
-            for (int l = 0; l < p.L; ++l)
-                for (int b = 0; b < p.lay[l].nb; ++b, ++bid) {
-                    const int r0 = 64 * b, R = std::min(64, p.lay[l].n - r0);
-                    const auto& sl = band_slots[bid];
-                    p.h_sfrb.push_back(FwdRowBlock{sl.front(), (int)sl.size(), R,
-                                                   p.xcol_l[r][l] + r0, l, r0});
-                }
-            // XCD-aware placement: workgroup w runs on XCD w % 8 (round-robin
-            // dispatch), so XCD x takes the contiguous eighth [x per, (x + 1) per)
-            // of the run list -- its bands' G slices and the eps / eps' columns
-            // up to its last band stay in that XCD's L2 instead of every XCD
-            // touching every band of both layers
-            if (nwg % 8 == 0 && !g_stream_rr) {
-                const int per = nwg / 8;
-                std::vector<StreamRange> xr(nwg);
-                for (int w = 0; w < nwg; ++w) xr[w] = p.h_str[(w % 8) * per + w / 8];
-                p.h_str.swap(xr);
-            }
-            p.n_str = (int)p.h_str.size();
-            p.n_sfrb = (int)p.h_sfrb.size();
-            p.n_sslots = ns;
-        }
-        p.upd_tiles = tiles;
-        // the K-split tables at every S: the Adam update at S > 128, the
-        // gradient mode (the HVP's reparameterised backward) at any S
-        build_kstream(p);
-        // the segmented sample at every S (x_0 of a loop, the HVP's tangent
-        // sample, the sharded step): equal runs over 512 workgroups
-        build_fseg(p);
-        p.n_fwd = (int)fwd.size();
-        p.n_upd = (int)p.h_upd.size();
-        const size_t xs = sizeof(float) * (size_t)S * p.rows_tot[r];
-        p.ws_bytes = align256(xs) * 2 + 256;
-    } else {
-        p.ws_bytes = align256(sizeof(float) * (size_t)p.acc_count);
+    if (fullcov && p.mchunks > 1 &&
+        !p.net_slots.alloc(sizeof(float) * (size_t)p.mchunks * std::max(1, p.s_cnt[p.rank]) * p.n_tot))
+        return fail(PSVI_EUNSUP, "cannot allocate the network's pseudopoint-chunk slots");
+    if (p.family == PSVI_FAMILY_MEANFIELD &&
+        !p.mf_slots.alloc(sizeof(float) * (size_t)std::max(1, p.s_cnt[p.rank]) * p.mchunks * p.n_tot))
+        return fail(PSVI_EUNSUP, "cannot allocate the mean-field gradient slots");
+    if (fullcov && p.fuse_sample && p.tiles_total > 0 && !p.aux.create())
+        return fail(PSVI_EUNSUP, "cannot create the inner loop's conversion stream");
+    if (p.eps_planes_ok) {
+        p.eps_planes_tab.host.assign(1, p.eps_planes);
+        if (int rc = upload(p.eps_planes_tab)) return rc;
     }
+    if (p.family == PSVI_FAMILY_LENET && !p.lenet_scratch.alloc(lenet_ws(p, nullptr).bytes))
+        return fail(PSVI_EUNSUP, "cannot allocate the LeNet activation scratch");
     return 0;
 }
 
@@ -643,11 +196,11 @@ int psvi_debug_set(int32_t key, int32_t value) {
             g_net_wg_target = value;
             return 0;
         case PSVI_DBG_FWD_ABLATION: g_fwd_ablation = value; return 0;
-        case PSVI_DBG_UPD_CHUNK: g_upd_chunk_tiles = value; return 0;
+        case PSVI_DBG_UPD_CHUNK: g_plan_dbg.upd_chunk_tiles = value; return 0;
         case PSVI_DBG_UPD_STREAM_OFF: g_stream_off = value; return 0;
         case PSVI_DBG_STREAM_BF_OFF: g_stream_bf_off = value; return 0;
         case PSVI_DBG_KSTREAM_OFF: g_ks_off = value; return 0;
-        case PSVI_DBG_KSTREAM_WGS: g_ks_wgs = value; return 0;
+        case PSVI_DBG_KSTREAM_WGS: g_plan_dbg.ks_wgs = value; return 0;
         case PSVI_DBG_FWD_SEG_OFF: g_fs_off = value; return 0;
         case PSVI_DBG_FWD_SEG_BF_OFF: g_fs_bf_off = value; return 0;
         case PSVI_DBG_FWD_PAIR_BF: g_fwd_pair_bf = value; return 0;
@@ -662,9 +215,9 @@ int psvi_debug_set(int32_t key, int32_t value) {
             if (value < 0 || value > 32) return fail(PSVI_EINVAL, "0..32");
             g_net_draw_role1 = value;
             return 0;
-        case PSVI_DBG_STREAM_WGS: g_stream_wgs = value; return 0;
-        case PSVI_DBG_STREAM_COST: g_stream_cost = value; return 0;
-        case PSVI_DBG_STREAM_RR: g_stream_rr = value; return 0;
+        case PSVI_DBG_STREAM_WGS: g_plan_dbg.stream_wgs = value; return 0;
+        case PSVI_DBG_STREAM_COST: g_plan_dbg.stream_cost = value; return 0;
+        case PSVI_DBG_STREAM_RR: g_plan_dbg.stream_rr = value; return 0;
         case PSVI_DBG_LENET_ABLATION: g_lenet_abl = value; return 0;
         case PSVI_DBG_NET_THREADS:
             if (value != 0 && value != 256 && value != 512) return fail(PSVI_EINVAL, "256 or 512");
@@ -734,111 +287,11 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world, int3
     p->d = *d;
     p->world = world;
     p->rank = rank;
-    int rc = build_plan(*p);
-    if (!rc && family == PSVI_FAMILY_FULLCOV && world == 1) {
-        // the bf16 planes of a draw (EpsPlanes): rows padded to 64-column
-        // multiples, layers back to back -- the streaming update's operands
-        // (bf_stream: the plans that run it), and for every plan the layout
-        // of the diagnostics planes (PSVI_DBG_NET_DRAW_PLANES)
-        psvi::EpsPlanes& E = p->eps_planes;
-        E.L = p->L;
-        int64_t po = 0, eo = 0;
-        for (int l = 0; l < p->L; ++l) {
-            const int n = p->lay[l].n;
-            E.eoff[l] = eo;
-            E.n[l] = n;
-            E.npad[l] = (n + 63) / 64 * 64;
-            E.poff[l] = po;
-            eo += (int64_t)p->d.S * n;
-            po += (int64_t)p->d.S * E.npad[l];
-        }
-        E.eoff[p->L] = eo;
-        E.pl = (po + 63) / 64 * 64;
-        p->eps_planes_ok = eo == p->Peps;
-        p->bf_stream = p->eps_planes_ok && p->fuse_sample && p->tiles_total > 0 && p->n_str > 0 &&
-                       p->d.S == 128;
-    }
+    std::string err;
+    int rc = build_plan(*p, err);
+    if (rc) rc = fail(rc, err);
     if (!rc && have_dev) {
-        // the only device allocations of the library: immutable work lists
-        if (!(rc = upload(p->h_fwd, &p->d_fwd)) && !(rc = upload(p->h_frb, &p->d_frb)))
-            rc = upload(p->h_upd, &p->d_upd);
-        if (!rc && p->n_fwd > 0) {
-            // split-K scratch of the sample phase (plan-owned, reused every step)
-            const size_t bytes = sizeof(float) * (size_t)p->n_fwd * p->d.S * kFwdRows;
-            if (hipMalloc((void**)&p->d_fwd_part, bytes) != hipSuccess)
-                rc = fail(PSVI_EUNSUP, "cannot allocate the sample-phase scratch");
-        }
-        if (!rc && p->fuse_sample && p->n_uslots > 0) {
-            const size_t bytes = sizeof(float) * (size_t)p->n_uslots * p->d.S * 64;
-            if ((rc = upload(p->h_ufrb, &p->d_ufrb)) == 0 &&
-                hipMalloc((void**)&p->d_upd_part, bytes) != hipSuccess)
-                rc = fail(PSVI_EUNSUP, "cannot allocate the fused-sample scratch");
-        }
-        if (!rc && p->n_str > 0) {
-            const size_t bytes = sizeof(float) * (size_t)p->n_sslots * p->d.S * 64;
-            if (!(rc = upload(p->h_str, &p->d_str)) && !(rc = upload(p->h_sfrb, &p->d_sfrb)) &&
-                (hipMalloc((void**)&p->d_str_part, bytes) != hipSuccess ||
-                 hipMalloc((void**)&p->d_str_cnt, sizeof(int) * (size_t)std::max(1, p->n_sfrb)) != hipSuccess ||
-                 hipMemset(p->d_str_cnt, 0, sizeof(int) * (size_t)std::max(1, p->n_sfrb)) != hipSuccess ||
-                 hipMalloc((void**)&p->d_str_bms, sizeof(float) * 128 * (size_t)std::max(1, p->n_sfrb)) != hipSuccess))
-                rc = fail(PSVI_EUNSUP, "cannot allocate the streaming-update scratch");
-        }
-        if (!rc && p->n_kwg > 0) {
-            if (!(rc = upload(p->h_ks_tiles, &p->d_ks_tiles)) &&
-                !(rc = upload(p->h_ks_segs, &p->d_ks_segs)))
-                rc = upload(p->h_ks_off, &p->d_ks_off);
-            const size_t sb = sizeof(float) * (size_t)std::max(1, p->n_ks_slots) * kKsSlotFloats;
-            if (!rc && (hipMalloc((void**)&p->d_ks_slots, sb) != hipSuccess ||
-                        hipMalloc((void**)&p->d_ks_cnt, sizeof(int) * std::max(1, p->n_ks_cnt)) !=
-                            hipSuccess ||
-                        hipMemset(p->d_ks_cnt, 0, sizeof(int) * std::max(1, p->n_ks_cnt)) !=
-                            hipSuccess))
-                rc = fail(PSVI_EUNSUP, "cannot allocate the K-split update's slots");
-        }
-        if (!rc && p->n_fswg > 0) {
-            if (!(rc = upload(p->h_fs_segs, &p->d_fs_segs)) && !(rc = upload(p->h_fs_off, &p->d_fs_off)))
-                rc = upload(p->h_fs_rb, &p->d_fs_rb);
-            if (!rc && !(rc = upload(p->h_fp_segs, &p->d_fp_segs)) && !(rc = upload(p->h_fp_off, &p->d_fp_off)))
-                rc = upload(p->h_fp_rb, &p->d_fp_rb);
-            // (the slots serve both tables)
-            const size_t sb = sizeof(float) * (size_t)std::max({1, p->n_fs_slots, p->n_fp_slots}) * kKsPass *
-                              kFwdRows;
-            if (!rc && hipMalloc((void**)&p->d_fs_part, sb) != hipSuccess)
-                rc = fail(PSVI_EUNSUP, "cannot allocate the segmented sample's slots");
-        }
-        if (!rc && family == PSVI_FAMILY_FULLCOV) {
-            std::vector<uint32_t> xmap;
-            std::vector<NetBand> bands;
-            net_xmap(*p, xmap, bands);
-            if (!(rc = upload(xmap, &p->d_net_xmap)))
-                rc = upload(bands, &p->d_net_bands);
-        }
-        if (!rc && family == PSVI_FAMILY_FULLCOV && p->mchunks > 1) {
-            const size_t bytes = sizeof(float) * (size_t)p->mchunks *
-                                 std::max(1, p->s_cnt[p->rank]) * p->n_tot;
-            if (hipMalloc((void**)&p->d_net_slots, bytes) != hipSuccess)
-                rc = fail(PSVI_EUNSUP, "cannot allocate the network's pseudopoint-chunk slots");
-        }
-        if (!rc && family == PSVI_FAMILY_MEANFIELD) {
-            const size_t bytes = sizeof(float) * (size_t)std::max(1, p->s_cnt[p->rank]) *
-                                 p->mchunks * p->n_tot;
-            if (hipMalloc((void**)&p->d_mf_slots, bytes) != hipSuccess)
-                rc = fail(PSVI_EUNSUP, "cannot allocate the mean-field gradient slots");
-        }
-        if (!rc && p->family == PSVI_FAMILY_FULLCOV && p->fuse_sample && p->tiles_total > 0 &&
-            (hipStreamCreateWithFlags(&p->aux_st, hipStreamNonBlocking) != hipSuccess ||
-             hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
-             hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
-            rc = fail(PSVI_EUNSUP, "cannot create the inner loop's conversion stream");
-        if (!rc && p->eps_planes_ok) {
-            std::vector<psvi::EpsPlanes> one(1, p->eps_planes);
-            rc = upload(one, &p->d_eps_planes);
-        }
-        if (!rc && family == PSVI_FAMILY_LENET) {
-            const size_t bytes = lenet_ws(*p, nullptr).bytes;
-            if (hipMalloc(&p->d_lenet_ws, bytes) != hipSuccess)
-                rc = fail(PSVI_EUNSUP, "cannot allocate the LeNet activation scratch");
-        }
+        rc = plan_to_device(*p);
         p->on_device = rc == 0;
     }
     if (rc) {
@@ -876,39 +329,6 @@ int psvi_plan_create_lik(int32_t family, const psvi_net_desc* d, int32_t world, 
 }
 
 int psvi_plan_destroy(psvi_plan* p) {
-    if (!p) return 0;
-    if (p->d_fwd) (void)hipFree(p->d_fwd);
-    if (p->d_frb) (void)hipFree(p->d_frb);
-    if (p->d_fwd_part) (void)hipFree(p->d_fwd_part);
-    if (p->d_ufrb) (void)hipFree(p->d_ufrb);
-    if (p->d_str) (void)hipFree(p->d_str);
-    if (p->d_sfrb) (void)hipFree(p->d_sfrb);
-    if (p->d_str_part) (void)hipFree(p->d_str_part);
-    if (p->d_str_cnt) (void)hipFree(p->d_str_cnt);
-    if (p->d_str_bms) (void)hipFree(p->d_str_bms);
-    if (p->d_upd_part) (void)hipFree(p->d_upd_part);
-    if (p->d_upd) (void)hipFree(p->d_upd);
-    if (p->d_lenet_ws) (void)hipFree(p->d_lenet_ws);
-    if (p->d_mf_slots) (void)hipFree(p->d_mf_slots);
-    if (p->d_net_slots) (void)hipFree(p->d_net_slots);
-    if (p->d_net_xmap) (void)hipFree(p->d_net_xmap);
-    if (p->d_ks_tiles) (void)hipFree(p->d_ks_tiles);
-    if (p->d_ks_segs) (void)hipFree(p->d_ks_segs);
-    if (p->d_ks_off) (void)hipFree(p->d_ks_off);
-    if (p->d_ks_slots) (void)hipFree(p->d_ks_slots);
-    if (p->d_ks_cnt) (void)hipFree(p->d_ks_cnt);
-    if (p->d_fs_segs) (void)hipFree(p->d_fs_segs);
-    if (p->d_fs_off) (void)hipFree(p->d_fs_off);
-    if (p->d_fs_rb) (void)hipFree(p->d_fs_rb);
-    if (p->d_fp_segs) (void)hipFree(p->d_fp_segs);
-    if (p->d_fp_off) (void)hipFree(p->d_fp_off);
-    if (p->d_fp_rb) (void)hipFree(p->d_fp_rb);
-    if (p->d_fs_part) (void)hipFree(p->d_fs_part);
-    if (p->d_net_bands) (void)hipFree(p->d_net_bands);
-    if (p->d_eps_planes) (void)hipFree(p->d_eps_planes);
-    if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-    if (p->ev_join) (void)hipEventDestroy(p->ev_join);
-    if (p->aux_st) (void)hipStreamDestroy(p->aux_st);
     delete p;
     return 0;
 }
@@ -958,7 +378,7 @@ static HvpWs hvp_ws(const psvi_plan* p, void* ws) {
     if (p->lik == PSVI_LIK_GAUSSIAN) o.dzd = (float*)take(sizeof(float) * S * M);
     if (p->family == PSVI_FAMILY_FULLCOV)
         o.part2 = (float*)take(sizeof(float) *
-                               std::max({(size_t)p->n_fwd * S, (size_t)p->n_fp_slots * kKsPass,
+                               std::max({(size_t)p->fwd.n() * S, (size_t)p->n_fp_slots * kKsPass,
                                          (size_t)p->n_fs_slots * kKsPass}) *
                                kFwdRows);  // item-grid or either segment table's slots
     o.bytes = off;
@@ -1135,11 +555,11 @@ static int step_impl(const psvi_plan* p, const float* u, Targets z, const float*
         up.kl_out = elbo_out; up.grad_out = grad_out; up.include_kl = include_kl;
         if (p->family == PSVI_FAMILY_LENET) {
             float* acc = (float*)wsb;
-            HIP_TRY(launch_lenet(*p, u, z.slots(), w, params, eps, acc, elbo_out, p->d_lenet_ws, st));
+            HIP_TRY(launch_lenet(*p, u, z.slots(), w, params, eps, acc, elbo_out, p->lenet_scratch.dev, st));
             up.acc = acc;
         } else {
             // per-(sample, chunk) gradient slots, summed in a fixed order by the update
-            n.params = params; n.eps = eps; n.mf_slots = p->d_mf_slots;
+            n.params = params; n.eps = eps; n.mf_slots = p->mf_slots.dev;
             HIP_TRY(launch_net(*p, n, st));
             up.slot_eps = eps;
         }
@@ -1191,11 +611,11 @@ int psvi_mf_phase_accumulate(const psvi_plan* p, const float* u, const int32_t* 
         return fail(PSVI_EINVAL, "null pointer");
     hipStream_t st = as_stream(stream);
     if (p->family == PSVI_FAMILY_LENET) {
-        HIP_TRY(launch_lenet(*p, u, z, w, params, eps, acc, nll_out, p->d_lenet_ws, st));
+        HIP_TRY(launch_lenet(*p, u, z, w, params, eps, acc, nll_out, p->lenet_scratch.dev, st));
         return 0;
     }
     NetLaunch n = net_rows(u, abi_targets(p, z), w, nll_out);
-    n.params = params; n.eps = eps; n.mf_slots = p->d_mf_slots;
+    n.params = params; n.eps = eps; n.mf_slots = p->mf_slots.dev;
     HIP_TRY(launch_net(*p, n, st));
     HIP_TRY(launch_mf_slot_acc(*p, eps, acc, st));
     return 0;
@@ -1440,7 +860,7 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
             const bool draw = !eps && t + 1 < T;
             float* en_buf = draw ? ebuf[(t + 1) & 1] : nullptr;
             NetLaunch n = net_rows(u, zt, w, elbo_out + t);
-            n.params = params; n.eps = e; n.mf_slots = p->d_mf_slots;
+            n.params = params; n.eps = e; n.mf_slots = p->mf_slots.dev;
             n.draw.out = en_buf; n.draw.n = draw ? p->Peps : 0;
             n.draw.seed = seed; n.draw.offset = offset + (uint64_t)(t + 1) * es;
             HIP_TRY(launch_net(*p, n, st));
@@ -1512,11 +932,11 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
     } else {
         // packed -> tiled state on the plan's conversion stream, behind x_0 and the
         // first network step (joined before the first update)
-        if (ts && p->aux_st) {
-            HIP_TRY(hipEventRecord(p->ev_fork, st));
-            HIP_TRY(hipStreamWaitEvent(p->aux_st, p->ev_fork, 0));
-            HIP_TRY(launch_mvn_tile_convert(*p, params, adam_m, adam_v, ts, true, p->aux_st, pads));
-            HIP_TRY(hipEventRecord(p->ev_join, p->aux_st));
+        if (ts && p->aux.st) {
+            HIP_TRY(hipEventRecord(p->aux.fork, st));
+            HIP_TRY(hipStreamWaitEvent(p->aux.st, p->aux.fork, 0));
+            HIP_TRY(launch_mvn_tile_convert(*p, params, adam_m, adam_v, ts, true, p->aux.st, pads));
+            HIP_TRY(hipEventRecord(p->aux.join, p->aux.st));
             join = true;
         } else if (ts) {
             HIP_TRY(launch_mvn_tile_convert(*p, params, adam_m, adam_v, ts, true, st, pads));
@@ -1553,7 +973,7 @@ int psvi_inner_loop_ex(const psvi_plan* p, const float* u, const int32_t* z, con
         const float* en = !last ? (eps ? eps + (size_t)(t + 1) * p->Peps : en_buf) : (keep ? en_buf : nullptr);
         if (tm) HIP_TRY(loop_event(1, st));
         if (join) {
-            HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
+            HIP_TRY(hipStreamWaitEvent(st, p->aux.join, 0));
             join = false;
         }
         // the last step (no next sample) writes corr / m / v back to the packed
@@ -1623,7 +1043,7 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
     n.params = params; n.eps = eps; n.xrecv = x; n.outer = &fw;
     if (p->family == PSVI_FAMILY_LENET)
         HIP_TRY(launch_lenet(*p, x_all, z_all.slots(), w_all, params, eps, nullptr, nullptr,
-                             p->d_lenet_ws, st, &fw));
+                             p->lenet_scratch.dev, st, &fw));
     else
         HIP_TRY(launch_net(*p, n, st));
     if (!ext_coef) {
@@ -1659,10 +1079,10 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
         up.params = const_cast<float*>(params); up.grad_out = grad_params;
         if (p->family == PSVI_FAMILY_LENET) {
             HIP_TRY(launch_lenet(*p, x_all, z_all.slots(), w_all, params, eps, acc, nullptr,
-                                 p->d_lenet_ws, st, &bw));
+                                 p->lenet_scratch.dev, st, &bw));
             up.acc = acc;
         } else {
-            b.params = params; b.eps = eps; b.mf_slots = p->d_mf_slots;
+            b.params = params; b.eps = eps; b.mf_slots = p->mf_slots.dev;
             HIP_TRY(launch_net(*p, b, st));
             up.slot_eps = eps;
         }
@@ -1758,7 +1178,7 @@ int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, cons
     n.params = params; n.eps = eps; n.xrecv = x; n.outer = &fw;
     if (p->family == PSVI_FAMILY_LENET)
         HIP_TRY(launch_lenet(*p, x_all, z_all, w_all, params, eps, nullptr, nullptr,
-                             p->d_lenet_ws, st, &fw));
+                             p->lenet_scratch.dev, st, &fw));
     else
         HIP_TRY(launch_net(*p, n, st));
     HIP_TRY(launch_eval(*p, n_pseudo, params, w_all, z_all, o.nll, o.stats, prob,

@@ -1715,7 +1715,7 @@ LenetTanWs lenet_tan_ws(const psvi_plan& p, void* base) {
 hipError_t launch_lenet_hvp(const psvi_plan& p, const float* u, const int32_t* z, const float* w,
                             const float* eps, const float* params, const float* vec, float* hv,
                             float* d_u, float* d_w, void* tws, hipStream_t st, bool include_kl) {
-    const LenetWs W = lenet_ws(p, p.d_lenet_ws);
+    const LenetWs W = lenet_ws(p, p.lenet_scratch.dev);
     const LenetTanWs T = lenet_tan_ws(p, tws);
     const SampleArgs sa = sample_args(p);
     const int S = sa.S_loc, M = p.d.M, nt = p.n_tot;
@@ -1723,7 +1723,7 @@ hipError_t launch_lenet_hvp(const psvi_plan& p, const float* u, const int32_t* z
     // primal pass: activations, routes, per-sample G, row probabilities
     if (hipError_t e = hipMemsetAsync(T.nll, 0, sizeof(double), st)) return e;
     NetOuter keep{0, 0, nullptr, nullptr, nullptr, nullptr, T.prob};
-    if (hipError_t e = launch_lenet(p, u, z, w, params, eps, T.acc, T.nll, p.d_lenet_ws, st, &keep))
+    if (hipError_t e = launch_lenet(p, u, z, w, params, eps, T.acc, T.nll, p.lenet_scratch.dev, st, &keep))
         return e;
     {
         const int64_t nb = std::min<int64_t>(((int64_t)S * nt + kThreads - 1) / kThreads, 8192);

@@ -242,7 +242,7 @@ static void mf_slot_args(const psvi_plan& p, const float* eps, MfUpdArgs& a) {
     }
     a.woff[p.L] = p.n_tot;
     a.n_tot = p.n_tot;
-    a.slots = p.d_mf_slots;
+    a.slots = p.mf_slots.dev;
     a.seps = eps;
     a.S_loc = p.s_cnt[p.rank];
     a.nz = p.mchunks;
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void mf_slot_acc_kernel(MfUpdArgs a, float* ac
 }
 
 hipError_t launch_mf_slot_acc(const psvi_plan& p, const float* eps, float* acc, hipStream_t st) {
-    if (!p.d_mf_slots) return hipErrorInvalidValue;
+    if (!p.mf_slots.dev) return hipErrorInvalidValue;
     MfUpdArgs a{};
     mf_slot_args(p, eps, a);
     hipLaunchKernelGGL(mf_slot_acc_kernel, dim3((p.n_tot + kSlotGroups - 1) / kSlotGroups),
@@ -286,7 +286,7 @@ hipError_t launch_mf_slot_acc(const psvi_plan& p, const float* eps, float* acc, 
 
 hipError_t launch_mf_update(const psvi_plan& p, const MfUpdate& r, hipStream_t st) {
     const bool slots = r.acc == nullptr;
-    if (slots && (!p.d_mf_slots || !r.slot_eps)) return hipErrorInvalidValue;
+    if (slots && (!p.mf_slots.dev || !r.slot_eps)) return hipErrorInvalidValue;
     MfUpdArgs a{};
     mf_slot_args(p, r.slot_eps, a);
     a.woff[p.L] = p.n_tot;

@@ -3144,7 +3144,7 @@ hipError_t launch_mvn_tile_convert(const psvi_plan& p, float* params, float* m, 
 // on one GPU); every (item, sample) partial still has one writer.
 static int fwd_sample_blocks(const psvi_plan& p, int pairs = 1) {
     const int nsb = (p.d.S + FST - 1) / FST;
-    const int want = (512 + p.n_fwd * pairs - 1) / (p.n_fwd * pairs);
+    const int want = (512 + p.fwd.n() * pairs - 1) / (p.fwd.n() * pairs);
     return std::max(1, std::min(nsb, want));
 }
 
@@ -3152,40 +3152,40 @@ hipError_t launch_mvn_fwd(const psvi_plan& p, const float* eps, const float* par
                           float* x_shard, hipStream_t st, const float* diag_of) {
     FwdArgs a{};
     a.diag_of = diag_of;
-    a.items = p.d_fwd;
+    a.items = p.fwd.dev;
     a.params = params;
     a.eps = eps;
-    a.part = p.d_fwd_part;
+    a.part = p.fwd_part.dev;
     a.ldx = p.rows_tot[p.rank];
     a.S = p.d.S;
     a.e_total = p.Peps;
     a.abl = g_fwd_ablation;
     a.stamps = g_fwd_stamps;
     fill_layers(p, a.lay);
-    if (p.n_fswg > 0 && !g_fs_off) {
+    if (p.n_fswg() > 0 && !g_fs_off) {
         // K = S > 128: the segmented sample, then the (row block, pass) reduce
-        a.segs = p.d_fs_segs;
-        a.seg_off = p.d_fs_off;
+        a.segs = p.fs_segs.dev;
+        a.seg_off = p.fs_off.dev;
         a.pcount = p.P;
-        a.part = p.d_fs_part;
+        a.part = p.fs_part.dev;
         a.slot_rows = FST;
         a.slot_frag = 1;
-        a.seg_nrun = p.n_fswg;
+        a.seg_nrun = p.n_fswg();
         a.abl = 0;
         if (g_fs_bf_off || a.stamps)
-            hipLaunchKernelGGL(mvn_fwd_seg_kernel, dim3(p.n_fswg), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(mvn_fwd_seg_kernel, dim3(p.n_fswg()), dim3(256), 0, st, a);
         else
-            hipLaunchKernelGGL(mvn_fwd_seg_bf_kernel<false>, dim3(p.n_fswg), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_fs_rb, FST / kRedSpb), dim3(256), 0, st,
-                           p.d_fs_rb, p.d_fs_part, a, x_shard);
+            hipLaunchKernelGGL(mvn_fwd_seg_bf_kernel<false>, dim3(p.n_fswg()), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.fs_rb.n(), FST / kRedSpb), dim3(256), 0, st,
+                           p.fs_rb.dev, p.fs_part.dev, a, x_shard);
         return hipGetLastError();
     }
-    if (p.n_fwd == 0) return hipSuccess;
+    if (p.fwd.n() == 0) return hipSuccess;
     // every x element is written by exactly one reduce thread: no memset
-    hipLaunchKernelGGL(mvn_fwd_kernel, dim3(p.n_fwd, 1, fwd_sample_blocks(p)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mvn_fwd_kernel, dim3(p.fwd.n(), 1, fwd_sample_blocks(p)), dim3(256), 0, st, a);
     constexpr int spb = kRedSpb;  // samples per reduce workgroup
-    hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_frb, (a.S + spb - 1) / spb), dim3(256), 0,
-                       st, p.d_frb, p.d_fwd_part, a, x_shard);
+    hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.frb.n(), (a.S + spb - 1) / spb), dim3(256), 0,
+                       st, p.frb.dev, p.fwd_part.dev, a, x_shard);
     return hipGetLastError();
 }
 
@@ -3195,7 +3195,7 @@ hipError_t launch_mvn_fwd(const psvi_plan& p, const float* eps, const float* par
 hipError_t launch_mvn_fwd_pair(const psvi_plan& p, const float* eps, const float* params,
                                float* x, const float* vec, float* x2, float* part2,
                                hipStream_t st) {
-    if (p.n_fpwg > 0 && !g_fs_off && !g_fs_bf_off && g_fwd_pair_bf) {
+    if (p.n_fpwg() > 0 && !g_fs_off && !g_fs_bf_off && g_fwd_pair_bf) {
         // the segmented sample's units over the pair table (256 workgroups of
         // eight waves), both matrices per unit (the eps stage shared), then the
         // pair reduce over the two slot sets.  Measured at C3: 25.4 + 7.5 us
@@ -3207,28 +3207,28 @@ hipError_t launch_mvn_fwd_pair(const psvi_plan& p, const float* eps, const float
         a.eps = eps;
         a.params2 = vec;
         a.diag_of2 = params;
-        a.part = p.d_fs_part;
+        a.part = p.fs_part.dev;
         a.part2 = part2;
         a.ldx = p.rows_tot[p.rank];
         a.S = p.d.S;
         a.e_total = p.Peps;
-        a.segs = p.d_fp_segs;
-        a.seg_off = p.d_fp_off;
+        a.segs = p.fp_segs.dev;
+        a.seg_off = p.fp_off.dev;
         a.pcount = p.P;
         a.slot_rows = FST;
         a.slot_frag = 1;
-        a.seg_nrun = p.n_fpwg;
+        a.seg_nrun = p.n_fpwg();
         fill_layers(p, a.lay);
-        hipLaunchKernelGGL(mvn_fwd_seg_bf_kernel<true>, dim3(p.n_fpwg), dim3(512), 0, st, a);
-        hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_fp_rb, FST / kRedSpb, 2), dim3(256), 0, st, p.d_fp_rb,
-                           p.d_fs_part, a, x, x2);
+        hipLaunchKernelGGL(mvn_fwd_seg_bf_kernel<true>, dim3(p.n_fpwg()), dim3(512), 0, st, a);
+        hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.fp_rb.n(), FST / kRedSpb, 2), dim3(256), 0, st, p.fp_rb.dev,
+                           p.fs_part.dev, a, x, x2);
         return hipGetLastError();
     }
     FwdArgs a{};
-    a.items = p.d_fwd;
+    a.items = p.fwd.dev;
     a.params = params;
     a.eps = eps;
-    a.part = p.d_fwd_part;
+    a.part = p.fwd_part.dev;
     a.params2 = vec;
     a.part2 = part2;
     a.diag_of2 = params;
@@ -3237,11 +3237,11 @@ hipError_t launch_mvn_fwd_pair(const psvi_plan& p, const float* eps, const float
     a.e_total = p.Peps;
     a.abl = g_fwd_ablation;
     fill_layers(p, a.lay);
-    if (p.n_fwd == 0) return hipSuccess;
-    hipLaunchKernelGGL(mvn_fwd_kernel, dim3(p.n_fwd, 2, fwd_sample_blocks(p, 2)), dim3(256), 0, st, a);
+    if (p.fwd.n() == 0) return hipSuccess;
+    hipLaunchKernelGGL(mvn_fwd_kernel, dim3(p.fwd.n(), 2, fwd_sample_blocks(p, 2)), dim3(256), 0, st, a);
     constexpr int spb = kRedSpb;
-    hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.n_frb, (a.S + spb - 1) / spb, 2), dim3(256),
-                       0, st, p.d_frb, p.d_fwd_part, a, x, x2);
+    hipLaunchKernelGGL(mvn_fwd_reduce_kernel, dim3(p.frb.n(), (a.S + spb - 1) / spb, 2), dim3(256),
+                       0, st, p.frb.dev, p.fwd_part.dev, a, x, x2);
     return hipGetLastError();
 }
 
@@ -3264,7 +3264,7 @@ static bool stream_ok(int S, int kind) {
     return S == 128 && (kind == PSVI_ADAM_HIGHER || kind == PSVI_ADAM_HYPERGRAD);
 }
 bool mvn_grad_takes_slots(const psvi_plan& p) {
-    return p.n_kwg > 0 && !g_ks_off && !g_ks_bf_off;
+    return p.n_kwg() > 0 && !g_ks_off && !g_ks_bf_off;
 }
 
 // the fields UpdArgs, StrArgs and KsArgs share by name
@@ -3308,12 +3308,12 @@ hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t
     UpdArgs a{};
     fill_update(p, r, a);
     a.kl_vec = r.kl_vec;
-    a.chunks = p.d_upd;
+    a.chunks = p.upd.dev;
     a.grad_out = r.grad_out;
     a.abl = g_upd_ablation;
     a.pcount = p.P;
-    if (p.n_upd == 0) return hipSuccess;
-    const dim3 grid(p.n_upd), block(256);
+    if (p.upd.n() == 0) return hipSuccess;
+    const dim3 grid(p.upd.n()), block(256);
     const int mode = a.S > USB ? 2 : a.S > UEH ? 1 : 0;  // samples per LDS pass
     if (r.tstate) {
         // tiled state (psvi_inner_loop on a fusable plan): corr / m / v in tstate
@@ -3321,20 +3321,20 @@ hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t
         a.tp = r.tstate;
         a.tm = r.tstate + tf;
         a.tv = r.tstate + 2 * tf;
-        if (r.next.eps && p.n_str > 0 && g_stream_off != 1 && stream_ok(a.S, a.adam.kind)) {
+        if (r.next.eps && p.str.n() > 0 && g_stream_off != 1 && stream_ok(a.S, a.adam.kind)) {
             StrArgs b{};
             fill_update(p, r, b);
-            b.ranges = p.d_str;
+            b.ranges = p.str.dev;
             b.eps_next = r.next.eps;
             b.tp = a.tp;
             b.tm = a.tm;
             b.tv = a.tv;
-            b.part = p.d_str_part;
+            b.part = p.str_part.dev;
             for (int l = 0; l < p.L; ++l) {
                 b.xcol[l] = p.xcol_l[p.rank][l];
                 b.nb[l] = p.lay[l].nb;
             }
-            const dim3 sg(p.n_str);
+            const dim3 sg(p.str.n());
             const bool bf = r.eps_planes && r.next.planes && p.bf_stream && r.padded && !g_stream_bf_off;
             if (bf) {
                 b.stamps = g_bf_stamps;
@@ -3347,10 +3347,10 @@ hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t
                     b.npad[l] = p.eps_planes.npad[l];
                 }
                 const dim3 b8(512);
-                const bool fold = p.d_str_cnt && p.d_str_bms && p.str_max_ends <= kFoldMax && !g_stream_fold_off;
-                b.rbs = p.d_sfrb;
-                b.bcnt = p.d_str_cnt;
-                b.bms = p.d_str_bms;
+                const bool fold = p.str_cnt.dev && p.str_bms.dev && p.str_max_ends <= kFoldMax && !g_stream_fold_off;
+                b.rbs = p.sfrb.dev;
+                b.bcnt = p.str_cnt.dev;
+                b.bms = p.str_bms.dev;
                 b.x = r.next.x;
                 b.ldx = p.rows_tot[p.rank];
                 if (fold && b.stamps && b.adam.kind == PSVI_ADAM_HIGHER)
@@ -3368,14 +3368,14 @@ hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t
                 hipLaunchKernelGGL((mvn_stream_kernel<4, PSVI_ADAM_HIGHER, true>), sg, block, 0, st, b);
             else
                 launch_stream(b.adam.kind, sg, block, st, b, r.padded);
-            return launch_next_reduce(p, r, p.d_sfrb, p.n_sfrb, p.d_str_part, st);
+            return launch_next_reduce(p, r, p.sfrb.dev, p.sfrb.n(), p.str_part.dev, st);
         }
         if (r.next.eps) {
             a.eps_next = r.next.eps;
-            a.part = p.d_upd_part;
+            a.part = p.upd_part.dev;
             if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<false, 1, true, true>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((mvn_update_kernel<false, 0, true, true>), grid, block, 0, st, a);
-            return launch_next_reduce(p, r, p.d_ufrb, p.n_ufrb, p.d_upd_part, st);
+            return launch_next_reduce(p, r, p.ufrb.dev, p.ufrb.n(), p.upd_part.dev, st);
         } else if (r.packed_out) {
             if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<false, 1, false, true, true>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((mvn_update_kernel<false, 0, false, true, true>), grid, block, 0, st, a);
@@ -3388,27 +3388,27 @@ hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t
     // gradient mode (the HVP's J^T G_dot) at any S on the bf16-piece K-split kernel
     const bool ks_grad = r.grad_out && mvn_grad_takes_slots(p);
     if (r.g_shard2 && !ks_grad) return hipErrorInvalidValue;
-    if ((mode == 2 && !r.grad_out && p.n_kwg > 0 && g_ks_off != 1) || ks_grad) {
+    if ((mode == 2 && !r.grad_out && p.n_kwg() > 0 && g_ks_off != 1) || ks_grad) {
         // K = S > 128: the K-split streaming update (then the next step's
         // sample from the new parameters when asked)
         KsArgs k{};
         fill_update(p, r, k);
-        k.tiles = p.d_ks_tiles;
-        k.segs = p.d_ks_segs;
-        k.seg_off = p.d_ks_off;
-        k.slots = p.d_ks_slots;
-        k.cnt = p.d_ks_cnt;
+        k.tiles = p.ks_tiles.dev;
+        k.segs = p.ks_segs.dev;
+        k.seg_off = p.ks_off.dev;
+        k.slots = p.ks_slots.dev;
+        k.cnt = p.ks_cnt.dev;
         k.slot_bytes = (int64_t)sizeof(float) * std::max(1, p.n_ks_slots) * kKsSlotFloats;
         k.pcount = p.P;
         k.grad_out = r.grad_out;
         k.kl_vec = r.kl_vec;
         k.g2 = r.g_shard2;
         if (ks_grad)
-            hipLaunchKernelGGL((mvn_kstream_kernel<true, true>), dim3(p.n_kwg), block, 0, st, k);
+            hipLaunchKernelGGL((mvn_kstream_kernel<true, true>), dim3(p.n_kwg()), block, 0, st, k);
         else if (g_ks_bf_off || k.stamps)
-            hipLaunchKernelGGL(mvn_kstream_kernel<false>, dim3(p.n_kwg), block, 0, st, k);
+            hipLaunchKernelGGL(mvn_kstream_kernel<false>, dim3(p.n_kwg()), block, 0, st, k);
         else
-            hipLaunchKernelGGL(mvn_kstream_kernel<true>, dim3(p.n_kwg), block, 0, st, k);
+            hipLaunchKernelGGL(mvn_kstream_kernel<true>, dim3(p.n_kwg()), block, 0, st, k);
         if (r.next.eps) {
             const hipError_t e = hipGetLastError();
             return e != hipSuccess ? e : launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
@@ -3424,10 +3424,10 @@ hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t
             return e != hipSuccess ? e : launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
         }
         a.eps_next = r.next.eps;
-        a.part = p.d_upd_part;
+        a.part = p.upd_part.dev;
         if (mode == 1) hipLaunchKernelGGL((mvn_update_kernel<false, 1, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((mvn_update_kernel<false, 0, true>), grid, block, 0, st, a);
-        return launch_next_reduce(p, r, p.d_ufrb, p.n_ufrb, p.d_upd_part, st);
+        return launch_next_reduce(p, r, p.ufrb.dev, p.ufrb.n(), p.upd_part.dev, st);
     }
     if (r.grad_out) {
         if (mode == 2) hipLaunchKernelGGL((mvn_update_kernel<true, 2>), grid, block, 0, st, a);

@@ -19,7 +19,7 @@
 // shapes whose buffers exceed the LDS, ranks with very few samples -- store
 // their partial dW into per-chunk slots of the plan, added in chunk order.)
 // Mean-field: every (sample, chunk) stores its gradient into its own slot of
-// the plan's d_mf_slots; mf_update_kernel sums the slots in a fixed order
+// the plan's mf_slots; mf_update_kernel sums the slots in a fixed order
 // (against eps for the rho accumulator), so the step is bitwise reproducible.
 //
 // LDS holds everything a workgroup touches.  Every matrix is row-major with
@@ -76,7 +76,7 @@ struct NetArgs {
     const float* eps;
     int64_t poff[kMaxL], eoff[kMaxL];
     // per-(sample, pseudopoint chunk) gradient slots [S_loc][gridDim.z][slot_ld]
-    // (the plan's d_mf_slots): one plain store per element, summed by the update
+    // (the plan's mf_slots): one plain store per element, summed by the update
     float* mf_slots;
     int slot_ld;
     // fused next-step draw (psvi_inner_loop): normals [0, rn_n) of the Philox
@@ -1592,15 +1592,15 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
     a.rn_n = d.n;
     a.rn_seed = d.seed;
     a.rn_off = d.offset;
-    a.rn_P = p.d_eps_planes;
-    a.rn_planes = rn_planes && p.d_eps_planes ? rn_planes : nullptr;
-    if (rn_planes && !p.d_eps_planes) return hipErrorInvalidValue;
+    a.rn_P = p.eps_planes_tab.dev;
+    a.rn_planes = rn_planes && p.eps_planes_tab.dev ? rn_planes : nullptr;
+    if (rn_planes && !p.eps_planes_tab.dev) return hipErrorInvalidValue;
     a.L = p.L;
     a.M = p.d.M;
     a.mc = p.mc;
     a.S_total = p.d.S;
     a.s_goff = p.s_off[p.rank];
-    a.gslot = p.family == PSVI_FAMILY_FULLCOV && p.mchunks > 1 ? p.d_net_slots : nullptr;
+    a.gslot = p.family == PSVI_FAMILY_FULLCOV && p.mchunks > 1 ? p.net_slots.dev : nullptr;
     a.gsz = (int64_t)p.s_cnt[p.rank] * p.n_tot;
     a.nroles = p.net_roles;
     a.abl = g_net_ablation;
@@ -1636,8 +1636,8 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
             c0 += (p.rows_tot[q] + 3) / 4;
         }
         a.src_chunk0[p.world] = c0;
-        a.xmap = p.d_net_xmap;
-        a.bands = p.d_net_bands;
+        a.xmap = p.xmap.dev;
+        a.bands = p.net_bands.dev;
         a.nbands = p.world > 1 ? p.band_base[p.L] : 0;
         if (!a.xmap || (p.world > 1 && !a.bands)) return hipErrorInvalidValue;
     }

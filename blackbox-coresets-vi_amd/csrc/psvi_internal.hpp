@@ -446,8 +446,78 @@ struct NetOuter {
     float* dz_part;       // mode 2, nullable, Gaussian plans: [S][n_pseudo] d loss_s / d z_m
 };
 
+// ------------------------------------------------------ plan-owned memory
+// A work list of a plan: the host copy, built with the plan, and the device
+// copy upload() makes of it, freed with the table.  The list's length is the
+// host vector's (an empty list has no device copy).
+template <class T>
+struct DevTable {
+    std::vector<T> host;
+    T* dev = nullptr;
+    DevTable() = default;
+    DevTable(const DevTable&) = delete;
+    DevTable& operator=(const DevTable&) = delete;
+    ~DevTable() {
+        if (dev) (void)hipFree(dev);
+    }
+    int n() const { return (int)host.size(); }
+    // *what: the call that failed, as the error message names it
+    hipError_t upload(const char** what) {
+        if (host.empty()) return hipSuccess;
+        *what = "hipMalloc((void**)dst, sizeof(T) * v.size())";
+        hipError_t e = hipMalloc((void**)&dev, sizeof(T) * host.size());
+        if (e != hipSuccess) {
+            dev = nullptr;
+            return e;
+        }
+        *what = "hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice)";
+        return hipMemcpy(dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice);
+    }
+};
+
+// Plan-owned device scratch, freed with the buffer.
+template <class T>
+struct DevBuffer {
+    T* dev = nullptr;
+    DevBuffer() = default;
+    DevBuffer(const DevBuffer&) = delete;
+    DevBuffer& operator=(const DevBuffer&) = delete;
+    ~DevBuffer() {
+        if (dev) (void)hipFree(dev);
+    }
+    bool alloc(size_t bytes, bool zero = false) {
+        if (hipMalloc((void**)&dev, bytes) != hipSuccess) {
+            dev = nullptr;
+            return false;
+        }
+        return !zero || hipMemset(dev, 0, bytes) == hipSuccess;
+    }
+};
+
+// A side stream of a plan with the events that fork it from and join it to the
+// caller's stream.
+struct AuxStream {
+    hipStream_t st = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    AuxStream() = default;
+    AuxStream(const AuxStream&) = delete;
+    AuxStream& operator=(const AuxStream&) = delete;
+    ~AuxStream() {
+        if (fork) (void)hipEventDestroy(fork);
+        if (join) (void)hipEventDestroy(join);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    bool create() {
+        return hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
+               hipEventCreateWithFlags(&fork, hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&join, hipEventDisableTiming) == hipSuccess;
+    }
+};
+
 }  // namespace psvi
 
+// The device members own their memory: a plan is not copyable, and deleting
+// it releases everything.
 struct psvi_plan {
     int family = 0;
     // observation model (psvi_plan_create_lik): PSVI_LIK_GAUSSIAN plans are
@@ -475,74 +545,63 @@ struct psvi_plan {
     int band_base[psvi::kMaxL + 1] = {0};
     // network kernel: LDS destination of every x element the workgroup loads
     // (stage position -> W_l / b_l offset | W_l^T offset << 16, 0xFFFF = none)
-    // and, world > 1, the band table (owner, column offset)
-    uint32_t* d_net_xmap = nullptr;
-    psvi::NetBand* d_net_bands = nullptr;
-    // work lists (host copies, then device)
-    std::vector<psvi::FwdItem> h_fwd;
-    std::vector<psvi::UpdChunk> h_upd;
-    bool on_device = false;
-    psvi::FwdItem* d_fwd = nullptr;
-    int n_fwd = 0;
-    std::vector<psvi::FwdRowBlock> h_frb;
-    psvi::FwdRowBlock* d_frb = nullptr;
-    int n_frb = 0;
-    float* d_fwd_part = nullptr;  // split-K partial slots: n_fwd x S x 32 floats (plan-owned)
-    psvi::UpdChunk* d_upd = nullptr;
+    // and, world > 1, the band table (owner, column offset); filled at upload
+    psvi::DevTable<uint32_t> xmap;
+    psvi::DevTable<psvi::NetBand> net_bands;
+    bool on_device = false;  // the tables are uploaded and the scratch allocated
+    // sample phase: forward items, their row blocks, split-K partial slots
+    // (fwd.n() x S x kFwdRows floats)
+    psvi::DevTable<psvi::FwdItem> fwd;
+    psvi::DevTable<psvi::FwdRowBlock> frb;
+    psvi::DevBuffer<float> fwd_part;
+    // update chunks (XCD order, padded with empty chunks)
+    psvi::DevTable<psvi::UpdChunk> upd;
+    int upd_tiles = 0;  // c-blocks over all chunks (work measure)
     // fused update + next-step sample (world == 1, S <= 128): one row block
     // per 64-row band, one partial slot per chunk
     bool fuse_sample = false;
     // tiled corr/m/v (world == 1, S <= 128 inner loops): 64x64 tiles (b, k <= b)
     // per layer in MFMA fragment order, tiles_total * 4096 floats per array
     int64_t tiles_total = 0;
-    std::vector<psvi::FwdRowBlock> h_ufrb;
-    psvi::FwdRowBlock* d_ufrb = nullptr;
-    int n_ufrb = 0, n_uslots = 0;
-    float* d_upd_part = nullptr;
+    psvi::DevTable<psvi::FwdRowBlock> ufrb;
+    int n_uslots = 0;
+    psvi::DevBuffer<float> upd_part;
     // streaming fused update (fuse_sample plans with S % 32 == 0): one
-    // workgroup per range, tile map, band row blocks over its slots
-    std::vector<psvi::StreamRange> h_str;
-    std::vector<psvi::FwdRowBlock> h_sfrb;
-    psvi::StreamRange* d_str = nullptr;
-    psvi::FwdRowBlock* d_sfrb = nullptr;
-    float* d_str_part = nullptr;
-    int* d_str_cnt = nullptr;  // the in-kernel band combine's arrival counters (n_sfrb)
-    float* d_str_bms = nullptr;  // per band: new mean + softplus(sd), 128 floats (n_sfrb)
-    int str_max_ends = 0;      // most band ends (slots) in one run of the stream
-    int n_str = 0, n_sfrb = 0, n_sslots = 0;
-    int n_upd = 0;
-    int upd_tiles = 0;  // c-blocks over all chunks (work measure)
+    // workgroup per range, band row blocks over its slots
+    psvi::DevTable<psvi::StreamRange> str;
+    psvi::DevTable<psvi::FwdRowBlock> sfrb;
+    psvi::DevBuffer<float> str_part;
+    psvi::DevBuffer<int> str_cnt;    // the in-kernel band combine's arrival counters (sfrb.n())
+    psvi::DevBuffer<float> str_bms;  // per band: new mean + softplus(sd), 128 floats (sfrb.n())
+    int str_max_ends = 0;            // most band ends (slots) in one run of the stream
+    int n_sslots = 0;
     // K-split streaming update (full-cov Adam steps with S > 128): tiles, the
-    // workgroups' segment lists (offsets [n_kwg + 1]), split-tile partial slots
+    // workgroups' segment lists (offsets [n_kwg() + 1]), split-tile partial slots
     // (kKsSlotFloats each) and their arrival counters (zeroed, reset by use)
-    std::vector<psvi::KsTile> h_ks_tiles;
-    std::vector<psvi::KsSeg> h_ks_segs;
-    std::vector<int> h_ks_off;
-    psvi::KsTile* d_ks_tiles = nullptr;
-    psvi::KsSeg* d_ks_segs = nullptr;
-    int* d_ks_off = nullptr;
-    float* d_ks_slots = nullptr;
-    int* d_ks_cnt = nullptr;
-    int n_kwg = 0, n_ks_slots = 0, n_ks_cnt = 0;
+    psvi::DevTable<psvi::KsTile> ks_tiles;
+    psvi::DevTable<psvi::KsSeg> ks_segs;
+    psvi::DevTable<int> ks_off;
+    psvi::DevBuffer<float> ks_slots;
+    psvi::DevBuffer<int> ks_cnt;
+    int n_ks_slots = 0, n_ks_cnt = 0;
     // segmented sample (S > 128): segments, per-workgroup offsets, (row block,
     // pass) reduce blocks, partial slots ([n_fs_slots][128][kFwdRows])
-    std::vector<psvi::FsSeg> h_fs_segs;
-    std::vector<int> h_fs_off;
-    std::vector<psvi::FwdRowBlock> h_fs_rb;
-    psvi::FsSeg* d_fs_segs = nullptr;
-    int* d_fs_off = nullptr;
-    psvi::FwdRowBlock* d_fs_rb = nullptr;
-    float* d_fs_part = nullptr;
-    int n_fswg = 0, n_fs_slots = 0, n_fs_rb = 0;
+    psvi::DevTable<psvi::FsSeg> fs_segs;
+    psvi::DevTable<int> fs_off;
+    psvi::DevTable<psvi::FwdRowBlock> fs_rb;
+    psvi::DevBuffer<float> fs_part;
+    int n_fs_slots = 0;
     // psvi_hvp's sample pair (one eight-wave workgroup per CU): the same units
-    // over 256 workgroups, slots in d_fs_part (sized for both tables)
-    std::vector<psvi::FsSeg> h_fp_segs;
-    std::vector<int> h_fp_off;
-    std::vector<psvi::FwdRowBlock> h_fp_rb;
-    psvi::FsSeg* d_fp_segs = nullptr;
-    int* d_fp_off = nullptr;
-    psvi::FwdRowBlock* d_fp_rb = nullptr;
-    int n_fpwg = 0, n_fp_slots = 0, n_fp_rb = 0;
+    // over 256 workgroups, slots in fs_part (sized for both tables)
+    psvi::DevTable<psvi::FsSeg> fp_segs;
+    psvi::DevTable<int> fp_off;
+    psvi::DevTable<psvi::FwdRowBlock> fp_rb;
+    int n_fp_slots = 0;
+    // workgroups of a segment table: its offset list less the closing entry
+    static int n_wg(const psvi::DevTable<int>& off) { return std::max(0, off.n() - 1); }
+    int n_kwg() const { return n_wg(ks_off); }
+    int n_fswg() const { return n_wg(fs_off); }
+    int n_fpwg() const { return n_wg(fp_off); }
     // net kernel geometry
     int mchunks = 1, mc = 0, net_threads = 256, net_roles = 1;
     bool net_mloop = false;  // full-cov inner objective: the LDS-forced chunks looped in a workgroup
@@ -550,26 +609,25 @@ struct psvi_plan {
     size_t ws_bytes = 0;
     int64_t acc_count = 0;
     // LeNet: plan-owned activation / gradient scratch (kernels_lenet.hip)
-    void* d_lenet_ws = nullptr;
+    psvi::DevBuffer<void> lenet_scratch;
     // mean-field: plan-owned per-(sample, pseudopoint chunk) gradient slots
     // [s_cnt[rank]][mchunks][n_tot]; one writer per element, summed in a fixed
     // order by the update (run-to-run bitwise reproducible, no float atomics)
-    float* d_mf_slots = nullptr;
+    psvi::DevBuffer<float> mf_slots;
     // full-cov with pseudopoint chunks: per-chunk dW slots [mchunks][s_cnt[rank]][n_tot],
     // added in chunk order into g_send (no float atomics)
-    float* d_net_slots = nullptr;
-    // tiled-state inner loops: the packed -> tiled conversion runs on aux_st,
+    psvi::DevBuffer<float> net_slots;
+    // tiled-state inner loops: the packed -> tiled conversion runs on aux.st,
     // forked from / joined to the caller's stream by the two events, behind the
     // first sample and network step (not re-entrant across host threads)
-    hipStream_t aux_st = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    psvi::AuxStream aux;
     // bf16-plane streaming update (tiled S = 128 loops): every eps draw of
     // the loop also as three bf16 planes (EpsPlanes; device copy for the
     // network kernel's fused draw), two plane buffers in the loop workspace
     bool bf_stream = false;
     bool eps_planes_ok = false;  // eps_planes describes this plan's draw (full-cov, world 1)
     psvi::EpsPlanes eps_planes{};
-    psvi::EpsPlanes* d_eps_planes = nullptr;
+    psvi::DevTable<psvi::EpsPlanes> eps_planes_tab;  // eps_planes, for the device
     // psvi_inner_loop_ex(PSVI_LOOP_KEEP): what the last call left in its
     // workspace -- the tiled corr / m / v, the draw at `offset` (eps buffer
     // `ebuf`, and its planes) and the sample x from it -- and for which
@@ -594,6 +652,22 @@ inline int plan_in_dim(const psvi_plan& p) {
 inline unsigned plan_nkl_mask(const psvi_plan& p) {
     return p.family == PSVI_FAMILY_LENET ? 0x1Cu : 0xFFu;
 }
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+// Plan building (plan_tables.cpp: host only, no HIP call): the layout, the
+// shards, the network geometry and every work list of a plan whose family, d,
+// world and rank are set.  Returns 0, or a PSVI_E* code with its message in err.
+int build_plan(psvi_plan& p, std::string& err);
+// the network kernel's chunking and LDS size (kernels_net.hip: its LDS layout)
+size_t net_plan_geometry(psvi_plan& p);
+// psvi_debug_set values read when a plan is built
+struct PlanDebug {
+    int stream_wgs = 0;       // PSVI_DBG_STREAM_WGS: streaming-update workgroups (0 = 256)
+    int stream_rr = 0;        // PSVI_DBG_STREAM_RR, 1: runs dealt round-robin over XCDs (A/B)
+    int stream_cost = -1;     // PSVI_DBG_STREAM_COST, first% + 1000 diag%: tile cost weights (tuning)
+    int upd_chunk_tiles = 0;  // PSVI_DBG_UPD_CHUNK: c-blocks per update chunk (0 = auto)
+    int ks_wgs = 0;           // PSVI_DBG_KSTREAM_WGS: K-split update workgroups (0 = 512)
+};
+extern PlanDebug g_plan_dbg;
 // the full-cov network kernel's x map and band table (kernels_net.hip)
 void net_xmap(const psvi_plan& p, std::vector<uint32_t>& xmap, std::vector<NetBand>& bands);
 // Per-row targets of the loss head: class labels (categorical plans) or fp32

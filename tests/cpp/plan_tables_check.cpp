@@ -1,0 +1,456 @@
+// plan_tables_check.cpp -- stand-alone check of the work lists plan_tables.cpp
+// builds (no GPU use): every plan of a list of shapes is built on the host and
+// its tables are checked against what the kernels assume of them.  Built with
+// the host sanitizers by `make check-tables`; exit status 0 when all hold.
+#include <cstdio>
+#include <map>
+#include <memory>
+#include <set>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "psvi_internal.hpp"
+
+using namespace psvi;
+
+// Stand-in for the network kernel's LDS geometry (kernels_net.hip): one chunk
+// of all M pseudopoints, no LDS demand.  No table depends on it.
+namespace psvi {
+size_t net_plan_geometry(psvi_plan& p) {
+    p.net_roles = 1;
+    p.mchunks = 1;
+    p.mc = p.d.M;
+    p.net_threads = 256;
+    p.net_mloop = false;
+    p.net_lds = 0;
+    return 0;
+}
+}  // namespace psvi
+
+namespace {
+
+int g_failed = 0;
+std::string g_what;  // the plan under check
+
+#define CHECK(cond)                                                                       \
+    do {                                                                                  \
+        if (!(cond)) {                                                                    \
+            if (++g_failed <= 50)                                                         \
+                std::fprintf(stderr, "%s:%d: [%s] %s\n", __FILE__, __LINE__, g_what.c_str(), #cond); \
+            return;                                                                       \
+        }                                                                                 \
+    } while (0)
+
+// the run of workgroup w, as the tables place them on the XCDs
+int xcd_run(int w, int nwg) { return nwg % 8 == 0 ? (w % 8) * (nwg / 8) + w / 8 : w; }
+
+struct Band {
+    int layer, b;
+};
+// the rank's 64-row bands, in run order
+std::vector<Band> rank_bands(const psvi_plan& p) {
+    std::vector<Band> v;
+    for (const ShardRun& run : p.runs[p.rank])
+        for (int b = run.lo / 64; 64 * b < run.hi; ++b) v.push_back(Band{run.layer, b});
+    return v;
+}
+// column of absolute row r of a layer in the rank's x shard (-1: not the rank's)
+int xcol_of(const psvi_plan& p, int layer, int r) {
+    for (const ShardRun& run : p.runs[p.rank])
+        if (run.layer == layer && r >= run.lo && r < run.hi) return run.col + (r - run.lo);
+    return -1;
+}
+
+bool all_fullcov_tables_empty(const psvi_plan& p) {
+    return p.fwd.n() == 0 && p.frb.n() == 0 && p.upd.n() == 0 && p.ufrb.n() == 0 && p.str.n() == 0 &&
+           p.sfrb.n() == 0 && p.ks_tiles.n() == 0 && p.ks_segs.n() == 0 && p.ks_off.n() == 0 &&
+           p.fs_segs.n() == 0 && p.fs_off.n() == 0 && p.fs_rb.n() == 0 && p.fp_segs.n() == 0 &&
+           p.fp_off.n() == 0 && p.fp_rb.n() == 0 && p.n_uslots == 0 && p.n_sslots == 0 &&
+           p.n_ks_slots == 0 && p.n_ks_cnt == 0 && p.n_fs_slots == 0 && p.n_fp_slots == 0 &&
+           p.str_max_ends == 0 && p.upd_tiles == 0 && p.n_kwg() == 0 && p.n_fswg() == 0 &&
+           p.n_fpwg() == 0 && !p.fuse_sample && !p.bf_stream && !p.eps_planes_ok;
+}
+
+// ---------------------------------------------------------- streaming table
+void check_stream(const psvi_plan& p, bool rr) {
+    const bool expect = p.world == 1 && p.d.S <= 128 && p.d.S % 32 == 0;
+    if (!expect) {
+        CHECK(p.str.n() == 0 && p.sfrb.n() == 0 && p.n_sslots == 0 && p.str_max_ends == 0);
+        return;
+    }
+    // the tile list: layer-major, band-major, the diagonal tile last
+    std::vector<uint32_t> lbk;
+    std::vector<int> tband;
+    std::vector<Band> bands;
+    for (int l = 0; l < p.L; ++l)
+        for (int b = 0; b < p.lay[l].nb; ++b) {
+            for (int k = 0; k <= b; ++k) {
+                lbk.push_back((uint32_t)l << 28 | (uint32_t)b << 14 | (uint32_t)k);
+                tband.push_back((int)bands.size());
+            }
+            bands.push_back(Band{l, b});
+        }
+    const int T = (int)lbk.size(), nwg = p.str.n();
+    CHECK(T == p.tiles_total && nwg >= 1 && nwg <= T);
+    // the XCD order undone
+    std::vector<StreamRange> runs(nwg);
+    std::vector<bool> set(nwg, false);
+    for (int w = 0; w < nwg; ++w) {
+        const int i = rr ? w : xcd_run(w, nwg);
+        CHECK(i >= 0 && i < nwg && !set[i]);
+        set[i] = true;
+        runs[i] = p.str.host[w];
+    }
+    // non-empty, disjoint, covering [0, T); slots consecutive, one per band touched
+    std::vector<std::vector<int>> band_slots(bands.size());
+    int t = 0, slot = 0, max_ends = 0;
+    for (const StreamRange& r : runs) {
+        CHECK(r.t0 == t && r.t1 > r.t0 && r.t1 <= T);
+        CHECK(r.lbk0 == lbk[r.t0]);
+        CHECK(r.slot0 == slot);
+        const int touched = tband[r.t1 - 1] - tband[r.t0] + 1;
+        for (int j = 0; j < touched; ++j) band_slots[tband[r.t0] + j].push_back(r.slot0 + j);
+        slot += touched;
+        max_ends = std::max(max_ends, touched);
+        t = r.t1;
+    }
+    CHECK(t == T);
+    CHECK(slot == p.n_sslots);
+    CHECK(max_ends == p.str_max_ends);
+    // band row blocks: nk = the runs touching the band, on consecutive slots
+    CHECK(p.sfrb.n() == (int)bands.size());
+    int nk_sum = 0;
+    for (size_t i = 0; i < bands.size(); ++i) {
+        const FwdRowBlock& rb = p.sfrb.host[i];
+        const std::vector<int>& sl = band_slots[i];
+        CHECK(rb.nk == (int)sl.size() && rb.nk >= 1);
+        for (int j = 0; j < rb.nk; ++j) CHECK(sl[j] == rb.slot0 + j);
+        CHECK(rb.layer == bands[i].layer && rb.r0 == 64 * bands[i].b);
+        CHECK(rb.R == std::min(64, p.lay[rb.layer].n - rb.r0) && rb.R >= 1);
+        CHECK(rb.xcol == xcol_of(p, rb.layer, rb.r0) && rb.s0 == 0);
+        nk_sum += rb.nk;
+    }
+    CHECK(nk_sum == p.n_sslots);
+}
+
+// ------------------------------------------------------------ K-split table
+void check_kstream(const psvi_plan& p) {
+    const int np = (p.d.S + kKsPass - 1) / kKsPass;
+    const std::vector<Band> bands = rank_bands(p);
+    // the rank's tiles, band-major, the diagonal tile last
+    size_t T = 0;
+    for (const Band& bd : bands) T += bd.b + 1;
+    CHECK((size_t)p.ks_tiles.n() == T);
+    {
+        size_t t = 0;
+        for (const Band& bd : bands)
+            for (int k = 0; k <= bd.b; ++k, ++t) {
+                const KsTile& kt = p.ks_tiles.host[t];
+                CHECK(kt.layer == bd.layer && kt.r0 == 64 * bd.b && kt.k == k && kt.diag == (k == bd.b));
+                CHECK(kt.rlo == kt.r0 && kt.rhi == std::min(kt.r0 + 64, p.lay[kt.layer].n));
+                CHECK(kt.xcol + kt.r0 == xcol_of(p, kt.layer, kt.r0));
+            }
+    }
+    if (T == 0) {
+        CHECK(p.ks_segs.n() == 0 && p.ks_off.n() == 0 && p.n_ks_slots == 0 && p.n_ks_cnt == 0);
+        return;
+    }
+    const int nwg = p.n_kwg();
+    CHECK(nwg >= 1 && p.ks_off.n() == nwg + 1);
+    CHECK(p.ks_off.host[0] == 0 && p.ks_off.host[nwg] == p.ks_segs.n());
+    // the XCD order undone: run i's segments
+    std::vector<std::pair<int, int>> run(nwg, {-1, -1});
+    for (int w = 0; w < nwg; ++w) {
+        const int i = xcd_run(w, nwg);
+        CHECK(i >= 0 && i < nwg && run[i].first < 0);
+        CHECK(p.ks_off.host[w] < p.ks_off.host[w + 1]);  // no empty run
+        run[i] = {p.ks_off.host[w], p.ks_off.host[w + 1]};
+    }
+    // every (tile, pass) unit in exactly one segment: the runs in order walk
+    // the units in order
+    std::vector<std::vector<KsSeg>> of_tile(T);
+    int64_t u = 0;
+    for (int i = 0; i < nwg; ++i) {
+        int last_tile = -1;
+        for (int s = run[i].first; s < run[i].second; ++s) {
+            const KsSeg& sg = p.ks_segs.host[s];
+            CHECK(sg.tile >= 0 && (size_t)sg.tile < T && sg.p0 >= 0 && sg.p0 < sg.p1 && sg.p1 <= np);
+            CHECK((int64_t)sg.tile * np + sg.p0 == u);
+            CHECK(sg.tile != last_tile);  // a run's passes of one tile are one segment
+            last_tile = sg.tile;
+            u = (int64_t)sg.tile * np + sg.p1;
+            of_tile[sg.tile].push_back(sg);
+        }
+    }
+    CHECK(u == (int64_t)T * np);
+    // split tiles: a counter, nc contributors ci = 0 .. nc - 1 in pass order on
+    // slots slot .. slot + nc - 1
+    std::set<int> cnts;
+    int slot = 0;
+    for (size_t t = 0; t < T; ++t) {
+        const std::vector<KsSeg>& v = of_tile[t];
+        const int nc = (int)v.size();
+        CHECK(nc >= 1);
+        CHECK((p.ks_tiles.host[t].cnt >= 0) == (nc > 1));
+        if (nc == 1) {
+            CHECK(v[0].slot == -1 && v[0].nc == 1 && v[0].ci == 0 && p.ks_tiles.host[t].cnt == -1);
+            continue;
+        }
+        CHECK(cnts.insert(p.ks_tiles.host[t].cnt).second);
+        for (int j = 0; j < nc; ++j)  // of_tile is in pass order (the walk above)
+            CHECK(v[j].nc == nc && v[j].ci == j && v[j].slot == slot);
+        slot += nc;
+    }
+    CHECK(slot == p.n_ks_slots);
+    CHECK((int)cnts.size() == p.n_ks_cnt);
+    CHECK(cnts.empty() || (*cnts.begin() == 0 && *cnts.rbegin() == p.n_ks_cnt - 1));
+}
+
+// --------------------------------------------------------- segmented tables
+void check_fseg(const psvi_plan& p, int nwg_max, const DevTable<FsSeg>& segs, const DevTable<int>& off,
+                const DevTable<FwdRowBlock>& rbs, int n_slots) {
+    const int np = (p.d.S + kKsPass - 1) / kKsPass;
+    struct Blk {
+        int layer, r0, r1, xcol, nkb;
+    };
+    std::vector<Blk> blks;
+    std::map<std::pair<int, int>, int> blk_of;  // (layer, r0) -> block
+    int64_t U = 0;
+    for (const ShardRun& run : p.runs[p.rank])
+        for (int r0 = run.lo; r0 < run.hi; r0 += kFwdRows) {
+            const int r1 = std::min(r0 + kFwdRows, run.hi);
+            const int kmax = std::max(0, std::min(r1 - 1, p.lay[run.layer].n - 2));
+            blk_of[{run.layer, r0}] = (int)blks.size();
+            blks.push_back(Blk{run.layer, r0, r1, run.col + (r0 - run.lo), (kmax + 63) / 64});
+            U += (int64_t)blks.back().nkb * np;
+        }
+    if (U == 0) {
+        CHECK(segs.n() == 0 && off.n() == 0 && rbs.n() == 0 && n_slots == 0);
+        return;
+    }
+    const int B = (int)blks.size(), nwg = off.n() - 1;
+    CHECK(nwg >= 1 && nwg <= nwg_max && off.host[0] == 0 && off.host[nwg] == segs.n());
+    for (int w = 0; w < nwg; ++w) CHECK(off.host[w] < off.host[w + 1]);
+    // every (row block, pass, 64-column block) unit in exactly one segment
+    std::vector<std::vector<char>> hit((size_t)B * np);
+    for (int b = 0; b < B; ++b)
+        for (int q = 0; q < np; ++q) hit[(size_t)b * np + q].assign(blks[b].nkb, 0);
+    std::vector<std::vector<int>> grp((size_t)B * np);  // the slots of a (row block, pass)
+    std::set<int> slots;
+    for (const FsSeg& sg : segs.host) {
+        const auto it = blk_of.find({sg.layer, sg.r0});
+        CHECK(it != blk_of.end());
+        const Blk& bk = blks[it->second];
+        CHECK(sg.r1 == bk.r1 && sg.pass >= 0 && sg.pass < np && sg.pad == 0);
+        CHECK(sg.k0 % 64 == 0 && sg.k1 % 64 == 0 && sg.k0 >= 0 && sg.k0 < sg.k1 && sg.k1 / 64 <= bk.nkb);
+        std::vector<char>& h = hit[(size_t)it->second * np + sg.pass];
+        for (int kb = sg.k0 / 64; kb < sg.k1 / 64; ++kb) {
+            CHECK(!h[kb]);
+            h[kb] = 1;
+        }
+        CHECK(sg.slot >= 0 && sg.slot < n_slots && slots.insert(sg.slot).second);
+        grp[(size_t)it->second * np + sg.pass].push_back(sg.slot);
+    }
+    for (const auto& h : hit)
+        for (char c : h) CHECK(c);
+    CHECK((int)slots.size() == n_slots);
+    // a workgroup's segments, XCD order undone, continue each other
+    {
+        std::vector<int> w_of(nwg, -1);
+        for (int w = 0; w < nwg; ++w) {
+            const int i = xcd_run(w, nwg);
+            CHECK(i >= 0 && i < nwg && w_of[i] < 0);
+            w_of[i] = w;
+        }
+        int64_t u = 0;
+        std::vector<int64_t> ub(B + 1, 0);
+        for (int b = 0; b < B; ++b) ub[b + 1] = ub[b] + (int64_t)blks[b].nkb * np;
+        for (int i = 0; i < nwg; ++i)
+            for (int s = off.host[w_of[i]]; s < off.host[w_of[i] + 1]; ++s) {
+                const FsSeg& sg = segs.host[s];
+                const int b = blk_of[{sg.layer, sg.r0}];
+                CHECK(ub[b] + (int64_t)sg.pass * blks[b].nkb + sg.k0 / 64 == u);
+                u += (sg.k1 - sg.k0) / 64;
+            }
+        CHECK(u == U);
+    }
+    // reduce blocks: one per (row block, pass), its slots consecutive; nk sums
+    // to the slot count
+    CHECK(rbs.n() == B * np);
+    int nk_sum = 0;
+    for (int b = 0; b < B; ++b)
+        for (int q = 0; q < np; ++q) {
+            const FwdRowBlock& rb = rbs.host[(size_t)b * np + q];
+            auto g = grp[(size_t)b * np + q];
+            std::sort(g.begin(), g.end());
+            CHECK(rb.nk == (int)g.size());
+            for (int j = 0; j < rb.nk; ++j) CHECK(g[j] == rb.slot0 + j);
+            if (rb.nk == 0) CHECK(rb.slot0 == 0);
+            CHECK(rb.layer == blks[b].layer && rb.r0 == blks[b].r0 && rb.R == blks[b].r1 - blks[b].r0);
+            CHECK(rb.xcol == blks[b].xcol && rb.s0 == kKsPass * q);
+            nk_sum += rb.nk;
+        }
+    CHECK(nk_sum == n_slots);
+}
+
+// ------------------------------------------- forward items and update chunks
+void check_fwd(const psvi_plan& p) {
+    int nrb = 0, items = 0;
+    std::set<int> slots;
+    for (const ShardRun& run : p.runs[p.rank])
+        for (int r0 = run.lo; r0 < run.hi; r0 += kFwdRows, ++nrb) {
+            CHECK(nrb < p.frb.n());
+            const FwdRowBlock& rb = p.frb.host[nrb];
+            const int r1 = std::min(r0 + kFwdRows, run.hi);
+            const int kmax = std::max(0, std::min(r1 - 1, p.lay[run.layer].n - 2));
+            CHECK(rb.layer == run.layer && rb.r0 == r0 && rb.R == r1 - r0 && rb.s0 == 0);
+            CHECK(rb.xcol == run.col + (r0 - run.lo) && rb.nk >= 1);
+            // the row block's items tile [0, kmax) on its slots
+            std::vector<std::pair<int, int>> ks;
+            for (const FwdItem& it : p.fwd.host)
+                if (it.layer == run.layer && it.r0 == r0) {
+                    CHECK(it.r1 == r1 && it.xcol == rb.xcol);
+                    CHECK(it.slot >= rb.slot0 && it.slot < rb.slot0 + rb.nk && slots.insert(it.slot).second);
+                    ks.push_back({it.k0, it.k1});
+                }
+            std::sort(ks.begin(), ks.end());
+            CHECK((int)ks.size() == rb.nk);
+            int k = 0;
+            for (const auto& kk : ks) {
+                CHECK(kk.first == k && (kk.second > kk.first || kmax == 0));
+                k = kk.second;
+            }
+            CHECK(k == kmax);
+            items += rb.nk;
+        }
+    CHECK(nrb == p.frb.n() && items == p.fwd.n());
+    for (int i = 0; i + 1 < p.fwd.n(); ++i) {  // longest first
+        const FwdItem &a = p.fwd.host[i], &b = p.fwd.host[i + 1];
+        CHECK(a.k1 - a.k0 >= b.k1 - b.k0);
+    }
+}
+
+void check_upd(const psvi_plan& p) {
+    const std::vector<Band> bands = rank_bands(p);
+    CHECK(p.ufrb.n() == (int)bands.size());
+    CHECK(p.upd.n() % 8 == 0);
+    // the pads: empty chunks and nothing else
+    std::map<std::pair<int, int>, std::vector<UpdChunk>> of_band;
+    for (const UpdChunk& c : p.upd.host) {
+        if (c.k0 == c.k1) {
+            CHECK(c.layer == 0 && c.r0 == 0 && c.k0 == 0 && c.rlo == 0 && c.rhi == 0 && c.xcol == 0 &&
+                  c.diag == 0 && c.slot == -1);
+            continue;
+        }
+        CHECK(c.k0 >= 0 && c.k0 < c.k1);
+        of_band[{c.layer, c.r0}].push_back(c);
+    }
+    CHECK(of_band.size() == bands.size());
+    int slot = 0, tiles = 0;
+    for (size_t i = 0; i < bands.size(); ++i) {
+        const int l = bands[i].layer, b = bands[i].b;
+        auto v = of_band[{l, 64 * b}];
+        std::sort(v.begin(), v.end(), [](const UpdChunk& x, const UpdChunk& y) { return x.k0 < y.k0; });
+        CHECK(!v.empty());
+        // the band's chunks tile c-blocks 0 .. b, the last one diagonal, on
+        // consecutive slots
+        const FwdRowBlock& rb = p.ufrb.host[i];
+        CHECK(rb.slot0 == slot && rb.nk == (int)v.size());
+        int k = 0, ndiag = 0;
+        for (const UpdChunk& c : v) {
+            CHECK(c.k0 == k && c.slot == slot++);
+            CHECK(c.diag == (c.k1 == b + 1));
+            CHECK(c.r0 == 64 * b && c.rlo < c.rhi && c.rhi > 64 * b && c.rlo < 64 * b + 64);
+            CHECK(c.xcol + std::max(64 * b, c.rlo) == xcol_of(p, l, std::max(64 * b, c.rlo)));
+            ndiag += c.diag;
+            k = c.k1;
+        }
+        CHECK(k == b + 1 && ndiag == 1);
+        tiles += b + 1;
+        CHECK(rb.layer == l && rb.r0 == std::max(64 * b, v[0].rlo));
+        CHECK(rb.R == std::min(64 * b + 64, v[0].rhi) - rb.r0 && rb.R >= 1);
+        CHECK(rb.xcol == xcol_of(p, l, rb.r0) && rb.s0 == 0);
+    }
+    CHECK(slot == p.n_uslots);
+    CHECK(tiles == p.upd_tiles);
+}
+
+// ------------------------------------------------------------------- plans
+std::unique_ptr<psvi_plan> make_plan(int family, const std::vector<int>& dims, int S, int M, int world,
+                                     int rank) {
+    std::unique_ptr<psvi_plan> p(new psvi_plan());
+    p->family = family;
+    p->d.n_layers = (int)dims.size() - 1;
+    for (size_t i = 0; i < dims.size(); ++i) p->d.dims[i] = dims[i];
+    p->d.S = S;
+    p->d.M = M;
+    p->d.prior_sd = 1.f;
+    p->world = world;
+    p->rank = rank;
+    std::string err;
+    const int rc = build_plan(*p, err);
+    if (rc) {
+        ++g_failed;
+        std::fprintf(stderr, "[%s] build_plan: %d %s\n", g_what.c_str(), rc, err.c_str());
+        return nullptr;
+    }
+    return p;
+}
+
+int g_plans = 0;
+
+void check_fullcov(const std::vector<int>& dims, int S, int world, int rank) {
+    g_what = "fullcov";
+    for (int d : dims) g_what += "-" + std::to_string(d);
+    g_what += " S=" + std::to_string(S) + " world=" + std::to_string(world) + " rank=" + std::to_string(rank) +
+              " dbg=" + std::to_string(g_plan_dbg.stream_wgs) + "/" + std::to_string(g_plan_dbg.ks_wgs);
+    const std::unique_ptr<psvi_plan> p = make_plan(PSVI_FAMILY_FULLCOV, dims, S, 100, world, rank);
+    if (!p) return;
+    ++g_plans;
+    check_stream(*p, g_plan_dbg.stream_rr != 0);
+    check_kstream(*p);
+    check_fseg(*p, 512, p->fs_segs, p->fs_off, p->fs_rb, p->n_fs_slots);
+    check_fseg(*p, 256, p->fp_segs, p->fp_off, p->fp_rb, p->n_fp_slots);
+    check_fwd(*p);
+    check_upd(*p);
+}
+
+void check_empty(int family, const char* name) {
+    g_what = name;
+    const std::unique_ptr<psvi_plan> p = make_plan(family, {64, 40, 40, 2}, 128, 100, 1, 0);
+    if (!p) return;
+    ++g_plans;
+    CHECK(all_fullcov_tables_empty(*p));
+}
+
+}  // namespace
+
+int main() {
+    const std::vector<int> fn2{64, 40, 40, 2};
+    for (int S : {128, 32, 96, 100, 130, 256, 1024}) check_fullcov(fn2, S, 1, 0);
+    for (int r = 0; r < 8; ++r) check_fullcov(fn2, 1024, 8, r);
+    for (int r = 0; r < 2; ++r) check_fullcov(fn2, 128, 2, r);
+    // one layer: n = 2, n = 6 (one tile), n = 64 exactly, n = 65 (a one-row second band)
+    for (int S : {128, 256})
+        for (const std::vector<int>& dims : {std::vector<int>{1, 1}, {2, 2}, {7, 8}, {12, 5}})
+            check_fullcov(dims, S, 1, 0);
+    check_fullcov({3, 5, 2}, 64, 1, 0);
+    check_empty(PSVI_FAMILY_MEANFIELD, "mean-field");
+    check_empty(PSVI_FAMILY_LENET, "lenet");
+    // workgroup counts that are no multiple of 8
+    g_plan_dbg.stream_wgs = 64;
+    check_fullcov(fn2, 128, 1, 0);
+    g_plan_dbg.stream_wgs = 100;
+    check_fullcov(fn2, 128, 1, 0);
+    g_plan_dbg.stream_wgs = 0;
+    g_plan_dbg.ks_wgs = 100;
+    check_fullcov(fn2, 128, 1, 0);
+    g_plan_dbg.ks_wgs = 0;
+    if (g_failed) {
+        std::fprintf(stderr, "plan_tables_check: %d failed checks\n", g_failed);
+        return 1;
+    }
+    std::printf("plan_tables_check: %d plans ok\n", g_plans);
+    return 0;
+}
