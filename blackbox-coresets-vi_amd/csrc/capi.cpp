@@ -308,23 +308,30 @@ int psvi_plan_create_lik(int32_t family, const psvi_net_desc* d, int32_t world, 
         return psvi_plan_create(family, d, world, rank, out);
     if (!out) return fail(PSVI_EINVAL, "null out");
     *out = nullptr;
-    if (lik->kind != PSVI_LIK_GAUSSIAN) return fail(PSVI_EINVAL, "unknown likelihood kind");
+    if (lik->kind != PSVI_LIK_GAUSSIAN && lik->kind != PSVI_LIK_BERNOULLI)
+        return fail(PSVI_EINVAL, "unknown likelihood kind");
+    const bool gauss = lik->kind == PSVI_LIK_GAUSSIAN;
     if (family != PSVI_FAMILY_MEANFIELD && family != PSVI_FAMILY_FULLCOV &&
         family != PSVI_FAMILY_LENET)
         return fail(PSVI_EINVAL, "unknown family");
     if (family != PSVI_FAMILY_MEANFIELD)
-        return fail(PSVI_EUNSUP, "the Gaussian likelihood runs mean-field plans only");
+        return fail(PSVI_EUNSUP, gauss ? "the Gaussian likelihood runs mean-field plans only"
+                                       : "the Bernoulli likelihood runs mean-field plans only");
     if (int rc = check_desc(d)) return rc;
     if (world < 1 || world > kMaxWorld || rank < 0 || rank >= world)
         return fail(PSVI_EINVAL, "world/rank out of range (world <= 8)");
-    if (world != 1) return fail(PSVI_EUNSUP, "the Gaussian likelihood needs world == 1");
+    if (world != 1)
+        return fail(PSVI_EUNSUP, gauss ? "the Gaussian likelihood needs world == 1"
+                                       : "the Bernoulli likelihood needs world == 1");
     if (d->dims[d->n_layers] != 1)
-        return fail(PSVI_EINVAL, "the Gaussian likelihood has one output (dims[n_layers] == 1)");
-    if (!(lik->tau > 0.f) || !std::isfinite(lik->tau))
+        return fail(PSVI_EINVAL,
+                    gauss ? "the Gaussian likelihood has one output (dims[n_layers] == 1)"
+                          : "the Bernoulli likelihood has one output (dims[n_layers] == 1)");
+    if (gauss && (!(lik->tau > 0.f) || !std::isfinite(lik->tau)))
         return fail(PSVI_EINVAL, "the Gaussian precision tau must be positive and finite");
     if (int rc = psvi_plan_create(family, d, world, rank, out)) return rc;
-    (*out)->lik = PSVI_LIK_GAUSSIAN;
-    (*out)->lik_tau = lik->tau;
+    (*out)->lik = lik->kind;
+    if (gauss) (*out)->lik_tau = lik->tau;
     return 0;
 }
 
@@ -500,6 +507,13 @@ static int check_plan(const psvi_plan* p, unsigned families = ~0u, const char* w
     return 0;
 }
 static const char kNotMf[] = "not a mean-field plan", kNotFc[] = "not a full-cov plan";
+
+// Bernoulli plans run the inner objective, psvi_sampled_kl_grad and
+// psvi_row_loglik only.
+static int refuse_bernoulli(const psvi_plan* p, const char* what) {
+    if (p && p->lik == PSVI_LIK_BERNOULLI) return fail(PSVI_EUNSUP, what);
+    return 0;
+}
 
 // The Adam hyper-parameters of an entry point that steps (required; the
 // gradient-only calls pass false and may leave hp null).
@@ -1006,6 +1020,9 @@ static int outer_impl(const psvi_plan* p, int32_t n_pseudo, const float* x_all,
                       int ablated = 0, float* grad_z = nullptr) {
     drop_resident(p);
     if (int rc = check_plan(p)) return rc;
+    if (int rc = refuse_bernoulli(p, "the outer objective has no Bernoulli-likelihood form "
+                                     "(psvi_row_loglik + psvi_select_weight_grad)"))
+        return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "the outer objective needs world == 1");
     if (p->d.S < 1) return fail(PSVI_EINVAL, "S must be >= 1");
     if (p->d.S > 2048) return fail(PSVI_EUNSUP, "the outer objective supports S <= 2048");
@@ -1152,6 +1169,8 @@ int psvi_evaluate(const psvi_plan* p, int32_t n_pseudo, const float* x_all, cons
     drop_resident(p);
     if (int rc = check_plan(p)) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "evaluate needs world == 1");
+    if (int rc = refuse_bernoulli(p, "a Bernoulli-likelihood plan predicts from psvi_row_loglik"))
+        return rc;
     if (p->lik != PSVI_LIK_CATEGORICAL)
         return fail(PSVI_ESTATE, "a Gaussian-likelihood plan evaluates with "
                                  "psvi_evaluate_regression");
@@ -1193,6 +1212,8 @@ int psvi_evaluate_regression(const psvi_plan* p, int32_t n_pseudo, const float* 
                              void* stream) {
     drop_resident(p);
     if (int rc = check_plan(p)) return rc;
+    if (int rc = refuse_bernoulli(p, "a Bernoulli-likelihood plan predicts from psvi_row_loglik"))
+        return rc;
     if (p->lik != PSVI_LIK_GAUSSIAN)
         return fail(PSVI_ESTATE, "psvi_evaluate_regression needs a Gaussian-likelihood plan");
     if (p->d.S < 2) return fail(PSVI_EINVAL, "evaluate needs S > 1 (psvi_classes.py:2229)");
@@ -1217,6 +1238,62 @@ int psvi_evaluate_regression(const psvi_plan* p, int32_t n_pseudo, const float* 
     return 0;
 }
 
+int psvi_sampled_kl_grad(const psvi_plan* p, const float* eps, const float* params,
+                         double* nkl_out, float* grad_out, void* stream) {
+    drop_resident(p);
+    if (int rc = check_plan(p, 1u << PSVI_FAMILY_MEANFIELD, kNotMf)) return rc;
+    if (p->world != 1) return fail(PSVI_EUNSUP, "the sampled KL term needs world == 1");
+    if (!eps || !params || (!nkl_out && !grad_out)) return fail(PSVI_EINVAL, "null pointer");
+    HIP_TRY(launch_mf_sampled_kl(*p, eps, params, nkl_out, grad_out, as_stream(stream)));
+    return 0;
+}
+
+int psvi_row_loglik(const psvi_plan* p, const float* x_all, const int32_t* z_all,
+                    const float* eps, const float* params, float* ll_out, float* logits_out,
+                    double* nkl_out, void* stream) {
+    drop_resident(p);
+    if (int rc = check_plan(p)) return rc;
+    if (p->lik != PSVI_LIK_BERNOULLI)
+        return fail(PSVI_ESTATE, "psvi_row_loglik needs a Bernoulli-likelihood plan");
+    if (p->d.S > 2048) return fail(PSVI_EUNSUP, "psvi_row_loglik supports S <= 2048");
+    if (!x_all || !z_all || !eps || !params || !ll_out) return fail(PSVI_EINVAL, "null pointer");
+    hipStream_t st = as_stream(stream);
+    // the forward pass of the outer objective: every row's -NLL, the raw
+    // output of the rows past n_pseudo = 0.  The forward reads no row weight:
+    // its weight slots load the first M floats of x_all.
+    NetOuter fw{1, 0, ll_out, nullptr, nullptr, nullptr, logits_out, nullptr};
+    fw.loglik = true;
+    NetLaunch n = net_rows(x_all, Targets::labels(z_all), x_all, nullptr);
+    n.params = params; n.eps = eps; n.outer = &fw;
+    HIP_TRY(launch_net(*p, n, st));
+    if (nkl_out) HIP_TRY(launch_mf_sampled_kl(*p, eps, params, nkl_out, nullptr, st));
+    return 0;
+}
+
+int psvi_select_scores(int32_t S, int32_t n_core, int32_t n_data, const float* ll,
+                       const double* nkl, const float* w_core, double sum_scaling, float* W_out,
+                       float* corr_out, float* corecorr_out, double* result_out, void* stream) {
+    if (S < 2 || n_core < 0 || n_data < 1) return fail(PSVI_EINVAL, "bad selection shape");
+    if (S > 2048) return fail(PSVI_EUNSUP, "the selection scores support S <= 2048");
+    if (!ll || !nkl || !W_out || !corr_out || !result_out ||
+        (n_core > 0 && (!w_core || !corecorr_out)))
+        return fail(PSVI_EINVAL, "null pointer");
+    HIP_TRY(launch_select_scores(S, n_core, n_data, ll, nkl, w_core, sum_scaling, W_out, corr_out,
+                                 corecorr_out, result_out, as_stream(stream)));
+    return 0;
+}
+
+int psvi_select_weight_grad(int32_t S, int32_t n_core, int32_t n_data, const float* ll,
+                            const double* nkl, const float* w_core, double N, double* loss_out,
+                            float* grad_w, void* stream) {
+    if (S < 2 || n_core < 1 || n_data < 1) return fail(PSVI_EINVAL, "bad selection shape");
+    if (S > 2048) return fail(PSVI_EUNSUP, "the weight objective supports S <= 2048");
+    if (!ll || !nkl || !w_core || !loss_out || !grad_w) return fail(PSVI_EINVAL, "null pointer");
+    HIP_TRY(launch_select_weight_grad(S, n_core, n_data, ll, nkl, w_core, N, loss_out, grad_w,
+                                      as_stream(stream)));
+    return 0;
+}
+
 int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,
@@ -1231,6 +1308,7 @@ int psvi_hvp_ex(const psvi_plan* p, const float* u, const int32_t* z, const floa
                 size_t ws_bytes, void* stream) {
     drop_resident(p);
     if (int rc = check_plan(p)) return rc;
+    if (int rc = refuse_bernoulli(p, "the R-op kernel has no Bernoulli head")) return rc;
     if (p->world != 1) return fail(PSVI_ESTATE, "psvi_hvp needs world == 1");
     if (!u || !z || !w || !eps || !params || !vec || !hv_out)
         return fail(PSVI_EINVAL, "null pointer");

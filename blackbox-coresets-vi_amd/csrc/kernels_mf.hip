@@ -315,6 +315,109 @@ hipError_t launch_mf_update(const psvi_plan& p, const MfUpdate& r, hipStream_t s
     return hipGetLastError();
 }
 
+// ------------------------------------------------- sampled KL (sparse-BBVI)
+// VIMixin.sampled_nkl (neural_net.py:110-115) of every layer, per sample, and
+// the gradient of -sum_s nkl_s (the reference's elbo, psvi/inference/utils.py:
+// 85-91, subtracts the per-sample term; autograd gives the sums below):
+//   nkl_s = sum_i [-theta_si^2 / (2 s0^2) - log s0 + log sigma_i + eps_si^2 / 2]
+//   d / d mu_i  = sum_s theta_si / s0^2
+//   d / d rho_i = (sum_s theta_si eps_si / s0^2 - S / sigma_i) sigmoid(rho_i)
+// theta_si = mu_i + sigma_i eps_si, sigma = softplus(rho).
+struct MfNklArgs {
+    int L, S, n_tot;
+    int woff[kMaxL + 1];
+    int64_t poff[kMaxL], eoff[kMaxL];
+    int n[kMaxL], nw[kMaxL], dout[kMaxL];
+    float inv_s0sq;
+    double log_s0;
+    const float* params;
+    const float* eps;
+    double* nkl;   // [S]
+    float* grad;   // [P], added into
+};
+
+// eps of sample s, element idx of layer l (weights [S][nw], then biases [S][dout])
+__device__ __forceinline__ float mf_eps_at(const MfNklArgs& a, int l, int s, int idx) {
+    const int nw = a.nw[l];
+    return idx < nw ? a.eps[a.eoff[l] + (int64_t)s * nw + idx]
+                    : a.eps[a.eoff[l] + (int64_t)a.S * nw + (int64_t)s * a.dout[l] + (idx - nw)];
+}
+
+// one workgroup per sample; thread t sums elements t, t + 256, ... of every
+// layer in order, the 256 partials meet in a fixed tree
+__global__ __launch_bounds__(256) void mf_nkl_kernel(MfNklArgs a) {
+    __shared__ double red[256];
+    const int s = blockIdx.x;
+    double acc = 0.0;
+    for (int l = 0; l < a.L; ++l) {
+        const int n = a.n[l];
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const float e = mf_eps_at(a, l, s, i);
+            const float mu = a.params[a.poff[l] + i], rho = a.params[a.poff[l] + n + i];
+            const float sp = softplus_f(rho);
+            const float th = mu + e * sp;
+            acc += -0.5 * (double)th * th * a.inv_s0sq + (double)logf(sp) + 0.5 * (double)e * e;
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.nkl[s] = red[0] - (double)a.n_tot * a.log_s0;
+}
+
+// one thread per element: the sums over s in sample order, one writer per slot
+__global__ __launch_bounds__(256) void mf_nkl_grad_kernel(MfNklArgs a) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.n_tot) return;
+    int l = 0;
+    while (l + 1 < a.L && e >= a.woff[l + 1]) ++l;
+    const int idx = e - a.woff[l];
+    const int64_t pmu = a.poff[l] + idx, prho = pmu + a.n[l];
+    const float mu = a.params[pmu], rho = a.params[prho];
+    const float sp = softplus_f(rho);
+    double gm = 0.0, gs = 0.0;
+    for (int s = 0; s < a.S; ++s) {
+        const float ev = mf_eps_at(a, l, s, idx);
+        const float th = mu + ev * sp;
+        gm += (double)th;
+        gs += (double)th * ev;
+    }
+    a.grad[pmu] += (float)(gm * a.inv_s0sq);
+    a.grad[prho] += (float)((gs * a.inv_s0sq - (double)a.S / sp) * sigmoid_f(rho));
+}
+
+hipError_t launch_mf_sampled_kl(const psvi_plan& p, const float* eps, const float* params,
+                                double* nkl_out, float* grad_out, hipStream_t st) {
+    if (p.family != PSVI_FAMILY_MEANFIELD || p.world != 1) return hipErrorInvalidValue;
+    MfNklArgs a{};
+    a.L = p.L;
+    a.S = p.d.S;
+    a.n_tot = p.n_tot;
+    for (int l = 0; l < p.L; ++l) {
+        a.woff[l] = p.lay[l].woff;
+        a.poff[l] = p.lay[l].poff;
+        a.eoff[l] = p.lay[l].eoff;
+        a.n[l] = p.lay[l].n;
+        a.nw[l] = p.lay[l].din * p.lay[l].dout;
+        a.dout[l] = p.lay[l].dout;
+    }
+    a.woff[p.L] = p.n_tot;
+    const double s0 = p.d.prior_sd;
+    a.inv_s0sq = (float)(1.0 / (s0 * s0));
+    a.log_s0 = std::log(s0);
+    a.params = params;
+    a.eps = eps;
+    a.nkl = nkl_out;
+    a.grad = grad_out;
+    if (nkl_out) hipLaunchKernelGGL(mf_nkl_kernel, dim3(p.d.S), dim3(256), 0, st, a);
+    if (grad_out)
+        hipLaunchKernelGGL(mf_nkl_grad_kernel, dim3((p.n_tot + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------ generic Adam
 __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict__ p,
                                                    const float* __restrict__ g,

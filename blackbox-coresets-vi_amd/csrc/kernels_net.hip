@@ -134,7 +134,30 @@ struct NetArgs {
     // dz_part (outer backward, nullable): [S][n_pseudo] d loss_s / d z_m
     float lik_tau, lik_c;
     float* dz_part;
+    // Bernoulli likelihood (LIK = PSVI_LIK_BERNOULLI: one output f, z holds class
+    // ids in {0, 1}): NLL = softplus(f) - z f.  The outer forward writes
+    // row_sign * NLL into nll_rows (-1: the row log-likelihoods of
+    // psvi_row_loglik) and the raw output f of the data rows into prob_rows.
+    float row_sign;
 };
+
+// The one-output heads: NLL of output f against the row's target slot zs
+// (Gaussian: the fp32 target; Bernoulli: the class id's bits) and d NLL / d f.
+template <int LIK>
+__device__ __forceinline__ void lik1_head(const NetArgs& a, float f, float zs, float& nll, float& dnll) {
+    if constexpr (LIK == PSVI_LIK_GAUSSIAN) {
+        const float d = f - zs;
+        nll = 0.5f * a.lik_tau * d * d + a.lik_c;
+        dnll = a.lik_tau * d;
+    } else {
+        // overflow-safe softplus: max(f, 0) + log1p(exp(-|f|))
+        const float zf = (float)__float_as_int(zs);
+        const float e = expf(-fabsf(f));
+        nll = fmaxf(f, 0.f) - zf * f + log1pf(e);
+        // sigmoid(f) = 1 / (1 + e) for f >= 0, e / (1 + e) otherwise
+        dnll = (f >= 0.f ? 1.f : e) / (1.f + e) - zf;
+    }
+}
 
 // ---- LDS carve (float offsets, row strides) of the network kernel.  Row
 // strides are 4 x odd (== 8 mod 16): a 16-lane float4 read along k (rows i16
@@ -513,13 +536,14 @@ __device__ __forceinline__ int64_t fc_addr(const NetArgs& a, int nsrc, const int
 // instantiation has straight-line x loads: with the run-table path in the
 // same kernel the register allocator shares registers across the two paths
 // and the waitcnt pass then serialises the u and x loads (seen in the ISA).
-// LIK: the loss head (PSVI_LIK_CATEGORICAL; PSVI_LIK_GAUSSIAN: one output,
-// mean-field only -- its own instantiation, the categorical ones are unchanged)
+// LIK: the loss head (PSVI_LIK_CATEGORICAL; PSVI_LIK_GAUSSIAN and
+// PSVI_LIK_BERNOULLI: one output, mean-field only -- their own instantiations,
+// the categorical ones are unchanged)
 template <int FAM, bool MSRC, bool VEC = false, bool MLOOP = false, int GEO = 0,
           int LIK = PSVI_LIK_CATEGORICAL>
 __global__ __launch_bounds__(512) void net_kernel(NetArgs a) {
     static_assert(LIK == PSVI_LIK_CATEGORICAL || (FAM == PSVI_FAMILY_MEANFIELD && GEO == 0),
-                  "the Gaussian head: mean-field, run-time geometry");
+                  "the one-output heads: mean-field, run-time geometry");
     using Geo = NetGeo<GEO>;
     const Geo g(a);
     constexpr int kUL = Geo::kUnroll;  // layer loops: fully unrolled for a fixed geometry
@@ -1040,19 +1064,21 @@ chunk_top:// a backward jump only when MLOOP (no loop at all in the other instan
             float* Xn = (head ? sm + g.ldl() : sm + g.lx(l + 1)) + r0 * (head ? g.lddl() : g.ldx(l + 1));
             const float* Bv = sm + g.lb(l);
             const int ldn = head ? g.lddl() : g.ldx(l + 1), jend = min((dout + 15) & ~15, ldn);
-            if (LIK == PSVI_LIK_GAUSSIAN && head && fuse_head) {
-                // Gaussian head (C = 1: the output f on lane j = 0 of the row's
-                // 16): NLL = tau / 2 (f - z)^2 + c, dlogit = w tau (f - z)
+            if (LIK != PSVI_LIK_CATEGORICAL && head && fuse_head) {
+                // one-output head (C = 1: the output f on lane j = 0 of the row's
+                // 16).  Gaussian: NLL = tau / 2 (f - z)^2 + c, dlogit = w tau (f - z);
+                // Bernoulli: NLL = softplus(f) - z f, dlogit = w (sigmoid(f) - z)
                 auto epi = [&](int m, int j, floatx4 v, int rot) {
                     const float b = Bv[0];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = m + ((r + rot) & 3), rg = r0 + row;
-                        const float d = v[r] + b - zw[rg];
+                        float nll, dnll;
+                        lik1_head<LIK>(a, v[r] + b, zw[rg], nll, dnll);
                         const float wr = zw[Mp + rg];
                         const bool ok = rg < mcnt && j == 0;
-                        if (j < jend) Xn[row * ldn + j] = ok ? wr * (a.lik_tau * d) : 0.f;
-                        if (ok) part += wr * (0.5f * a.lik_tau * d * d + a.lik_c);
+                        if (j < jend) Xn[row * ldn + j] = ok ? wr * dnll : 0.f;
+                        if (ok) part += wr * nll;
                     }
                 };
                 row_gemm<true, true>(dout, din, X, g.ldx(l), sm + g.lw(l), g.ldw(l), epi);
@@ -1099,28 +1125,30 @@ chunk_top:// a backward jump only when MLOOP (no loop at all in the other instan
         }
         // ---- loss head on VALU (C > 16, the outer objective): lanes 0..15
         // take the tile's rows, logits -> weighted NLL, dlogits in place
-        if (LIK == PSVI_LIK_GAUSSIAN && !fuse_head && !(a.abl & 4) && lane < 16 &&
+        if (LIK != PSVI_LIK_CATEGORICAL && !fuse_head && !(a.abl & 4) && lane < 16 &&
             r0 + lane < mcnt) {
-            // Gaussian head on VALU (the outer objective): the output f in column 0
+            // one-output head on VALU (the outer objective): the output f in column 0
             const int m = r0 + lane, mg = m0 + m;
             float* row = sm + g.ldl() + m * g.lddl();
-            const float f = row[0], d = f - zw[m];
-            const float nll = 0.5f * a.lik_tau * d * d + a.lik_c;
+            const float f = row[0];
+            float nll, dnll;
+            lik1_head<LIK>(a, f, zw[m], nll, dnll);
             if (a.outer == 1) {
-                a.nll_rows[(size_t)s * a.M + mg] = nll;
+                a.nll_rows[(size_t)s * a.M + mg] =
+                    LIK == PSVI_LIK_BERNOULLI ? a.row_sign * nll : nll;
                 // evaluate: the raw output of the data rows [S][M - n_pseudo][1]
                 if (a.prob_rows && mg >= a.n_pseudo)
                     a.prob_rows[(size_t)s * (a.M - a.n_pseudo) + mg - a.n_pseudo] = f;
             } else {
                 const float wm = zw[Mp + m] * (mg < a.n_pseudo ? cp : cd);
-                const float dl = wm * (a.lik_tau * d);
+                const float dl = wm * dnll;
                 part += wm * nll;
                 row[0] = dl;
                 // d NLL / d z = -d NLL / d f (the role that owns layer 0 writes)
                 if (a.outer == 2 && a.dz_part && own_lo == 0 && mg < a.n_pseudo)
                     a.dz_part[(size_t)s * a.n_pseudo + mg] = -dl;
             }
-        } else if (LIK != PSVI_LIK_GAUSSIAN && !fuse_head && !(a.abl & 4) && lane < 16 &&
+        } else if (LIK == PSVI_LIK_CATEGORICAL && !fuse_head && !(a.abl & 4) && lane < 16 &&
                    r0 + lane < mcnt) {
             const int m = r0 + lane;
             const int ldl = g.lddl();
@@ -1472,9 +1500,9 @@ uint16_t* g_net_draw_planes = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_NET_DRAW_
 int g_net_draw_role1 = 17;  // psvi_debug_set(PSVI_DBG_NET_DRAW_ROLE1, n): role 1's 32nds of the fused draw
 int g_net_draw_spare_off = 0;  // psvi_debug_set(PSVI_DBG_NET_DRAW_SPARE_OFF, 1): the whole draw at the end (A/B)
 
-// Every net_kernel instantiation, once.  Mean-field plans take the Gaussian
-// or the categorical head; full-cov plans are keyed by (several source ranks,
-// float4 x loads, pseudopoint chunks looped in the workgroup, fixed fn2
+// Every net_kernel instantiation, once.  Mean-field plans take the Gaussian,
+// the Bernoulli or the categorical head; full-cov plans are keyed by (several
+// source ranks, float4 x loads, pseudopoint chunks looped in the workgroup, fixed fn2
 // geometry), and the fn2 geometry comes only with float4 loads (NetGeo 1 for
 // one source, 2 for several) and the chunk loop only with float4 loads.
 struct NetVariant {
@@ -1487,6 +1515,8 @@ static const NetVariant kNetVariants[] = {
      net_kernel<PSVI_FAMILY_MEANFIELD, false>},
     {PSVI_FAMILY_MEANFIELD, PSVI_LIK_GAUSSIAN, false, false, false, false,
      net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_GAUSSIAN>},
+    {PSVI_FAMILY_MEANFIELD, PSVI_LIK_BERNOULLI, false, false, false, false,
+     net_kernel<PSVI_FAMILY_MEANFIELD, false, false, false, 0, PSVI_LIK_BERNOULLI>},
     {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, false, false, false, false,
      net_kernel<PSVI_FAMILY_FULLCOV, false>},
     {PSVI_FAMILY_FULLCOV, PSVI_LIK_CATEGORICAL, true, false, false, false,
@@ -1516,7 +1546,7 @@ static const NetVariant kNetVariants[] = {
 static const NetVariant* net_variant(int family, int lik, bool multi, bool vec, bool loop, bool fn2) {
     if (family == PSVI_FAMILY_MEANFIELD) {
         multi = vec = loop = fn2 = false;
-        if (lik != PSVI_LIK_GAUSSIAN) lik = PSVI_LIK_CATEGORICAL;
+        if (lik != PSVI_LIK_GAUSSIAN && lik != PSVI_LIK_BERNOULLI) lik = PSVI_LIK_CATEGORICAL;
     } else {
         family = PSVI_FAMILY_FULLCOV;
         lik = PSVI_LIK_CATEGORICAL;
@@ -1585,6 +1615,14 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
         a.lik_tau = p.lik_tau;
         a.lik_c = (float)(0.5 * std::log(2.0 * 3.14159265358979323846 / (double)p.lik_tau));
     } else if (a.dz_part) {
+        return hipErrorInvalidValue;
+    }
+    a.row_sign = 1.f;
+    if (p.lik == PSVI_LIK_BERNOULLI) {
+        if (p.family != PSVI_FAMILY_MEANFIELD || p.lay[p.L - 1].dout != 1)
+            return hipErrorInvalidValue;
+        if (outer && outer->loglik) a.row_sign = -1.f;
+    } else if (outer && outer->loglik) {
         return hipErrorInvalidValue;
     }
     a.inv_s0sq = 1.f / (p.d.prior_sd * p.d.prior_sd);

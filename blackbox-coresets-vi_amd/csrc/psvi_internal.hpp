@@ -444,6 +444,7 @@ struct NetOuter {
     float* prob_rows;     // mode 1, nullable: [S][M - n_pseudo][C] softmax of the data rows
                           // (Gaussian plans: the raw output f, C = 1)
     float* dz_part;       // mode 2, nullable, Gaussian plans: [S][n_pseudo] d loss_s / d z_m
+    bool loglik = false;  // mode 1, Bernoulli plans: nll_rows receives -NLL (psvi_row_loglik)
 };
 
 // ------------------------------------------------------ plan-owned memory
@@ -783,6 +784,18 @@ AdamC make_adam(const psvi_adam_hp* hp);
 hipError_t launch_adam_adjoint(int64_t n, const float* lt, float* lm, float* lv, const float* m,
                                const float* v, const float* g, float* lg,
                                const psvi_adam_hp* hp, hipStream_t st);
+// sampled KL of a mean-field plan (kernels_mf.hip): nkl_out [S] doubles
+// (nullable), grad_out [P] += d(-sum_s nkl_s) / d params (nullable)
+hipError_t launch_mf_sampled_kl(const psvi_plan& p, const float* eps, const float* params,
+                                double* nkl_out, float* grad_out, hipStream_t st);
+// sparse black-box VI (kernels_select.hip): selection scores and the weight
+// objective from ll [S][Nu + B] and nkl [S]
+hipError_t launch_select_scores(int S, int Nu, int B, const float* ll, const double* nkl,
+                                const float* w, double sum_scaling, float* W_out, float* corr,
+                                float* corecorr, double* result, hipStream_t st);
+hipError_t launch_select_weight_grad(int S, int Nu, int B, const float* ll, const double* nkl,
+                                     const float* w, double N, double* loss, float* grad_w,
+                                     hipStream_t st);
 // outer objective (kernels_outer.hip)
 hipError_t launch_outer_stats(const psvi_plan& p, const float* params, const float* eps,
                               const float* x, double* stats, hipStream_t st);

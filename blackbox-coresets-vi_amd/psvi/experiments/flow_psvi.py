@@ -1,6 +1,6 @@
 """flow_psvi.experiment_driver (psvi/experiments/flow_psvi.py:357-454) over the
-methods the HIP path runs: the PSVI variants' run_psvi and the MFVI
-baselines.  No CLI: method_args is the reference's dict of parsed arguments.
+methods the HIP path runs: the PSVI variants' run_psvi, the MFVI baselines
+and the sparse black-box VI coreset construction.  No CLI: method_args is the reference's dict of parsed arguments.
 
 Multi-GPU (one process per GPU): every rank calls
 experiment_driver with the same arguments and its ``world`` / ``rank`` (or
@@ -12,7 +12,8 @@ every rank holds the same u, v and network after every step); the MFVI
 baselines have no sample-sharded form and run whole on every rank.  Rank 0
 alone writes the results files."""
 from ..inference import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV, PSVILearnV,
-                         PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, run_mfvi, run_mfvi_subset)
+                         PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, run_mfvi, run_mfvi_subset,
+                         run_sparsevi_with_bb_elbo)
 from .experiments_utils import read_dataset, rec_dd, write_to_files
 
 
@@ -24,8 +25,8 @@ def _psvi(cls):
 # classes run on the HIP path (psvi.inference.PSVI_regressor,
 # PSVILearnV_regressor, PSVIAV_regressor), but the reference's regression
 # datasets are remote downloads and read_dataset returns no y_mean / y_std --
-# and the selection baselines (sparsevi, giga, opsvi, random, sparsebbvi),
-# which are not on the HIP path
+# and the selection baselines (sparsevi, giga, opsvi, random), which are not
+# on the HIP path.  sparsebbvi runs on it (Bernoulli plans, one output).
 inf_dict = {
     "psvi": _psvi(PSVI),
     "psvi_ablated": _psvi(PSVI_Ablated),
@@ -38,6 +39,7 @@ inf_dict = {
     "psvi_alpha_fixed_u": _psvi(PSVIAFixedU),
     "mfvi": run_mfvi,
     "mfvi_subset": run_mfvi_subset,
+    "sparsebbvi": run_sparsevi_with_bb_elbo,
 }
 
 
@@ -89,7 +91,9 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
                         n_hidden=method_args.get("n_hidden", 40),
                         n_layers=method_args.get("n_layers", 1),
                         train_dataset=train_dataset, test_dataset=test_dataset, dnm=dnm, nc=nc,
-                        learn_z=method_args.get("learn_z", False))
+                        learn_z=method_args.get("learn_z", False),
+                        **(dict(outer_it=method_args["outer_it"], scatterplot_coreset=False)
+                           if nm_alg == "sparsebbvi" else {}))
     if write and rank == 0:
         return write_to_files(results, method_args.get("fnm", "results"),
                               method_args.get("results_folder", "results"))

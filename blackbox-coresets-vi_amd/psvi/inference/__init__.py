@@ -3,3 +3,4 @@ from .psvi_classes import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV,  # 
                            PSVILearnV, PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, HipInnerELBO,
                            PSVI_regressor, PSVILearnV_regressor, PSVIAV_regressor)
 from .baselines import run_mfvi, run_mfvi_subset  # noqa: F401,E402
+from .sparsebbvi import run_sparsevi_with_bb_elbo  # noqa: F401,E402

@@ -22,6 +22,7 @@ ADAM_HYPERGRAD = 1
 ADAM_TORCH = 2
 LIK_CATEGORICAL = 0
 LIK_GAUSSIAN = 1
+LIK_BERNOULLI = 2
 
 Q_PARAM_COUNT = 1
 Q_EPS_COUNT = 2
@@ -119,6 +120,12 @@ SIGNATURES = {
     "psvi_evaluate_regression": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, ctypes.c_float,
                                         ctypes.c_float, _P, _P, _P, _SZ, _P]),
     "psvi_evaluate": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _SZ, _P]),
+    "psvi_sampled_kl_grad": (_I32, [_P, _P, _P, _P, _P, _P]),
+    "psvi_row_loglik": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psvi_select_scores": (_I32, [_I32, _I32, _I32, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P,
+                                  _P]),
+    "psvi_select_weight_grad": (_I32, [_I32, _I32, _I32, _P, _P, _P, ctypes.c_double, _P, _P,
+                                       _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -72,16 +72,21 @@ class InnerLoopPlan:
     stack); layers: [(in, out), ...]; S: global MC samples; M: pseudopoints.
     likelihood: None (categorical, class ids in an int32 z) or ("gaussian", tau):
     Normal(f, 1 / sqrt(tau)) over the one network output, the regressors'
-    observation model -- every z / z_all is then a float32 tensor of targets."""
+    observation model -- every z / z_all is then a float32 tensor of targets;
+    or "bernoulli" (also ("bernoulli", None)): Bernoulli(logits = f) over the one
+    output, int32 class ids in {0, 1} in z -- sparse black-box VI."""
 
     def __init__(self, family, layers, S, M, prior_sd=1.0, world=1, rank=0, likelihood=None):
         self.lib = _lib.load()
         if likelihood is None:
             self.likelihood, self.tau = "categorical", None
+        elif likelihood == "bernoulli" or tuple(likelihood) == ("bernoulli", None):
+            self.likelihood, self.tau = "bernoulli", None
         else:
             kind, tau = likelihood
             if kind != "gaussian":
-                raise ValueError(f"unknown likelihood {kind!r} (None or ('gaussian', tau))")
+                raise ValueError(f"unknown likelihood {kind!r} (None, 'bernoulli' or "
+                                 "('gaussian', tau))")
             self.likelihood, self.tau = "gaussian", float(tau)
         # dtype of every z / z_all argument
         self._zdtype = torch.float32 if self.likelihood == "gaussian" else torch.int32
@@ -112,8 +117,9 @@ class InnerLoopPlan:
         d.S, d.M, d.prior_sd = self.S, self.M, float(prior_sd)
         self.desc = d
         h = ctypes.c_void_p()
-        if self.likelihood == "gaussian":
-            lik = Likelihood(_lib.LIK_GAUSSIAN, self.tau)
+        if self.likelihood != "categorical":
+            lik = (Likelihood(_lib.LIK_GAUSSIAN, self.tau) if self.likelihood == "gaussian"
+                   else Likelihood(_lib.LIK_BERNOULLI, 0.0))
             check(self.lib.psvi_plan_create_lik(fam, ctypes.byref(d), self.world, self.rank,
                                                 ctypes.byref(lik), ctypes.byref(h)),
                   "psvi_plan_create_lik")
@@ -183,6 +189,46 @@ class InnerLoopPlan:
         _need(z, "z", self.M, self._zdtype)
         _need(w, "w", self.M)
         _need(eps, "eps", self.eps_count)
+
+    # ------------------------------------------------- sparse black-box VI
+    def sampled_kl_grad(self, eps, params, grad=None, nkl=None):
+        """The sampled KL term of every layer (psvi_sampled_kl_grad, mean-field
+        plans): returns nkl (S float64, log p(theta_s) - log q(theta_s)); with
+        ``grad`` (param_count float32) the gradient of -sum_s nkl_s is ADDED
+        into it.  Bitwise reproducible."""
+        _need(eps, "eps", self.eps_count)
+        _need(params, "params", self.param_count)
+        if grad is not None:
+            _need(grad, "grad", self.param_count)
+        if nkl is None:
+            nkl = torch.empty(self.S, dtype=torch.float64, device=params.device)
+        _need(nkl, "nkl", self.S, torch.float64)
+        check(self.lib.psvi_sampled_kl_grad(self.handle, _ptr(eps), _ptr(params), _ptr(nkl),
+                                            _ptr(grad), _stream()), "psvi_sampled_kl_grad")
+        if grad is not None:
+            _wrote(grad)
+        return nkl
+
+    def row_loglik(self, x_all, z_all, eps, params, logits=False, nkl=True):
+        """Per-sample, per-row log-likelihoods of a Bernoulli plan's M rows under
+        ONE draw eps (psvi_row_loglik).  Returns (ll, f, nkl): ll (S, M) float32
+        = -NLL; f (S, M) the raw outputs when ``logits``; nkl (S) float64 when
+        ``nkl`` (else None).  The labels must be class ids in {0, 1}: checked by
+        the caller (``check_binary``)."""
+        if self.likelihood != "bernoulli":
+            raise ValueError("row_loglik needs a Bernoulli-likelihood plan")
+        _need(x_all, "x_all", self.M * self.in_features)
+        _need(z_all, "z_all", self.M, torch.int32)
+        _need(eps, "eps", self.eps_count)
+        _need(params, "params", self.param_count)
+        dev = params.device
+        ll = torch.empty(self.S, self.M, dtype=torch.float32, device=dev)
+        f = torch.empty(self.S, self.M, dtype=torch.float32, device=dev) if logits else None
+        k = torch.empty(self.S, dtype=torch.float64, device=dev) if nkl else None
+        check(self.lib.psvi_row_loglik(self.handle, _ptr(x_all), _ptr(z_all), _ptr(eps),
+                                       _ptr(params), _ptr(ll), _ptr(f), _ptr(k), _stream()),
+              "psvi_row_loglik")
+        return ll, f, k
 
     # --------------------------------------------------------- world == 1
     def inner_step(self, u, z, w, eps, params, adam_m, adam_v, step, lr, kind="higher",
@@ -608,6 +654,60 @@ class InnerLoopPlan:
                                              int(bool(include_kl)), _stream()),
               "psvi_mvn_phase_update")
         _wrote(params, adam_m, adam_v)
+
+
+def check_binary(z, name="z"):
+    """The host's range check of a Bernoulli plan's labels: class ids in {0, 1}."""
+    if z.is_floating_point() and not torch.equal(z, z.round()):
+        raise ValueError(f"{name} must hold class ids")
+    if z.numel() and not bool(((z == 0) | (z == 1)).all()):
+        raise ValueError(f"{name} must hold class ids in {{0, 1}} (Bernoulli likelihood)")
+
+
+def _ll_shape(ll, nkl, n_core, n_data):
+    if ll is None or ll.dim() != 2:
+        raise ValueError("ll must be the (S, n_core + n_data) tensor of row_loglik")
+    S = int(ll.shape[0])
+    _need(ll, "ll", S * (int(n_core) + int(n_data)))
+    _need(nkl, "nkl", S, torch.float64)
+    return S
+
+
+def select_scores(ll, nkl, w_core, n_core, sum_scaling):
+    """Greedy selection scores of sparse black-box VI (psvi_select_scores) from
+    row_loglik's ll (S, n_core + n_data; core columns first) and nkl.  Returns a
+    dict of device tensors: W (S), corr (n_data), corecorr (n_core, None at 0)
+    and result (4 float64: max corr, its first arg, max corecorr, attach)."""
+    n_core = int(n_core)
+    n_data = int(ll.shape[1]) - n_core
+    S = _ll_shape(ll, nkl, n_core, n_data)
+    if n_core:
+        _need(w_core, "w_core", n_core)
+    dev = ll.device
+    out = {"W": torch.empty(S, dtype=torch.float32, device=dev),
+           "corr": torch.empty(n_data, dtype=torch.float32, device=dev),
+           "corecorr": torch.empty(n_core, dtype=torch.float32, device=dev) if n_core else None,
+           "result": torch.empty(4, dtype=torch.float64, device=dev)}
+    check(_lib.load().psvi_select_scores(S, n_core, n_data, _ptr(ll), _ptr(nkl),
+                                         _ptr(w_core) if n_core else None, float(sum_scaling),
+                                         _ptr(out["W"]), _ptr(out["corr"]), _ptr(out["corecorr"]),
+                                         _ptr(out["result"]), _stream()), "psvi_select_scores")
+    return out
+
+
+def select_weight_grad(ll, nkl, w_core, N):
+    """sparsevi_psvi_elbo and its gradient w.r.t. the core weights
+    (psvi_select_weight_grad): returns (loss (1,) float64, grad_w (n_core,))."""
+    n_core = int(w_core.numel())
+    n_data = int(ll.shape[1]) - n_core
+    S = _ll_shape(ll, nkl, n_core, n_data)
+    _need(w_core, "w_core", n_core)
+    loss = torch.empty(1, dtype=torch.float64, device=ll.device)
+    gw = torch.empty(n_core, dtype=torch.float32, device=ll.device)
+    check(_lib.load().psvi_select_weight_grad(S, n_core, n_data, _ptr(ll), _ptr(nkl),
+                                              _ptr(w_core), float(N), _ptr(loss), _ptr(gw),
+                                              _stream()), "psvi_select_weight_grad")
+    return loss, gw
 
 
 def randn_(out, seed, offset=0):

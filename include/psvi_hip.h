@@ -152,9 +152,19 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world,
  * = gaussian_fn(scale = 1 / sqrt(tau)), make_regressor_net neural_net.py:300-331).
  * For a row with output f, target z and weight w:
  *   NLL = tau / 2 (f - z)^2 + log(2 pi / tau) / 2,  d NLL / d f = tau (f - z),
- *   d NLL / d z = -d NLL / d f. */
+ *   d NLL / d z = -d NLL / d f.
+ *
+ * PSVI_LIK_BERNOULLI: Bernoulli(logits = f) over ONE network output f -- the
+ * observation model of the sparse black-box VI coreset construction
+ * (run_sparsevi_with_bb_elbo, psvi/inference/sparsebbvi.py; elbo /
+ * forward_through_coreset / sparsevi_psvi_elbo / predict_through_coreset,
+ * psvi/inference/utils.py:85-141).  z stays int32 class ids, in {0, 1} (the
+ * caller checks the range); tau is ignored.  For output f, label z:
+ *   NLL = softplus(f) - z f = max(f, 0) - z f + log1p(exp(-|f|)),
+ *   d NLL / d f = sigmoid(f) - z. */
 #define PSVI_LIK_CATEGORICAL 0
 #define PSVI_LIK_GAUSSIAN    1
+#define PSVI_LIK_BERNOULLI   2
 typedef struct psvi_likelihood {
     int32_t kind;      /* PSVI_LIK_*                                      */
     float   tau;       /* PSVI_LIK_GAUSSIAN: the precision, > 0           */
@@ -168,7 +178,13 @@ typedef struct psvi_likelihood {
  * phases, psvi_outer_elbo_grad(_coef)(_ex), psvi_hvp(_partial / _ex) and
  * psvi_evaluate_regression run with fp32 targets (see Conventions);
  * psvi_evaluate returns PSVI_ESTATE and psvi_outer_ablated_elbo_grad
- * PSVI_EUNSUP (the reference has no ablated regressor). */
+ * PSVI_EUNSUP (the reference has no ablated regressor).
+ * A Bernoulli lik has the same limits (mean-field, world == 1: PSVI_EUNSUP
+ * otherwise; dims[n_layers] == 1: PSVI_EINVAL otherwise).  On such a plan
+ * psvi_inner_step, psvi_elbo_grad, psvi_inner_loop(_ex), the mean-field phases
+ * (with include_kl = 1: the analytic KL, as on every plan), psvi_sampled_kl_grad
+ * and psvi_row_loglik run; the outer-objective, evaluate, HVP and R-op entry
+ * points return PSVI_EUNSUP. */
 int psvi_plan_create_lik(int32_t family, const psvi_net_desc* d, int32_t world,
                          int32_t rank, const psvi_likelihood* lik, psvi_plan** out);
 int psvi_plan_destroy(psvi_plan* plan);
@@ -459,6 +475,64 @@ int psvi_evaluate_regression(const psvi_plan* plan, int32_t n_pseudo, const floa
                              const float* params, int32_t correction, float y_mean,
                              float y_std, float* pred_out, double* stats_out, void* ws,
                              size_t ws_bytes, void* stream);
+
+/* ---- sparse black-box VI (run_sparsevi_with_bb_elbo) -----------------------
+ * The sampled KL term of every mean-field layer (VIMixin.sampled_nkl,
+ * psvi/models/neural_net.py:110-115) on a mean-field plan of any likelihood,
+ * world == 1.  With theta_s = mu + sigma eps_s, sigma = softplus(rho), n
+ * sampled elements and prior sd s0 (the log(2 pi) constants cancel):
+ *   nkl_out[s] (S doubles, written; nullable) <- log p(theta_s) - log q(theta_s)
+ *       = -n log s0 - |theta_s|^2 / (2 s0^2) + sum_i log sigma_i + |eps_s|^2 / 2
+ *   grad_out (PARAM_COUNT floats, nullable, ADDED into) += d(-sum_s nkl_s) / d params:
+ *       mu_i:  sum_s theta_si / s0^2
+ *       rho_i: (sum_s theta_si eps_si / s0^2 - S / sigma_i) sigmoid(rho_i)
+ * At least one of nkl_out / grad_out is given (PSVI_EINVAL otherwise); a NULL
+ * one is skipped.  One writer per element, the sums over s and i in a fixed
+ * order: bitwise reproducible run to run; no float atomics. */
+int psvi_sampled_kl_grad(const psvi_plan* plan, const float* eps, const float* params,
+                         double* nkl_out, float* grad_out, void* stream);
+
+/* Per-sample, per-row log-likelihoods of a Bernoulli plan's M rows (the
+ * network's forward pass; forward_through_coreset / predict_through_coreset,
+ * psvi/inference/utils.py:108-141), world == 1:
+ *   ll_out     ([S][M] floats, row index contiguous) <- -NLL_sm, unweighted
+ *   logits_out ([S][M] floats, nullable)             <- the raw output f_sm
+ *   nkl_out    (S doubles, nullable)                 <- as psvi_sampled_kl_grad
+ * x_all ([M][D]), z_all (M class ids in {0, 1}), eps (EPS_COUNT: ONE draw for
+ * all rows) and params as psvi_elbo_grad's.  No workspace. */
+int psvi_row_loglik(const psvi_plan* plan, const float* x_all, const int32_t* z_all,
+                    const float* eps, const float* params, float* ll_out, float* logits_out,
+                    double* nkl_out, void* stream);
+
+/* The greedy selection scores of sparse black-box VI (sparsebbvi.py:143-170)
+ * from ll ([S][n_core + n_data], psvi_row_loglik's layout: core columns
+ * first), nkl (S doubles), w_core (n_core floats) and sum_scaling = N / B:
+ *   W_s         = softmax_s(sum_m w_m ll_sm + nkl_s)
+ *   cll_sj      = ll_sj (1 - W_s)      (the reference scales, it does not centre)
+ *   resid_s     = sum_scaling sum_n cll_sn - sum_m w_m cll_sm
+ *   corr_n      = (cll_.n . resid) / |cll_.n| / S       -> corr_out (n_data)
+ *   corecorr_m  = |cll_.m . resid| / |cll_.m| / S       -> corecorr_out (n_core)
+ *   W_out (S floats) <- W
+ *   result_out (4 doubles) <- max corr, its first arg (as a double), max
+ *       corecorr (-inf when n_core == 0), attach = (n_core == 0 or max corr >
+ *       max corecorr)
+ * 2 <= S <= 2048, n_core >= 0 (w_core / corecorr_out may be NULL at 0),
+ * n_data >= 1.  fp64 sums in a fixed order: bitwise reproducible. */
+int psvi_select_scores(int32_t S, int32_t n_core, int32_t n_data, const float* ll,
+                       const double* nkl, const float* w_core, double sum_scaling, float* W_out,
+                       float* corr_out, float* corecorr_out, double* result_out, void* stream);
+
+/* sparsevi_psvi_elbo (psvi/inference/utils.py:94-105) and its gradient with
+ * respect to the core weights, from the same ll / nkl layout.  With c_sm =
+ * -ll_sm over the core, d_s = -sum_n ll_sn over the data, a_s = (N / n_core)
+ * sum_m w_m c_sm, lw_s = -a_s + nkl_s, W = softmax_s(lw), r_s = (N / n_data)
+ * d_s - a_s, rbar = sum_s W_s r_s:
+ *   loss_out[0] (double, written) <- rbar - mean_s lw_s
+ *   grad_w (n_core floats) <- (N / n_core) sum_s c_sm [1 / S - W_s (1 + r_s - rbar)]
+ * 2 <= S <= 2048, n_core >= 1, n_data >= 1; fixed-order fp64 sums. */
+int psvi_select_weight_grad(int32_t S, int32_t n_core, int32_t n_data, const float* ll,
+                            const double* nkl, const float* w_core, double N, double* loss_out,
+                            float* grad_w, void* stream);
 
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's
