@@ -1294,6 +1294,61 @@ int psvi_select_weight_grad(int32_t S, int32_t n_core, int32_t n_data, const flo
     return 0;
 }
 
+int psvi_laplace_fit(const psvi_laplace_fit_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    if (q->d < 2 || q->d > kLapMaxD || q->n_core < 0 || q->n_core > kLapMaxNu || q->S < 0 ||
+        q->S > 2048 || q->T < 0 || q->T > kLapMaxT)
+        return fail(PSVI_EINVAL, "the Laplace fit supports 2 <= d <= 256, 0 <= n_core <= 4096, "
+                                 "0 <= S <= 2048, 0 <= T <= 1048576");
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    if (!pos(q->lr) || !pos(q->beta1) || !pos(q->beta2) || q->beta1 >= 1.0 || q->beta2 >= 1.0 ||
+        !pos(q->adam_eps) || !pos(q->prior_sd) || !std::isfinite(q->prior_mean))
+        return fail(PSVI_EINVAL, "bad Adam constants or prior");
+    if (!q->theta || !q->prec_out || (q->n_core > 0 && (!q->x_core || !q->y_core || !q->w_core)) ||
+        (q->eps && (!q->samples_out || q->S < 1)))
+        return fail(PSVI_EINVAL, "null pointer");
+    hipStream_t st = as_stream(stream);
+    if (q->n_core > 0) {
+        // zero weights add nothing to the reference's masked precision sum; negative ones would
+        std::vector<float> w(q->n_core);
+        HIP_TRY(hipMemcpyAsync(w.data(), q->w_core, sizeof(float) * w.size(), hipMemcpyDeviceToHost,
+                               st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (float v : w)
+            if (!(v >= 0.0f) || !std::isfinite(v))
+                return fail(PSVI_EINVAL, "the Laplace fit needs finite weights >= 0");
+    }
+    LaplaceFit r;
+    r.Nu = q->n_core; r.d = q->d; r.S = q->eps ? q->S : 0; r.T = q->T;
+    r.x = q->x_core; r.y = q->y_core; r.w = q->w_core;
+    r.mu0 = q->prior_mean; r.sd0 = q->prior_sd;
+    r.theta = q->theta;
+    r.lr = q->lr; r.beta1 = q->beta1; r.beta2 = q->beta2; r.adam_eps = q->adam_eps;
+    r.eps = q->eps; r.loss_out = q->loss_out; r.prec_out = q->prec_out;
+    r.samples_out = q->samples_out;
+    HIP_TRY(launch_laplace_fit(r, st));
+    return 0;
+}
+
+int psvi_laplace_scores(const psvi_laplace_scores_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    if (q->S < 2 || q->S > 2048 || q->d < 2 || q->d > kLapMaxD || q->n_core < 0 ||
+        q->n_data < 1 || (int64_t)q->n_core + q->n_data > kLapMaxRows)
+        return fail(PSVI_EINVAL, "the Laplace scores support 2 <= S <= 2048, 2 <= d <= 256, "
+                                 "n_data >= 1, n_core + n_data <= 2048");
+    if (!q->samples || !q->rows || !q->labels || !q->corr_out || !q->result_out ||
+        (q->n_core > 0 && (!q->w_core || !q->corecorr_out)))
+        return fail(PSVI_EINVAL, "null pointer");
+    LaplaceScores r;
+    r.S = q->S; r.d = q->d; r.Nu = q->n_core; r.B = q->n_data;
+    r.samples = q->samples; r.rows = q->rows; r.labels = q->labels; r.w = q->w_core;
+    r.sum_scaling = q->sum_scaling;
+    r.corr = q->corr_out; r.corecorr = q->corecorr_out; r.result = q->result_out;
+    r.grad_w = q->grad_w; r.ll_out = q->ll_out; r.grad_u = q->grad_u;
+    HIP_TRY(launch_laplace_scores(r, as_stream(stream)));
+    return 0;
+}
+
 int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,

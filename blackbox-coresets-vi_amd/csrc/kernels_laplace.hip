@@ -1,0 +1,290 @@
+// kernels_laplace.hip -- the computational core of the Laplace coreset
+// baselines (random, sparsevi, opsvi): the Laplace fit of a weighted logistic
+// regression on the coreset, its diagonal precision and samples, and the
+// selection scores / weight gradient / pseudo-input gradient from the samples'
+// centred log-likelihoods.
+//
+// Reference:
+//   run_laplace         psvi/inference/baselines.py:35-70
+//   model               psvi/models/logreg.py:17-26
+//   laplace_precision   psvi/models/logreg.py:95-107 (diagonal)
+//   scores / gradients  psvi/inference/baselines.py:550-575, 617-635, 783-805
+//
+// Fit: T torch-Adam steps on theta [d] of the negative log-joint
+//   loss = -sum_m w_m (y_m f_m - softplus(f_m)) - sum_j log N(theta_j; mu0, sd0),  f = X theta
+//   g    = -X^T (w o (y - sigmoid(f))) + (theta - mu0) / sd0^2
+// in ONE launch of ONE workgroup: a chain of up to a million dependent steps
+// on a few hundred numbers is latency, not throughput.  theta is double-
+// buffered in LDS (the step reads one copy, the column owners write the
+// other), m / v / theta live in the column owner's registers, X is staged to
+// LDS (rows padded to an odd stride) when it fits beside them and read from
+// global memory otherwise.  Two barriers per step:
+//   rows:    thread t owns rows t, t + 256, ...: f_m, r_m = w_m (y_m - p_m) -> LDS,
+//            its rows' share of the objective -> part[t]
+//   columns: thread j < d owns column j: g_j over the rows in order, the Adam
+//            update; thread 255 sums part[] and the prior in order -> loss_out[t]
+// Every sum has one owner and a fixed order, all of them in fp64; theta is
+// rounded to float on output only.  No atomics.
+//
+// Scores: one workgroup as kernels_select.hip, which scales ll by 1 - W_s where
+// these baselines centre it by the per-row mean over the samples.  ll_sj = y_j f_sj -
+// softplus(f_sj) is rounded to float (what ll_out holds) before any sum uses it.
+#include "psvi_internal.hpp"
+#include "select_reduce.hpp"
+
+namespace psvi {
+
+constexpr int kLapThreads = 256;
+constexpr size_t kLapLds = 160 * 1024;
+
+// overflow-safe Bernoulli terms of a logit f: e = exp(-|f|),
+// sigmoid(f) = 1 / (1 + e) or e / (1 + e), softplus(f) = max(f, 0) + log1p(e)
+__device__ __forceinline__ double lap_sigmoid(double f) {
+    const double e = exp(-fabs(f));
+    return f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+// y f - softplus(f) in BCEWithLogits' arrangement, -((1 - y) f + max(-f, 0) +
+// log1p(e)): at a saturated logit on the label's side the first two terms
+// vanish exactly and the tiny log1p(e) survives
+__device__ __forceinline__ double lap_loglik(double y, double f) {
+    return -((1.0 - y) * f + fmax(-f, 0.0) + log1p(exp(-fabs(f))));
+}
+
+struct LapFitArgs {
+    int Nu, d, S, T, ds;
+    const float *x, *y, *w, *eps;
+    double mu0, inv_var0, log_norm0;  // log_norm0 = -log(sd0) - log(2 pi) / 2
+    double lr, b1, b2, adam_eps;
+    float* theta;
+    double* loss;
+    float* prec;
+    float* samples;
+};
+
+template <bool XLDS>
+__global__ __launch_bounds__(kLapThreads) void laplace_fit_kernel(LapFitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lap_sm[];
+    const int Nu = a.Nu, d = a.d, tid = threadIdx.x;
+    double* th = lap_sm;                 // [2][kLapMaxD]
+    double* part = th + 2 * kLapMaxD;    // [kLapThreads]
+    double* r = part + kLapThreads;      // [Nu]
+    float* xs = (float*)(r + Nu);        // [Nu][ds], XLDS only
+    const int ld = XLDS ? a.ds : d;
+    if (XLDS) {
+        for (int i = tid; i < Nu * d; i += kLapThreads) xs[(i / d) * ld + i % d] = a.x[i];
+    }
+    auto X = [&](int m, int j) -> double {
+        return XLDS ? (double)xs[m * ld + j] : (double)a.x[(size_t)m * d + j];
+    };
+    double tj = 0.0, mj = 0.0, vj = 0.0;  // column owner's theta_j and Adam moments
+    if (tid < d) {
+        tj = (double)a.theta[tid];
+        th[tid] = tj;
+    }
+    __syncthreads();
+    double p1 = 1.0, p2 = 1.0;  // beta^t
+    for (int t = 0; t < a.T; ++t) {
+        const double* tc = th + (t & 1) * kLapMaxD;
+        double* tn = th + ((t + 1) & 1) * kLapMaxD;
+        double lt = 0.0;
+        for (int m = tid; m < Nu; m += kLapThreads) {
+            double f = 0.0;
+            for (int j = 0; j < d; ++j) f += X(m, j) * tc[j];
+            const double wm = a.w[m], ym = a.y[m];
+            r[m] = wm * (ym - lap_sigmoid(f));
+            if (a.loss) lt += wm * lap_loglik(ym, f);
+        }
+        part[tid] = lt;
+        __syncthreads();
+        p1 *= a.b1;
+        p2 *= a.b2;
+        if (tid < d) {
+            double g = 0.0;
+            for (int m = 0; m < Nu; ++m) g += X(m, tid) * r[m];
+            g = (tj - a.mu0) * a.inv_var0 - g;
+            // torch.optim.Adam: step = lr / bc1, denom = sqrt(v) / sqrt(bc2) + eps
+            mj = a.b1 * mj + (1.0 - a.b1) * g;
+            vj = a.b2 * vj + (1.0 - a.b2) * g * g;
+            const double denom = sqrt(vj) / sqrt(1.0 - p2) + a.adam_eps;
+            tj -= a.lr / (1.0 - p1) * (mj / denom);
+            tn[tid] = tj;
+        }
+        if (a.loss && tid == kLapThreads - 1) {
+            double s = 0.0;
+            for (int i = 0; i < kLapThreads; ++i) s += part[i];
+            for (int j = 0; j < d; ++j) {
+                const double z = tc[j] - a.mu0;
+                s += a.log_norm0 - 0.5 * z * z * a.inv_var0;
+            }
+            a.loss[t] = -s;
+        }
+        __syncthreads();
+    }
+    // diagonal precision at the fitted theta and the samples from it
+    const double* tc = th + (a.T & 1) * kLapMaxD;
+    for (int m = tid; m < Nu; m += kLapThreads) {
+        double f = 0.0;
+        for (int j = 0; j < d; ++j) f += X(m, j) * tc[j];
+        const double p = lap_sigmoid(f);
+        r[m] = (double)a.w[m] * p * (1.0 - p);
+    }
+    __syncthreads();
+    if (tid < d) {
+        double pr = 0.0;
+        for (int m = 0; m < Nu; ++m) {
+            const double xv = X(m, tid);
+            pr += r[m] * xv * xv;
+        }
+        pr += 1.0;
+        a.theta[tid] = (float)tj;
+        a.prec[tid] = (float)pr;
+        if (a.eps) {
+            const double sd = 1.0 / sqrt(pr);
+            for (int s = 0; s < a.S; ++s)
+                a.samples[(size_t)s * d + tid] = (float)(tj + sd * (double)a.eps[(size_t)s * d + tid]);
+        }
+    }
+}
+
+static size_t lap_fit_lds(int Nu, int ds, bool xlds) {
+    return sizeof(double) * (2 * kLapMaxD + kLapThreads + (size_t)Nu) +
+           (xlds ? sizeof(float) * (size_t)Nu * ds : 0);
+}
+
+hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st) {
+    if (r.d < 1 || r.d > kLapMaxD || r.Nu < 0 || r.Nu > kLapMaxNu || r.S < 0 || r.T < 0 ||
+        r.T > kLapMaxT)
+        return hipErrorInvalidValue;
+    LapFitArgs a{};
+    a.Nu = r.Nu; a.d = r.d; a.S = r.S; a.T = r.T;
+    a.ds = r.d | 1;  // odd row stride: the row owners' reads of one column spread over the banks
+    a.x = r.x; a.y = r.y; a.w = r.w; a.eps = r.eps;
+    a.mu0 = r.mu0;
+    a.inv_var0 = 1.0 / (r.sd0 * r.sd0);
+    a.log_norm0 = -std::log(r.sd0) - 0.5 * std::log(2.0 * 3.14159265358979323846);
+    a.lr = r.lr; a.b1 = r.beta1; a.b2 = r.beta2; a.adam_eps = r.adam_eps;
+    a.theta = r.theta; a.loss = r.loss_out; a.prec = r.prec_out; a.samples = r.samples_out;
+    const bool xlds = lap_fit_lds(r.Nu, a.ds, true) <= kLapLds;
+    const size_t lds = lap_fit_lds(r.Nu, a.ds, xlds);
+    auto kernel = xlds ? laplace_fit_kernel<true> : laplace_fit_kernel<false>;
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[xlds]) {
+        hipError_t e = hipFuncSetAttribute((const void*)kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLapLds);
+        if (e != hipSuccess) return e;
+        attr_set[xlds] = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(kLapThreads), lds, st, a);
+    return hipGetLastError();
+}
+
+struct LapScoreArgs {
+    int S, d, Nu, B;
+    const float *samples, *rows, *labels, *w;
+    double scale;
+    float *corr, *corecorr, *grad_w, *ll, *grad_u;
+    double* result;
+};
+
+// ll_sj as the float the sums use
+__device__ __forceinline__ double lap_ll(const LapScoreArgs& a, int s, int j) {
+    const float* th = a.samples + (size_t)s * a.d;
+    const float* x = a.rows + (size_t)j * a.d;
+    double f = 0.0;
+    for (int k = 0; k < a.d; ++k) f += (double)x[k] * (double)th[k];
+    return (double)(float)lap_loglik((double)a.labels[j], f);
+}
+
+__global__ __launch_bounds__(kSelThreads) void laplace_scores_kernel(LapScoreArgs a) {
+    __shared__ double mean[kLapMaxRows], resid[kSelMaxS], coef[kSelMaxS], red[kSelThreads];
+    __shared__ int redi[kSelThreads];
+    const int S = a.S, d = a.d, Nu = a.Nu, B = a.B, M = Nu + B, tid = threadIdx.x;
+    // per column: the mean over the samples, in sample order
+    for (int j = tid; j < M; j += kSelThreads) {
+        double sum = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double l = lap_ll(a, s, j);
+            if (a.ll) a.ll[(size_t)s * M + j] = (float)l;
+            sum += l;
+        }
+        mean[j] = sum / S;
+    }
+    __syncthreads();
+    // per sample: resid_s = scale sum_n cll_sn - sum_m w_m cll_sm, rows in order
+    double rsum = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        double core = 0.0, data = 0.0;
+        for (int m = 0; m < Nu; ++m) core += (double)a.w[m] * (lap_ll(a, s, m) - mean[m]);
+        for (int n = Nu; n < M; ++n) data += lap_ll(a, s, n) - mean[n];
+        resid[s] = a.scale * data - core;
+        rsum += resid[s];
+    }
+    const double rbar = sel_sum(rsum, red) / S;
+    // per column: cll_.j . resid and |cll_.j|, samples in order
+    double best = -INFINITY, bestc = -INFINITY;
+    int besti = 0x7fffffff;
+    for (int j = tid; j < M; j += kSelThreads) {
+        double dot = 0.0, sq = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double c = lap_ll(a, s, j) - mean[j];
+            dot += c * resid[s];
+            sq += c * c;
+        }
+        if (j < Nu) {
+            const double v = fabs(dot) / sqrt(sq) / S;
+            a.corecorr[j] = (float)v;
+            if (a.grad_w) a.grad_w[j] = (float)(-dot / S);
+            bestc = fmax(bestc, v);
+        } else {
+            const double v = dot / sqrt(sq) / S;
+            a.corr[j - Nu] = (float)v;
+            if (v > best) {  // columns ascending per thread: the first of equal values stays
+                best = v;
+                besti = j - Nu;
+            }
+        }
+    }
+    bestc = sel_max(bestc, red);
+    sel_argmax_first(best, besti, red, redi);
+    if (tid == 0) {
+        a.result[0] = red[0];
+        a.result[1] = (double)(redi[0] == 0x7fffffff ? 0 : redi[0]);
+        a.result[2] = bestc;
+        a.result[3] = (Nu == 0 || red[0] > bestc) ? 1.0 : 0.0;
+    }
+    if (!a.grad_u) return;
+    // d u_function / d u_m = -(w_m / S) sum_s (resid_s - rbar) (z_m - sigmoid(f_sm)) theta_s:
+    // per core row, the S coefficients to LDS, then one owner per input column
+    for (int m = 0; m < Nu; ++m) {
+        __syncthreads();
+        const float* x = a.rows + (size_t)m * d;
+        for (int s = tid; s < S; s += kSelThreads) {
+            const float* th = a.samples + (size_t)s * d;
+            double f = 0.0;
+            for (int k = 0; k < d; ++k) f += (double)x[k] * (double)th[k];
+            coef[s] = (resid[s] - rbar) * ((double)a.labels[m] - lap_sigmoid(f));
+        }
+        __syncthreads();
+        for (int k = tid; k < d; k += kSelThreads) {
+            double g = 0.0;
+            for (int s = 0; s < S; ++s) g += coef[s] * (double)a.samples[(size_t)s * d + k];
+            // the ones column takes no gradient
+            a.grad_u[(size_t)m * d + k] = k == d - 1 ? 0.0f : (float)(-(double)a.w[m] / S * g);
+        }
+    }
+}
+
+hipError_t launch_laplace_scores(const LaplaceScores& r, hipStream_t st) {
+    if (r.S < 2 || r.S > kSelMaxS || r.d < 1 || r.Nu < 0 || r.B < 1 || r.Nu + r.B > kLapMaxRows)
+        return hipErrorInvalidValue;
+    LapScoreArgs a{};
+    a.S = r.S; a.d = r.d; a.Nu = r.Nu; a.B = r.B;
+    a.samples = r.samples; a.rows = r.rows; a.labels = r.labels; a.w = r.w;
+    a.scale = r.sum_scaling;
+    a.corr = r.corr; a.corecorr = r.corecorr; a.grad_w = r.grad_w; a.ll = r.ll_out;
+    a.grad_u = r.grad_u; a.result = r.result;
+    hipLaunchKernelGGL(laplace_scores_kernel, dim3(1), dim3(kSelThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace psvi

@@ -23,33 +23,9 @@
 // every sum has one owner and a fixed order; the block-wide sums meet in a
 // fixed tree.  No atomics.
 #include "psvi_internal.hpp"
+#include "select_reduce.hpp"
 
 namespace psvi {
-
-constexpr int kSelMaxS = 2048;
-constexpr int kSelThreads = 512;
-
-// block-wide fixed-tree reductions over kSelThreads values; result in every thread
-__device__ __forceinline__ double sel_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kSelThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    return red[0];
-}
-__device__ __forceinline__ double sel_max(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kSelThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // softmax over lw[0, S) in place (LDS): W_s = exp(lw_s - max) / sum
 __device__ __forceinline__ void sel_softmax(double* lw, int S, double* red) {
@@ -125,21 +101,7 @@ __global__ __launch_bounds__(kSelThreads) void select_scores_kernel(SelArgs a) {
     }
     bestc = sel_max(bestc, red);
     // max corr and its first argument: (value, index) pairs in a fixed tree
-    __syncthreads();
-    red[tid] = best;
-    redi[tid] = besti;
-    __syncthreads();
-    for (int o = kSelThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double v = red[tid + o];
-            const int i = redi[tid + o];
-            if (v > red[tid] || (v == red[tid] && i < redi[tid])) {
-                red[tid] = v;
-                redi[tid] = i;
-            }
-        }
-        __syncthreads();
-    }
+    sel_argmax_first(best, besti, red, redi);
     if (tid == 0) {
         a.result[0] = red[0];
         a.result[1] = (double)(redi[0] == 0x7fffffff ? 0 : redi[0]);

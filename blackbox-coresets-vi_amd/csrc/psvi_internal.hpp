@@ -796,6 +796,44 @@ hipError_t launch_select_scores(int S, int Nu, int B, const float* ll, const dou
 hipError_t launch_select_weight_grad(int S, int Nu, int B, const float* ll, const double* nkl,
                                      const float* w, double N, double* loss, float* grad_w,
                                      hipStream_t st);
+// Laplace coreset baselines (kernels_laplace.hip).  The fit: T torch-Adam steps
+// on theta [d] of the weighted logistic log-joint of x [Nu][d] / y / w in one
+// workgroup, then the diagonal precision and (eps given) S samples from it.
+constexpr int kLapMaxD = 256;      // one column owner per thread of the fit's workgroup
+constexpr int kLapMaxNu = 4096;    // the fit's per-row terms live in LDS
+constexpr int kLapMaxRows = 2048;  // the scores' per-row means live in LDS
+constexpr int kLapMaxT = 1 << 20;
+struct LaplaceFit {
+    int Nu = 0, d = 0, S = 0, T = 0;
+    const float* x = nullptr;
+    const float* y = nullptr;
+    const float* w = nullptr;
+    double mu0 = 0.0, sd0 = 1.0;
+    float* theta = nullptr;  // in / out
+    double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8;
+    const float* eps = nullptr;    // [S][d], nullable
+    double* loss_out = nullptr;    // [T], nullable
+    float* prec_out = nullptr;     // [d]
+    float* samples_out = nullptr;  // [S][d], written when eps is given
+};
+hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st);
+// scores, weight gradient and pseudo-input gradient from samples [S][d] and
+// rows [Nu + B][d] (core rows first)
+struct LaplaceScores {
+    int S = 0, d = 0, Nu = 0, B = 0;
+    const float* samples = nullptr;
+    const float* rows = nullptr;
+    const float* labels = nullptr;
+    const float* w = nullptr;
+    double sum_scaling = 1.0;
+    float* corr = nullptr;      // [B]
+    float* corecorr = nullptr;  // [Nu]
+    double* result = nullptr;   // [4]
+    float* grad_w = nullptr;    // [Nu], nullable
+    float* ll_out = nullptr;    // [S][Nu + B], nullable
+    float* grad_u = nullptr;    // [Nu][d], nullable
+};
+hipError_t launch_laplace_scores(const LaplaceScores& r, hipStream_t st);
 // outer objective (kernels_outer.hip)
 hipError_t launch_outer_stats(const psvi_plan& p, const float* params, const float* eps,
                               const float* x, double* stats, hipStream_t st);

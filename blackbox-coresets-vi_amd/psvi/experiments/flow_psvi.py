@@ -13,7 +13,7 @@ baselines have no sample-sharded form and run whole on every rank.  Rank 0
 alone writes the results files."""
 from ..inference import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV, PSVILearnV,
                          PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, run_mfvi, run_mfvi_subset,
-                         run_sparsevi_with_bb_elbo)
+                         run_opsvi, run_random, run_sparsevi, run_sparsevi_with_bb_elbo)
 from .experiments_utils import read_dataset, rec_dd, write_to_files
 
 
@@ -25,8 +25,9 @@ def _psvi(cls):
 # classes run on the HIP path (psvi.inference.PSVI_regressor,
 # PSVILearnV_regressor, PSVIAV_regressor), but the reference's regression
 # datasets are remote downloads and read_dataset returns no y_mean / y_std --
-# and the selection baselines (sparsevi, giga, opsvi, random), which are not
-# on the HIP path.  sparsebbvi runs on it (Bernoulli plans, one output).
+# and giga, whose geodesic step is not on the HIP path.  sparsebbvi runs on it
+# (Bernoulli plans, one output), and so do the Laplace baselines random,
+# sparsevi and opsvi (psvi_laplace_fit, psvi_laplace_scores).
 inf_dict = {
     "psvi": _psvi(PSVI),
     "psvi_ablated": _psvi(PSVI_Ablated),
@@ -40,6 +41,9 @@ inf_dict = {
     "mfvi": run_mfvi,
     "mfvi_subset": run_mfvi_subset,
     "sparsebbvi": run_sparsevi_with_bb_elbo,
+    "random": run_random,
+    "sparsevi": run_sparsevi,
+    "opsvi": run_opsvi,
 }
 
 
@@ -93,7 +97,9 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
                         train_dataset=train_dataset, test_dataset=test_dataset, dnm=dnm, nc=nc,
                         learn_z=method_args.get("learn_z", False),
                         **(dict(outer_it=method_args["outer_it"], scatterplot_coreset=False)
-                           if nm_alg == "sparsebbvi" else {}))
+                           if nm_alg == "sparsebbvi" else {}),
+                        **(dict(outer_it=method_args["outer_it"])
+                           if nm_alg == "sparsevi" else {}))
     if write and rank == 0:
         return write_to_files(results, method_args.get("fnm", "results"),
                               method_args.get("results_folder", "results"))

@@ -2,5 +2,6 @@
 from .psvi_classes import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV,  # noqa: F401
                            PSVILearnV, PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, HipInnerELBO,
                            PSVI_regressor, PSVILearnV_regressor, PSVIAV_regressor)
-from .baselines import run_mfvi, run_mfvi_subset  # noqa: F401,E402
+from .baselines import (run_mfvi, run_mfvi_subset, run_random, run_sparsevi,  # noqa: F401,E402
+                        run_opsvi, process_wt_index)
 from .sparsebbvi import run_sparsevi_with_bb_elbo  # noqa: F401,E402

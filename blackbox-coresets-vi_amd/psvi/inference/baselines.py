@@ -13,6 +13,48 @@ trains without KL.  The predictive evaluation every ``log_every`` iterations
 averages the LOGITS over samples (baselines.py:898-906) and runs the model's
 torch forward on the device (not the hot path).  There is no CPU fallback:
 the training step raises without the HIP library or a device.
+
+Laplace coreset baselines ("Laplace baselines"):
+
+  run_random    baselines.py:118-203   uniform random coreset, weights N / |core|
+  run_sparsevi  baselines.py:426-648   Sparse VI (Campbell & Beronov, 2019)
+  run_opsvi     baselines.py:652-821   the original PSVI (Manousakas et al., 2020)
+
+Their shared core runs on the HIP library: the Laplace fit of the weighted
+logistic regression on the coreset, its diagonal precision and samples
+(psvi_laplace_fit: the whole chain of Adam steps in one launch), and the
+scores, weight gradient and pseudo-input gradient from the samples' centred
+log-likelihoods (psvi_laplace_scores).  The noise -- d floats for theta0, S d
+for the samples -- is drawn on the host from the CPU generators in the
+reference's order and uploaded with the request.  Reference behaviours kept:
+
+* ``run_laplace`` reseeds ``random``, ``numpy`` and ``torch`` with its ``seed``
+  on every call.  ``run_sparsevi`` calls it without a seed, so 0 is used; the
+  minibatch indices and ``random.choice`` that follow a logging step restart
+  from that seed.
+* In ``run_random`` and at sparsevi's logging step theta0 is drawn before the
+  reseed; both fit 1000 steps there whatever ``inner_it`` says.
+* sparsevi creates a new ``optim_w`` every epoch: fresh Adam state over the
+  full w (N,), only core entries get gradient, ``clamp_(w, 0)`` follows each
+  step.  The point attached is the true argmax of corr over the minibatch.
+* In sparsevi's step 4 theta carries across the ``outer_it`` fits while each
+  fit's Adam is new.
+* opsvi's weight optimiser runs at ``lr0v * N``; its pseudo-inputs carry the
+  ones column with zero gradient; its ``optim_net`` is re-created each epoch
+  and its theta persists (the logging fit trains the same theta).  The
+  reference's ``optim_w.zero_grad()`` / ``w.grad.data = ...`` pair is taken
+  with in-place zeroing, the behaviour it was written against: the gradients
+  the step sees are exactly the ones assigned.
+* opsvi's ``us`` / ``vs`` logs are numpy views of the live tensors, which the
+  in-place optimiser steps keep writing: every logged entry holds the final
+  values.
+* ``run_random`` sets ``w[core] = N / len(core)``.
+
+``mcmc=True`` (stan) and ``diagonal=False`` raise NotImplementedError.
+Optional test hooks: ``noise_source(n)`` supplies each host draw,
+``batch_source()`` the ``np.random.randint`` minibatches,
+``choice_source(candidates)`` run_random's ``random.choice``; ``state_out`` (a
+dict) receives the final w, core_idcs, theta and, for opsvi, u.
 """
 import random
 import time
@@ -24,10 +66,11 @@ from torch.utils.data import DataLoader
 
 from ..models import (VILinear, VILinearMultivariateNormal, categorical_fn, make_fc2net,
                       make_fcnet, make_lenet, model_spec)
-from ..runtime import InnerLoopPlan, adam_update_, randn_
+from ..runtime import (InnerLoopPlan, adam_update_, check_binary, laplace_fit, laplace_scores,
+                       randn_)
 
 __all__ = ["set_up_model", "pseudo_subsample_init", "pseudo_rand_init", "run_mfvi",
-           "run_mfvi_subset"]
+           "run_mfvi_subset", "process_wt_index", "run_random", "run_sparsevi", "run_opsvi"]
 
 
 def set_up_model(D=None, n_hidden=None, nc=None, mc_samples=None, architecture=None,
@@ -228,3 +271,240 @@ def run_mfvi_subset(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibat
     stepper.sync_model()
     return {"accs": accs, "nlls": nlls, "times": times[1:], "elbos": elbos,
             "csizes": [num_pseudo] * (mul_fact * num_epochs)}
+
+
+# ---------------------------------------------------------------- Laplace baselines
+def process_wt_index(log_core_idcs, log_core_wts):
+    """psvi/inference/utils.py:180-192: per logging step, {core index: weight}."""
+    return [{int(i): float(wts[int(i)]) for i in idcs}
+            for idcs, wts in zip(log_core_idcs, log_core_wts)]
+
+
+def _reseed(seed):
+    random.seed(seed), np.random.seed(seed), torch.manual_seed(seed)
+
+
+def _refuse(mcmc, diagonal=True):
+    if mcmc:
+        raise NotImplementedError("mcmc=True needs stan, which is not on the HIP path")
+    if not diagonal:
+        raise NotImplementedError("diagonal=False (full Laplace precision) is not on the HIP path")
+
+
+class _Laplace:
+    """Device side of one Laplace-baseline run: the augmented train and test
+    rows, the host noise draws and the two library entries."""
+
+    def __init__(self, x, y, xt, yt, mc_samples, noise_source):
+        self.device = _device()
+        f32 = dict(device=self.device, dtype=torch.float32)
+        x, xt = x.detach().to(**f32), xt.detach().to(**f32)
+        x, xt = x.reshape(x.shape[0], -1), xt.reshape(xt.shape[0], -1)
+        self.x = torch.cat((x, torch.ones(x.shape[0], 1, **f32)), dim=1).contiguous()
+        self.xt = torch.cat((xt, torch.ones(xt.shape[0], 1, **f32)), dim=1).contiguous()
+        self.y, self.yt = y.detach().to(**f32).contiguous(), yt.detach().to(**f32)
+        self.N, self.d = int(self.x.shape[0]), int(self.x.shape[1])
+        self.S, self.noise_source = int(mc_samples), noise_source
+
+    def draw(self, *shape):
+        """A host draw of the reference (Normal.rsample on the CPU generator)."""
+        n = int(np.prod(shape))
+        if self.noise_source is not None:
+            out = torch.as_tensor(self.noise_source(n), dtype=torch.float32).reshape(-1)
+            if out.numel() != n:
+                raise ValueError(f"noise_source returned {out.numel()} draws, expected {n}")
+        else:
+            out = torch.empty(n).normal_()
+        return out.reshape(shape).to(self.device).contiguous()
+
+    def fit(self, theta, xc, yc, wc, T, lr, want_loss=False):
+        """T Adam steps on theta (in place), then S samples: (samples, loss)."""
+        out = laplace_fit(xc, yc, wc, theta, T, lr, eps=self.draw(self.S, self.d),
+                          want_loss=want_loss)
+        return out["samples"], out["loss"]
+
+    def run_laplace(self, theta, xc, yc, wc, T, lr, seed=0):
+        """baselines.py:35-70: reseeds every generator first."""
+        _reseed(seed)
+        return self.fit(theta, xc, yc, wc, T, lr)[0]
+
+    def predict(self, samples):
+        """logreg_forward and the test metrics: (accuracy, mean NLL)."""
+        probs = (self.xt @ samples.T).sigmoid().mean(dim=1)
+        acc = probs.gt(0.5).float().eq(self.yt).float().mean().item()
+        nll = (-torch.distributions.Bernoulli(probs=probs).log_prob(self.yt).mean()).item()
+        return acc, nll
+
+    def minibatch(self, B, batch_source):
+        idx = batch_source() if batch_source is not None else np.random.randint(self.N, size=B)
+        idx = np.asarray(idx, dtype=np.int64)
+        return idx, torch.as_tensor(idx, device=self.device)
+
+    def scores(self, samples, xc, yc, wc, sub_t, **want):
+        rows = torch.cat((xc, self.x[sub_t])).contiguous()
+        labels = torch.cat((yc, self.y[sub_t])).contiguous()
+        return laplace_scores(samples, rows, labels, wc, int(xc.shape[0]),
+                              self.N / int(sub_t.numel()), **want)
+
+
+def run_random(x=None, y=None, xt=None, yt=None, mc_samples=4, num_epochs=100, log_every=10,
+               N=None, D=None, seed=0, mcmc=False, lr0net=1e-3, noise_source=None,
+               choice_source=None, state_out=None, **kwargs):
+    """A Laplace fit on a uniformly random subset of the training data that
+    grows by one point per epoch (baselines.py:118-203).  Returns the
+    reference's results dict {accs, nlls, csizes, times, wt_index}."""
+    _refuse(mcmc)
+    check_binary(y, "y")
+    _reseed(seed)
+    L = _Laplace(x, y, xt, yt, mc_samples, noise_source)
+    N = L.N
+    w = torch.zeros(N, device=L.device)
+    nlls, accs, csizes, times, core_idcs = [], [], [], [0], []
+    log_core_idcs, log_core_wts = [], []
+    theta = None
+    t_start = time.time()
+    for it in range(num_epochs):
+        if it % log_every == 0:
+            ci = torch.as_tensor(np.asarray(core_idcs, dtype=np.int64), device=L.device)
+            theta = L.draw(L.d)  # drawn before run_laplace reseeds
+            smp = L.run_laplace(theta, L.x[ci].contiguous(), L.y[ci].contiguous(),
+                                w[ci].contiguous(), 1000, lr0net, seed=seed)
+            times.append(times[-1] + time.time() - t_start)
+            acc, nll = L.predict(smp)
+            nlls.append(nll), accs.append(acc), csizes.append(len(core_idcs))
+            log_core_idcs.append(core_idcs.copy())
+            log_core_wts.append(w.cpu().numpy().tolist())
+        candidates = tuple(set(range(N)).difference(set(core_idcs)))
+        pt = choice_source(candidates) if choice_source is not None else random.choice(candidates)
+        core_idcs.append(int(pt))
+        w[torch.as_tensor(core_idcs, device=L.device)] = N / len(core_idcs)
+    if state_out is not None:
+        state_out.update(w=w.cpu().numpy(), core_idcs=list(core_idcs),
+                         theta=None if theta is None else theta.cpu().numpy())
+    return {"accs": accs, "nlls": nlls, "csizes": csizes, "times": times[1:],
+            "wt_index": process_wt_index(log_core_idcs, log_core_wts)}
+
+
+def run_sparsevi(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibatch=128,
+                 num_epochs=100, log_every=10, N=None, D=None, diagonal=True, inner_it=10,
+                 outer_it=10, lr0net=1e-3, lr0v=1e-1, seed=0, mcmc=False, noise_source=None,
+                 batch_source=None, state_out=None, **kwargs):
+    """Sparse VI (Campbell & Beronov, 2019; baselines.py:426-648): per epoch a
+    Laplace fit on the coreset, the greedy pick of the minibatch point whose
+    centred log-likelihood correlates best with the residual, and ``outer_it``
+    projected Adam steps on the weights, each after a fit of its own.  Returns
+    the reference's results dict {nlls, accs, csizes, times, wt_index}."""
+    _refuse(mcmc, diagonal)
+    check_binary(y, "y")
+    outer_it = min(outer_it, 500)
+    _reseed(seed)
+    L = _Laplace(x, y, xt, yt, mc_samples, noise_source)
+    N, B = L.N, int(data_minibatch)
+    w = torch.zeros(N, device=L.device, requires_grad=True)
+    nlls, accs, csizes, times, core_idcs = [], [], [], [0], []
+    log_core_idcs, log_core_wts = [], []
+    theta = None
+
+    def core():
+        ci = torch.as_tensor(np.asarray(core_idcs, dtype=np.int64), device=L.device)
+        return ci, L.x[ci].contiguous(), L.y[ci].contiguous(), w.detach()[ci].contiguous()
+
+    t_start = time.time()
+    for it in range(num_epochs):
+        ci, xc, yc, wc = core()
+        if it % log_every == 0:
+            theta = L.draw(L.d)  # drawn before run_laplace reseeds (with its default, 0)
+            smp = L.run_laplace(theta, xc, yc, wc, 1000, lr0net)
+            times.append(times[-1] + time.time() - t_start)
+            acc, nll = L.predict(smp)
+            nlls.append(nll), accs.append(acc), csizes.append(len(core_idcs))
+            log_core_idcs.append(core_idcs.copy())
+            log_core_wts.append(w.detach().cpu().numpy().tolist())
+        # 1. the coreset posterior; 2. log-likelihoods; 3. the point to attach
+        sub, sub_t = L.minibatch(B, batch_source)
+        theta = L.draw(L.d)
+        smp, _ = L.fit(theta, xc, yc, wc, inner_it, lr0net)
+        res = L.scores(smp, xc, yc, wc, sub_t)["result"].tolist()
+        if res[3] > 0:
+            pt = int(sub[int(res[1])])
+            if pt not in core_idcs:
+                core_idcs.append(pt)
+        # 4. projected Adam steps on the weights, a fit before each
+        ci, xc, yc, _ = core()
+        optim_w = torch.optim.Adam([w], lr0v)
+        theta = L.draw(L.d)
+        for _ in range(outer_it):
+            wc = w.detach()[ci].contiguous()
+            smp, _ = L.fit(theta, xc, yc, wc, inner_it, lr0net)
+            sub, sub_t = L.minibatch(B, batch_source)
+            gw = L.scores(smp, xc, yc, wc, sub_t, want_grad_w=True)["grad_w"]
+            w.grad = torch.zeros_like(w)
+            w.grad[ci] = gw
+            optim_w.step()
+            with torch.no_grad():
+                torch.clamp_(w, 0)
+    if state_out is not None:
+        state_out.update(w=w.detach().cpu().numpy(), core_idcs=[int(i) for i in core_idcs],
+                         theta=None if theta is None else theta.cpu().numpy())
+    return {"nlls": nlls, "accs": accs, "csizes": csizes, "times": times[1:],
+            "wt_index": process_wt_index(log_core_idcs, log_core_wts)}
+
+
+def run_opsvi(x=None, y=None, xt=None, yt=None, mc_samples=10, data_minibatch=128,
+              num_epochs=100, log_every=10, N=None, D=None, num_pseudo=10, inner_it=10,
+              diagonal=True, lr0net=1e-3, lr0u=1e-3, lr0v=1e-3, register_elbos=False,
+              init_args="subsample", seed=0, mcmc=False, log_pseudodata=False,
+              noise_source=None, batch_source=None, state_out=None, **kwargs):
+    """The original PSVI construction (Manousakas et al., 2020;
+    baselines.py:652-821): ``num_pseudo`` weighted pseudo-points (u, z), a
+    Laplace fit on them every epoch, then one Adam step on the weights and one
+    on the pseudo-inputs.  Returns the reference's results dict {accs, nlls,
+    csizes, times, elbos} (+ us, zs, vs under log_pseudodata)."""
+    _refuse(mcmc, diagonal)
+    _reseed(seed)
+    L = _Laplace(x, y, xt, yt, mc_samples, noise_source)
+    N, B = L.N, int(data_minibatch)
+    csizes, elbos, n_logged = [], [], 0
+    nlls, accs, times = [], [], [0]
+    w = (N / num_pseudo * torch.ones(num_pseudo, device=L.device)).requires_grad_(True)
+    theta = L.draw(L.d)
+    init = pseudo_rand_init if init_args == "random" else pseudo_subsample_init
+    with torch.no_grad():
+        u0, z0 = init(x.detach().cpu().float().reshape(N, -1), y.detach().cpu(),
+                      num_pseudo=num_pseudo, seed=seed)
+    u = torch.cat((u0.detach().float(), torch.ones(num_pseudo, 1)), dim=1).to(
+        L.device).contiguous().requires_grad_(True)
+    z = z0.float().to(L.device).contiguous()
+    optim_u = torch.optim.Adam([u], lr0u)
+    optim_w = torch.optim.Adam([w], lr0v * N)
+    t_start = time.time()
+    for it in range(num_epochs):
+        if it % log_every == 0:
+            smp = L.run_laplace(theta, u.detach(), z, w.detach(), inner_it, lr0net, seed=seed)
+            times.append(times[-1] + time.time() - t_start)
+            acc, nll = L.predict(smp)
+            csizes.append(num_pseudo), nlls.append(nll), accs.append(acc)
+            n_logged += 1
+        smp, loss = L.fit(theta, u.detach(), z, w.detach(), inner_it, lr0net,
+                          want_loss=register_elbos)
+        if register_elbos:
+            elbos.extend((1, -l) for l in loss.tolist()[::log_every])
+        sub, sub_t = L.minibatch(B, batch_source)
+        sc = L.scores(smp, u.detach(), z, w.detach(), sub_t, want_grad_w=True, want_grad_u=True)
+        w.grad, u.grad = sc["grad_w"], sc["grad_u"]
+        optim_w.step()
+        optim_u.step()
+        with torch.no_grad():
+            torch.clamp_(w, 0)
+    if state_out is not None:
+        state_out.update(w=w.detach().cpu().numpy(), core_idcs=list(range(num_pseudo)),
+                         theta=theta.cpu().numpy(), u=u.detach().cpu().numpy())
+    results = {"accs": accs, "nlls": nlls, "csizes": csizes, "times": times[1:], "elbos": elbos}
+    if log_pseudodata:
+        # the reference logs u.detach().numpy() / w.detach().numpy(): views of the
+        # live tensors, which the in-place optimiser steps keep writing, so every
+        # logged entry holds the final values
+        results["us"] = [u.detach().cpu().numpy()] * n_logged
+        results["zs"] = [z.cpu().numpy()] * n_logged
+        results["vs"] = [w.detach().cpu().numpy()] * n_logged
+    return results

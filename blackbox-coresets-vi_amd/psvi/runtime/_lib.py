@@ -72,6 +72,33 @@ class AdamHP(ctypes.Structure):
     ]
 
 
+class LaplaceFitReq(ctypes.Structure):
+    _fields_ = [
+        ("n_core", ctypes.c_int32), ("d", ctypes.c_int32), ("S", ctypes.c_int32),
+        ("T", ctypes.c_int32),
+        ("x_core", ctypes.c_void_p), ("y_core", ctypes.c_void_p), ("w_core", ctypes.c_void_p),
+        ("prior_mean", ctypes.c_float), ("prior_sd", ctypes.c_float),
+        ("theta", ctypes.c_void_p),
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+        ("adam_eps", ctypes.c_double),
+        ("eps", ctypes.c_void_p), ("loss_out", ctypes.c_void_p), ("prec_out", ctypes.c_void_p),
+        ("samples_out", ctypes.c_void_p),
+    ]
+
+
+class LaplaceScoresReq(ctypes.Structure):
+    _fields_ = [
+        ("S", ctypes.c_int32), ("d", ctypes.c_int32), ("n_core", ctypes.c_int32),
+        ("n_data", ctypes.c_int32),
+        ("samples", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+        ("w_core", ctypes.c_void_p),
+        ("sum_scaling", ctypes.c_double),
+        ("corr_out", ctypes.c_void_p), ("corecorr_out", ctypes.c_void_p),
+        ("result_out", ctypes.c_void_p), ("grad_w", ctypes.c_void_p), ("ll_out", ctypes.c_void_p),
+        ("grad_u", ctypes.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -126,6 +153,8 @@ SIGNATURES = {
                                   _P]),
     "psvi_select_weight_grad": (_I32, [_I32, _I32, _I32, _P, _P, _P, ctypes.c_double, _P, _P,
                                        _P]),
+    "psvi_laplace_fit": (_I32, [ctypes.POINTER(LaplaceFitReq), _P]),
+    "psvi_laplace_scores": (_I32, [ctypes.POINTER(LaplaceScoresReq), _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),

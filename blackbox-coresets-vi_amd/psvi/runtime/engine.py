@@ -710,6 +710,80 @@ def select_weight_grad(ll, nkl, w_core, N):
     return loss, gw
 
 
+def laplace_fit(x_core, y_core, w_core, theta, T, lr, eps=None, prior_mean=0.0, prior_sd=1.0,
+                betas=(0.9, 0.999), adam_eps=1e-8, want_loss=False):
+    """The Laplace fit of the coreset baselines (psvi_laplace_fit): T torch-Adam
+    steps from fresh moments on theta (d,), updated in place, for the weighted
+    logistic log-joint of x_core (n_core, d; the ones column included), float
+    labels y_core and weights w_core >= 0 (all None for an empty core).
+    Returns a dict of device tensors: prec (d), samples (S, d; None without
+    eps (S, d)) and loss (T float64: the negative log-joint before each step;
+    None unless want_loss)."""
+    d = int(theta.numel())
+    _need(theta, "theta", d)
+    n_core = 0 if x_core is None else int(x_core.shape[0])
+    if n_core:
+        _need(x_core, "x_core", n_core * d)
+        _need(y_core, "y_core", n_core)
+        _need(w_core, "w_core", n_core)
+    S = 0
+    dev = theta.device
+    if eps is not None:
+        if eps.dim() != 2:
+            raise ValueError("eps must be the (S, d) tensor of draws")
+        S = int(eps.shape[0])
+        _need(eps, "eps", S * d)
+    out = {"prec": torch.empty(d, dtype=torch.float32, device=dev),
+           "samples": torch.empty(S, d, dtype=torch.float32, device=dev) if S else None,
+           "loss": torch.empty(int(T), dtype=torch.float64, device=dev) if want_loss else None}
+    on = bool(n_core)
+    req = _lib.LaplaceFitReq(
+        n_core, d, S, int(T), _ptr(x_core if on else None), _ptr(y_core if on else None),
+        _ptr(w_core if on else None), float(prior_mean), float(prior_sd), _ptr(theta), float(lr),
+        float(betas[0]), float(betas[1]), float(adam_eps), _ptr(eps), _ptr(out["loss"]),
+        _ptr(out["prec"]), _ptr(out["samples"]))
+    check(_lib.load().psvi_laplace_fit(ctypes.byref(req), _stream()), "psvi_laplace_fit")
+    _wrote(theta)
+    return out
+
+
+def laplace_scores(samples, rows, labels, w_core, n_core, sum_scaling, want_grad_w=False,
+                   want_ll=False, want_grad_u=False):
+    """Selection scores and gradients of the Laplace baselines
+    (psvi_laplace_scores) from samples (S, d), rows (n_core + n_data, d; core
+    rows first), their float labels and w_core.  Returns a dict of device
+    tensors: corr (n_data), corecorr (n_core, None at 0), result (4 float64:
+    max corr, its first arg, max corecorr, attach) and, on request, grad_w
+    (n_core), ll (S, n_core + n_data) and grad_u (n_core, d)."""
+    if samples is None or samples.dim() != 2 or rows is None or rows.dim() != 2:
+        raise ValueError("samples must be (S, d) and rows (n_core + n_data, d)")
+    S, d = int(samples.shape[0]), int(samples.shape[1])
+    n_core = int(n_core)
+    M = int(rows.shape[0])
+    n_data = M - n_core
+    _need(samples, "samples", S * d)
+    _need(rows, "rows", M * d)
+    _need(labels, "labels", M)
+    if n_core:
+        _need(w_core, "w_core", n_core)
+    dev = samples.device
+
+    def new(*shape, on=True, dtype=torch.float32):
+        return torch.empty(*shape, dtype=dtype, device=dev) if on else None
+
+    out = {"corr": new(max(n_data, 0)), "corecorr": new(n_core, on=n_core > 0),
+           "result": new(4, dtype=torch.float64),
+           "grad_w": new(n_core, on=want_grad_w and n_core > 0),
+           "ll": new(S, M, on=want_ll), "grad_u": new(n_core, d, on=want_grad_u and n_core > 0)}
+    req = _lib.LaplaceScoresReq(
+        S, d, n_core, n_data, _ptr(samples), _ptr(rows), _ptr(labels),
+        _ptr(w_core if n_core else None), float(sum_scaling), _ptr(out["corr"]),
+        _ptr(out["corecorr"]), _ptr(out["result"]), _ptr(out["grad_w"]), _ptr(out["ll"]),
+        _ptr(out["grad_u"]))
+    check(_lib.load().psvi_laplace_scores(ctypes.byref(req), _stream()), "psvi_laplace_scores")
+    return out
+
+
 def randn_(out, seed, offset=0):
     """Fill a float32 device tensor with N(0,1) (Philox4x32-10 + Box-Muller)."""
     _need(out, "out", None)

@@ -534,6 +534,87 @@ int psvi_select_weight_grad(int32_t S, int32_t n_core, int32_t n_data, const flo
                             const double* nkl, const float* w_core, double N, double* loss_out,
                             float* grad_w, void* stream);
 
+/* ---- Laplace coreset baselines (random, sparsevi, opsvi) -----------------
+ * The Laplace fit of a weighted logistic regression on the coreset
+ * (run_laplace, psvi/inference/baselines.py:35-70; model and
+ * laplace_precision, psvi/models/logreg.py:17-26, 95-107), one launch of one
+ * workgroup for the whole fit.  x_core ([n_core][d], d = D + 1: the caller
+ * appends the ones column), y_core (n_core FLOAT labels: the likelihood is
+ * y f - softplus(f) for any float y), w_core (n_core floats, >= 0), the prior
+ * N(prior_mean, prior_sd^2) on every coordinate, theta (d floats, in / out).
+ * T steps of torch.optim.Adam (PSVI_ADAM_TORCH arithmetic: step = lr / bc1,
+ * denom = sqrt(v) / sqrt(bc2) + adam_eps) from zero moments and step count 0
+ * -- every fit of the baselines starts from a new optimiser -- on
+ *   loss = -sum_m w_m (y_m f_m - softplus(f_m)) - sum_j log N(theta_j),  f = x theta
+ *   g    = -x^T (w o (y - sigmoid(f))) + (theta - prior_mean) / prior_sd^2
+ * and then
+ *   loss_out    (T doubles, nullable)  <- the loss before each step
+ *   prec_out    (d floats)             <- 1 + sum_m w_m p_m (1 - p_m) x_mj^2 at the final theta
+ *   samples_out ([S][d] floats)        <- theta + prec^(-1/2) o eps_s, written iff eps
+ *                                         ([S][d] floats, nullable) is given
+ * theta, the moments and every sum are fp64 inside the kernel, each sum with
+ * one owner and a fixed order: bitwise reproducible; no atomics.  x_core stays
+ * in LDS when n_core * d floats fit beside the state (160 KiB) and is read
+ * from global memory otherwise.
+ * Ranges (PSVI_EINVAL outside them): 2 <= d <= 256, 0 <= n_core <= 4096 (the
+ * core pointers may be NULL at 0: the prior alone drives theta, prec = 1),
+ * 0 <= S <= 2048 (S >= 1 with eps), 0 <= T <= 1048576, lr / betas / adam_eps /
+ * prior_sd finite and > 0 (betas < 1).  A negative or NaN weight is
+ * PSVI_EINVAL too: the entry reads w_core back before the launch, so it
+ * synchronises the stream. */
+typedef struct psvi_laplace_fit_req {
+    int32_t n_core, d, S, T;
+    const float* x_core;
+    const float* y_core;
+    const float* w_core;
+    float prior_mean, prior_sd;
+    float* theta;
+    double lr, beta1, beta2, adam_eps;
+    const float* eps;
+    double* loss_out;
+    float* prec_out;
+    float* samples_out;
+} psvi_laplace_fit_req;
+int psvi_laplace_fit(const psvi_laplace_fit_req* req, void* stream);
+
+/* The selection scores and gradients of the Laplace baselines
+ * (baselines.py:550-575, 617-635, 783-805) from samples ([S][d]), rows
+ * ([n_core + n_data][d], core rows first), labels (n_core + n_data floats),
+ * w_core (n_core floats) and sum_scaling = N / B:
+ *   ll_sj       = y_j f_sj - softplus(f_sj),  f_sj = rows_j . samples_s
+ *   cll_sj      = ll_sj - mean_s ll_sj    (these baselines centre; psvi_select_scores scales)
+ *   resid_s     = sum_scaling sum_n cll_sn - sum_m w_m cll_sm
+ *   corr_n      = (cll_.n . resid) / |cll_.n| / S       -> corr_out (n_data)
+ *   corecorr_m  = |cll_.m . resid| / |cll_.m| / S       -> corecorr_out (n_core)
+ *   result_out (4 doubles) <- as psvi_select_scores: max corr, its first arg,
+ *       max corecorr (-inf when n_core == 0), attach
+ *   grad_w (n_core floats, nullable)  <- -(cll_.m . resid) / S
+ *   ll_out ([S][n_core + n_data] floats, nullable) <- ll
+ *   grad_u ([n_core][d] floats, nullable) <- the gradient with respect to the
+ *       core rows of -(1 / S) sum_s resid_s sum_m w_m cll_sm at constant resid
+ *       (opsvi's u_function): -(w_m / S) sum_s (resid_s - mean resid)
+ *       (y_m - sigmoid(f_sm)) samples_s, its last (ones) column set to 0
+ * ll is rounded to float before any sum uses it (ll_out holds exactly the
+ * values summed); the sums run in fp64 in a fixed order: bitwise reproducible.
+ * Ranges (PSVI_EINVAL outside them): 2 <= S <= 2048, 2 <= d <= 256,
+ * n_core >= 0 (w_core / corecorr_out / grad_w / grad_u may be NULL at 0),
+ * n_data >= 1, n_core + n_data <= 2048. */
+typedef struct psvi_laplace_scores_req {
+    int32_t S, d, n_core, n_data;
+    const float* samples;
+    const float* rows;
+    const float* labels;
+    const float* w_core;
+    double sum_scaling;
+    float* corr_out;
+    float* corecorr_out;
+    double* result_out;
+    float* grad_w;
+    float* ll_out;
+    float* grad_u;
+} psvi_laplace_scores_req;
+int psvi_laplace_scores(const psvi_laplace_scores_req* req, void* stream);
+
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's
  * objective, KL included) at fixed eps, world == 1:

@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""Times the Laplace fit (psvi_laplace_fit) at Nu = 100, d = 65, T = 1000 with
+hipEvents, and the reference's ``run_laplace`` on the CPU for the same problem.
+Not a test and not read by bench.py.
+
+  python tools/laplace_probe.py                 the kernel (needs a HIP device)
+  PSVI_REFERENCE=<tree> python tools/laplace_probe.py --reference
+                                                the reference on this CPU
+
+One process, warm-up launches first, the median of the timed repeats reported;
+each mode prints one JSON line with the machine it ran on."""
+import argparse
+import json
+import os
+import platform
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+NU, D, T, S, LR = 100, 65, 1000, 4, 1e-3
+
+
+def problem():
+    g = torch.Generator().manual_seed(0)
+    x = torch.cat((torch.randn(NU, D - 1, generator=g), torch.ones(NU, 1)), dim=1)
+    y = (torch.rand(NU, generator=g) > 0.5).float()
+    w = 0.5 + 2 * torch.rand(NU, generator=g)
+    return x, y, w, torch.randn(D, generator=g), torch.randn(S, D, generator=g)
+
+
+def gpu(warmup, reps):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
+                                    "blackbox-coresets-vi_amd"))
+    from psvi.runtime import laplace_fit
+
+    x, y, w, theta0, eps = (t.cuda().contiguous() for t in problem())
+    times = []
+    for i in range(warmup + reps):
+        theta = theta0.clone()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        laplace_fit(x, y, w, theta, T, LR, eps=eps)
+        b.record()
+        b.synchronize()
+        if i >= warmup:
+            times.append(a.elapsed_time(b))
+    print(json.dumps(dict(what="psvi_laplace_fit", Nu=NU, d=D, T=T, reps=reps,
+                          median_ms=statistics.median(times), min_ms=min(times),
+                          max_ms=max(times), us_per_step=1e3 * statistics.median(times) / T,
+                          device=torch.cuda.get_device_name(0))))
+
+
+def reference(reps):
+    ref = os.environ.get("PSVI_REFERENCE")
+    if not ref or not os.path.isdir(ref):
+        raise SystemExit("set PSVI_REFERENCE to the reference tree")
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from gen_golden import _install_stubs
+
+    _install_stubs()
+    sys.path.insert(0, ref)
+    import psvi.inference.baselines as RB
+
+    x, y, w, theta0, _ = problem()
+    mu0, sigma0 = torch.zeros(D), torch.ones(D)
+    times = []
+    for i in range(1 + reps):
+        theta = torch.nn.Parameter(theta0.clone(), requires_grad=True)
+        t0 = time.perf_counter()
+        RB.run_laplace(theta, mu0, sigma0, x, y, w, torch.optim.Adam([theta], LR), inner_it=T,
+                       diagonal=True, mc_samples=S, seed=0)
+        if i:
+            times.append(1e3 * (time.perf_counter() - t0))
+    print(json.dumps(dict(what="reference run_laplace (CPU)", Nu=NU, d=D, T=T, reps=reps,
+                          median_ms=statistics.median(times), min_ms=min(times),
+                          threads=torch.get_num_threads(), machine=platform.processor()
+                          or platform.machine(), torch=torch.__version__,
+                          numpy=np.__version__)))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", action="store_true")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    reference(min(a.reps, 5)) if a.reference else gpu(a.warmup, a.reps)
