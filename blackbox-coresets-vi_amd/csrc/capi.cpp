@@ -1349,6 +1349,25 @@ int psvi_laplace_scores(const psvi_laplace_scores_req* q, void* stream) {
     return 0;
 }
 
+int psvi_giga_step(const psvi_giga_step_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    if (q->S < 2 || q->S > 2048 || q->d < 2 || q->d > kLapMaxD || q->n_data < 1 ||
+        q->n_data > kLapMaxRows)
+        return fail(PSVI_EINVAL, "the GIGA step supports 2 <= S <= 2048, 2 <= d <= 256, "
+                                 "1 <= n_data <= 2048");
+    if (!q->samples || !q->rows || !q->labels || !q->lw_in || !q->score_out || !q->lw_out ||
+        !q->result_out)
+        return fail(PSVI_EINVAL, "null pointer");
+    if (q->lw_out < q->lw_in + q->S && q->lw_in < q->lw_out + q->S)
+        return fail(PSVI_EINVAL, "lw_out must not alias lw_in");
+    GigaStep r;
+    r.S = q->S; r.d = q->d; r.n_data = q->n_data;
+    r.samples = q->samples; r.rows = q->rows; r.labels = q->labels; r.lw_in = q->lw_in;
+    r.score = q->score_out; r.lw_out = q->lw_out; r.ll_out = q->ll_out; r.result = q->result_out;
+    HIP_TRY(launch_giga_step(r, as_stream(stream)));
+    return 0;
+}
+
 int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,

@@ -29,6 +29,11 @@
 // Scores: one workgroup as kernels_select.hip, which scales ll by 1 - W_s where
 // these baselines centre it by the per-row mean over the samples.  ll_sj = y_j f_sj -
 // softplus(f_sj) is rounded to float (what ll_out holds) before any sum uses it.
+//
+// GIGA (Campbell & Broderick, 2018; baselines.py:306-322, 362-413): the
+// geodesic direction of every minibatch point on the unit sphere of centred
+// log-likelihood vectors, the greedy pick and the line-search step, one
+// workgroup over the same float-rounded ll (giga_step_kernel below).
 #include "psvi_internal.hpp"
 #include "select_reduce.hpp"
 
@@ -187,12 +192,16 @@ struct LapScoreArgs {
 };
 
 // ll_sj as the float the sums use
-__device__ __forceinline__ double lap_ll(const LapScoreArgs& a, int s, int j) {
-    const float* th = a.samples + (size_t)s * a.d;
-    const float* x = a.rows + (size_t)j * a.d;
+__device__ __forceinline__ double lap_ll(const float* samples, const float* rows,
+                                         const float* labels, int d, int s, int j) {
+    const float* th = samples + (size_t)s * d;
+    const float* x = rows + (size_t)j * d;
     double f = 0.0;
-    for (int k = 0; k < a.d; ++k) f += (double)x[k] * (double)th[k];
-    return (double)(float)lap_loglik((double)a.labels[j], f);
+    for (int k = 0; k < d; ++k) f += (double)x[k] * (double)th[k];
+    return (double)(float)lap_loglik((double)labels[j], f);
+}
+__device__ __forceinline__ double lap_ll(const LapScoreArgs& a, int s, int j) {
+    return lap_ll(a.samples, a.rows, a.labels, a.d, s, j);
 }
 
 __global__ __launch_bounds__(kSelThreads) void laplace_scores_kernel(LapScoreArgs a) {
@@ -284,6 +293,151 @@ hipError_t launch_laplace_scores(const LaplaceScores& r, hipStream_t st) {
     a.corr = r.corr; a.corecorr = r.corecorr; a.grad_w = r.grad_w; a.ll = r.ll_out;
     a.grad_u = r.grad_u; a.result = r.result;
     hipLaunchKernelGGL(laplace_scores_kernel, dim3(1), dim3(kSelThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+struct GigaArgs {
+    int S, d, N;
+    const float *samples, *rows, *labels, *lw;
+    float *score, *lw_out, *ll;
+    double* result;
+};
+
+// One geodesic-ascent step of GIGA in one workgroup.  A thread owns whole
+// columns (data rows: n = tid, tid + 512, ...) or whole samples (s = tid, ...);
+// the vectors over the samples meet in the fixed trees of select_reduce.hpp.
+//   columns: mean_n, 1 / max(|cll_.n|, 1e-12), ell_n . lw            -> LDS
+//   samples: sum_lls_s -> L, ell, zeta1, d = normalize(ell - zeta1 lw) -> LDS
+//   columns: score_n = d . normalize(ell_n - (ell_n . lw) lw), first argmax n*
+//   samples: ell* = ell_n*, zeta0, zeta2, gamma, lw_out, scale
+__global__ __launch_bounds__(kSelThreads) void giga_step_kernel(GigaArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double giga_sm[];
+    __shared__ double red[kSelThreads];
+    __shared__ int redi[kSelThreads];
+    const int S = a.S, d = a.d, N = a.N, tid = threadIdx.x;
+    double* mean = giga_sm;  // [N]
+    double* inv = mean + N;  // [N]
+    double* b = inv + N;     // [N]
+    double* ell = b + N;     // [S]
+    double* dd = ell + S;    // [S]: d, then ell*
+    auto LL = [&](int s, int n) { return lap_ll(a.samples, a.rows, a.labels, d, s, n); };
+    for (int n = tid; n < N; n += kSelThreads) {
+        double sum = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double l = LL(s, n);
+            if (a.ll) a.ll[(size_t)s * N + n] = (float)l;
+            sum += l;
+        }
+        const double m = sum / S;
+        double sq = 0.0, dot = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double c = LL(s, n) - m;
+            sq += c * c;
+            dot += c * (double)a.lw[s];
+        }
+        mean[n] = m;
+        inv[n] = 1.0 / fmax(sqrt(sq), 1e-12);
+        b[n] = dot * inv[n];
+    }
+    __syncthreads();
+    double sq = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        double sum = 0.0;
+        for (int n = 0; n < N; ++n) sum += LL(s, n) - mean[n];
+        ell[s] = sum;
+        sq += sum * sum;
+    }
+    const double L = sqrt(sel_sum(sq, red));
+    double z1 = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        ell[s] /= fmax(L, 1e-12);
+        z1 += ell[s] * (double)a.lw[s];
+    }
+    z1 = sel_sum(z1, red);
+    sq = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        dd[s] = ell[s] - z1 * (double)a.lw[s];
+        sq += dd[s] * dd[s];
+    }
+    const double dnorm = fmax(sqrt(sel_sum(sq, red)), 1e-12);
+    for (int s = tid; s < S; s += kSelThreads) dd[s] /= dnorm;
+    __syncthreads();
+    double best = -INFINITY;
+    int besti = 0x7fffffff;
+    for (int n = tid; n < N; n += kSelThreads) {
+        double num = 0.0, vsq = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double v = (LL(s, n) - mean[n]) * inv[n] - b[n] * (double)a.lw[s];
+            num += v * dd[s];
+            vsq += v * v;
+        }
+        const double v = num / fmax(sqrt(vsq), 1e-12);
+        a.score[n] = (float)v;
+        if (v > best) {  // columns ascending per thread: the first of equal values stays
+            best = v;
+            besti = n;
+        }
+    }
+    sel_argmax_first(best, besti, red, redi);
+    const double smax = red[0];
+    const int ns = redi[0] == 0x7fffffff ? 0 : redi[0];
+    // every thread is past its reads of d (the barriers of the argmax): dd takes ell*
+    double z0 = 0.0, z2 = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        dd[s] = (LL(s, ns) - mean[ns]) * inv[ns];
+        z0 += ell[s] * dd[s];
+        z2 += dd[s] * (double)a.lw[s];
+    }
+    z0 = sel_sum(z0, red);
+    z2 = sel_sum(z2, red);
+    const double gamma = (z0 - z1 * z2) / (z0 - z1 * z2 + z1 - z0 * z2);
+    sq = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        ell[s] = (1.0 - gamma) * (double)a.lw[s] + gamma * dd[s];
+        sq += ell[s] * ell[s];
+    }
+    const double tnorm = fmax(sqrt(sel_sum(sq, red)), 1e-12);
+    // the reference scales the weights by the norm taken with the NEW lw
+    // (baselines.py:405-413: lw is reassigned before the norm is formed)
+    sq = 0.0;
+    for (int s = tid; s < S; s += kSelThreads) {
+        const double l = ell[s] / tnorm;
+        a.lw_out[s] = (float)l;
+        const double u = (1.0 - gamma) * l + gamma * dd[s];
+        sq += u * u;
+    }
+    const double unorm = sqrt(sel_sum(sq, red));
+    if (tid == 0) {
+        a.result[0] = smax;
+        a.result[1] = (double)ns;
+        a.result[2] = z0;
+        a.result[3] = z1;
+        a.result[4] = z2;
+        a.result[5] = gamma;
+        a.result[6] = 1.0 / unorm;
+        a.result[7] = L;
+    }
+}
+
+hipError_t launch_giga_step(const GigaStep& r, hipStream_t st) {
+    if (r.S < 2 || r.S > kSelMaxS || r.d < 2 || r.d > kLapMaxD || r.n_data < 1 ||
+        r.n_data > kLapMaxRows)
+        return hipErrorInvalidValue;
+    GigaArgs a{};
+    a.S = r.S; a.d = r.d; a.N = r.n_data;
+    a.samples = r.samples; a.rows = r.rows; a.labels = r.labels; a.lw = r.lw_in;
+    a.score = r.score; a.lw_out = r.lw_out; a.ll = r.ll_out; a.result = r.result;
+    // above the 64 KiB a launch gets unasked at the range's far corner
+    constexpr size_t max_lds = sizeof(double) * (3 * (size_t)kLapMaxRows + 2 * (size_t)kSelMaxS);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)giga_step_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    const size_t lds = sizeof(double) * (3 * (size_t)r.n_data + 2 * (size_t)r.S);
+    hipLaunchKernelGGL(giga_step_kernel, dim3(1), dim3(kSelThreads), lds, st, a);
     return hipGetLastError();
 }
 

@@ -834,6 +834,19 @@ struct LaplaceScores {
     float* grad_u = nullptr;    // [Nu][d], nullable
 };
 hipError_t launch_laplace_scores(const LaplaceScores& r, hipStream_t st);
+// one geodesic-ascent step of GIGA from samples [S][d] and the minibatch rows
+struct GigaStep {
+    int S = 0, d = 0, n_data = 0;
+    const float* samples = nullptr;
+    const float* rows = nullptr;    // [n_data][d]
+    const float* labels = nullptr;  // [n_data]
+    const float* lw_in = nullptr;   // [S]
+    float* score = nullptr;         // [n_data]
+    float* lw_out = nullptr;        // [S], not lw_in
+    float* ll_out = nullptr;        // [S][n_data], nullable
+    double* result = nullptr;       // [8]
+};
+hipError_t launch_giga_step(const GigaStep& r, hipStream_t st);
 // outer objective (kernels_outer.hip)
 hipError_t launch_outer_stats(const psvi_plan& p, const float* params, const float* eps,
                               const float* x, double* stats, hipStream_t st);

@@ -25,7 +25,7 @@ def _psvi(cls):
 # classes run on the HIP path (psvi.inference.PSVI_regressor,
 # PSVILearnV_regressor, PSVIAV_regressor), but the reference's regression
 # datasets are remote downloads and read_dataset returns no y_mean / y_std --
-# and giga, whose geodesic step is not on the HIP path.  sparsebbvi runs on it
+# and giga (psvi.inference.run_giga runs on the HIP path; call it directly).  sparsebbvi runs on it
 # (Bernoulli plans, one output), and so do the Laplace baselines random,
 # sparsevi and opsvi (psvi_laplace_fit, psvi_laplace_scores).
 inf_dict = {

@@ -50,11 +50,34 @@ reference's order and uploaded with the request.  Reference behaviours kept:
   values.
 * ``run_random`` sets ``w[core] = N / len(core)``.
 
+  run_giga      baselines.py:207-423   GIGA (Campbell & Broderick, 2018)
+
+GIGA shares the Laplace fit; its geodesic direction, greedy pick and line
+search are one launch of psvi_giga_step per step.  Reference behaviours kept:
+
+* ``mc_samples = max(mc_samples, 50)``.
+* The posterior samples come once, from a 1000-step Laplace fit on
+  ``subset_size`` random rows with weights ``N / data_minibatch``; every step
+  works on those samples.
+* The geodesic step sits inside ``if it % log_every == 0``: the coreset grows
+  only on logging iterations (a minibatch is still drawn on the others).
+* The logging fit takes 100 steps on ``w[core]`` (``w_pred`` is computed but
+  read by the mcmc branch only), from a fresh theta0 drawn before
+  ``run_laplace``'s reseed; an empty core fits the prior alone.
+* ``run_laplace`` reseeds with ``seed`` on every call, so the
+  ``np.random.randint`` minibatches after a logging step restart from it.
+* ``csizes`` logs ``len(w[w > 0])`` before that iteration's step.
+* ``w = clamp(((1 - gamma) w + gamma e_pt) / |(1 - gamma) lw + gamma ell*|, 0)``
+  on the full w (N,), the norm taken with the already updated lw.
+* The minibatch is drawn with replacement, the first occurrence wins the
+  argmax, and a point already in the core is not appended again.
+
 ``mcmc=True`` (stan) and ``diagonal=False`` raise NotImplementedError.
 Optional test hooks: ``noise_source(n)`` supplies each host draw,
 ``batch_source()`` the ``np.random.randint`` minibatches,
 ``choice_source(candidates)`` run_random's ``random.choice``; ``state_out`` (a
-dict) receives the final w, core_idcs, theta and, for opsvi, u.
+dict) receives the final w, core_idcs, theta and, for opsvi, u (for giga: w,
+core_idcs, lw and pt_idcs, the point picked at each step).
 """
 import random
 import time
@@ -66,11 +89,12 @@ from torch.utils.data import DataLoader
 
 from ..models import (VILinear, VILinearMultivariateNormal, categorical_fn, make_fc2net,
                       make_fcnet, make_lenet, model_spec)
-from ..runtime import (InnerLoopPlan, adam_update_, check_binary, laplace_fit, laplace_scores,
-                       randn_)
+from ..runtime import (InnerLoopPlan, adam_update_, check_binary, giga_step, laplace_fit,
+                       laplace_scores, randn_)
 
 __all__ = ["set_up_model", "pseudo_subsample_init", "pseudo_rand_init", "run_mfvi",
-           "run_mfvi_subset", "process_wt_index", "run_random", "run_sparsevi", "run_opsvi"]
+           "run_mfvi_subset", "process_wt_index", "run_random", "run_sparsevi", "run_opsvi",
+           "run_giga"]
 
 
 def set_up_model(D=None, n_hidden=None, nc=None, mc_samples=None, architecture=None,
@@ -383,6 +407,56 @@ def run_random(x=None, y=None, xt=None, yt=None, mc_samples=4, num_epochs=100, l
                          theta=None if theta is None else theta.cpu().numpy())
     return {"accs": accs, "nlls": nlls, "csizes": csizes, "times": times[1:],
             "wt_index": process_wt_index(log_core_idcs, log_core_wts)}
+
+
+def run_giga(x=None, y=None, xt=None, yt=None, mc_samples=100, data_minibatch=512,
+             num_epochs=100, log_every=10, N=None, D=None, seed=0, mcmc=False, subset_size=200,
+             lr0net=1e-3, noise_source=None, batch_source=None, state_out=None, **kwargs):
+    """GIGA (Campbell & Broderick, 2018; baselines.py:207-423): posterior samples
+    from one Laplace fit on a random subset, then on every logging iteration a
+    fit on the coreset and one geodesic-ascent step on the minibatch: the point
+    whose direction aligns best with the residual's is attached and the weights
+    follow the line search.  Returns the reference's results dict {accs, nlls,
+    csizes, times}."""
+    _refuse(mcmc)
+    check_binary(y, "y")
+    _reseed(seed)
+    L = _Laplace(x, y, xt, yt, max(mc_samples, 50), noise_source)
+    N, B = L.N, int(data_minibatch)
+    w = torch.zeros(N, device=L.device)
+    nlls, accs, csizes, times, core_idcs, pt_idcs = [], [], [], [0], [], []
+    t_start = time.time()
+    _, sub_t = L.minibatch(int(subset_size), batch_source)
+    theta = L.draw(L.d)  # drawn before run_laplace reseeds
+    smp = L.run_laplace(theta, L.x[sub_t].contiguous(), L.y[sub_t].contiguous(),
+                        torch.full((sub_t.numel(),), N / B, device=L.device), 1000, lr0net,
+                        seed=seed)
+    lw = torch.zeros(L.S, device=L.device)
+    for it in range(num_epochs):
+        sub, sub_t = L.minibatch(B, batch_source)
+        if it % log_every:
+            continue
+        ci = torch.as_tensor(np.asarray(core_idcs, dtype=np.int64), device=L.device)
+        theta = L.draw(L.d)
+        pred = L.run_laplace(theta, L.x[ci].contiguous(), L.y[ci].contiguous(),
+                             w[ci].contiguous(), 100, lr0net, seed=seed)
+        times.append(times[-1] + time.time() - t_start)
+        acc, nll = L.predict(pred)
+        nlls.append(nll), accs.append(acc), csizes.append(int((w > 0).sum()))
+        step = giga_step(smp, L.x[sub_t].contiguous(), L.y[sub_t].contiguous(), lw)
+        res = step["result"].tolist()
+        pt, gamma, scale = int(sub[int(res[1])]), res[5], res[6]
+        pt_idcs.append(pt)
+        if pt not in core_idcs:
+            core_idcs.append(pt)
+        lw = step["lw"]
+        w = (1 - gamma) * w
+        w[pt] += gamma
+        w = torch.clamp_(w * scale, 0)
+    if state_out is not None:
+        state_out.update(w=w.cpu().numpy(), core_idcs=list(core_idcs), lw=lw.cpu().numpy(),
+                         pt_idcs=pt_idcs)
+    return {"accs": accs, "nlls": nlls, "csizes": csizes, "times": times[1:]}
 
 
 def run_sparsevi(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibatch=128,

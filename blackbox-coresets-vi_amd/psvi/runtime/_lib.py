@@ -99,6 +99,16 @@ class LaplaceScoresReq(ctypes.Structure):
     ]
 
 
+class GigaStepReq(ctypes.Structure):
+    _fields_ = [
+        ("S", ctypes.c_int32), ("d", ctypes.c_int32), ("n_data", ctypes.c_int32),
+        ("samples", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+        ("lw_in", ctypes.c_void_p),
+        ("score_out", ctypes.c_void_p), ("lw_out", ctypes.c_void_p), ("ll_out", ctypes.c_void_p),
+        ("result_out", ctypes.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -155,6 +165,7 @@ SIGNATURES = {
                                        _P]),
     "psvi_laplace_fit": (_I32, [ctypes.POINTER(LaplaceFitReq), _P]),
     "psvi_laplace_scores": (_I32, [ctypes.POINTER(LaplaceScoresReq), _P]),
+    "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -784,6 +784,33 @@ def laplace_scores(samples, rows, labels, w_core, n_core, sum_scaling, want_grad
     return out
 
 
+def giga_step(samples, rows, labels, lw, want_ll=False):
+    """One geodesic-ascent step of GIGA (psvi_giga_step) from samples (S, d),
+    the minibatch rows (n_data, d; the ones column included), their float
+    labels and lw (S: the coreset's unit vector, zeros before the first step).
+    Returns a dict of device tensors: score (n_data), lw (S: the new vector),
+    result (8 float64: max score, its first arg, zeta0, zeta1, zeta2, gamma,
+    scale, L) and, on request, ll (S, n_data)."""
+    if samples is None or samples.dim() != 2 or rows is None or rows.dim() != 2:
+        raise ValueError("samples must be (S, d) and rows (n_data, d)")
+    S, d = int(samples.shape[0]), int(samples.shape[1])
+    n_data = int(rows.shape[0])
+    _need(samples, "samples", S * d)
+    _need(rows, "rows", n_data * d)
+    _need(labels, "labels", n_data)
+    _need(lw, "lw", S)
+    dev = samples.device
+    out = {"score": torch.empty(n_data, dtype=torch.float32, device=dev),
+           "lw": torch.empty(S, dtype=torch.float32, device=dev),
+           "result": torch.empty(8, dtype=torch.float64, device=dev),
+           "ll": torch.empty(S, n_data, dtype=torch.float32, device=dev) if want_ll else None}
+    req = _lib.GigaStepReq(S, d, n_data, _ptr(samples), _ptr(rows), _ptr(labels), _ptr(lw),
+                           _ptr(out["score"]), _ptr(out["lw"]), _ptr(out["ll"]),
+                           _ptr(out["result"]))
+    check(_lib.load().psvi_giga_step(ctypes.byref(req), _stream()), "psvi_giga_step")
+    return out
+
+
 def randn_(out, seed, offset=0):
     """Fill a float32 device tensor with N(0,1) (Philox4x32-10 + Box-Muller)."""
     _need(out, "out", None)

@@ -615,6 +615,45 @@ typedef struct psvi_laplace_scores_req {
 } psvi_laplace_scores_req;
 int psvi_laplace_scores(const psvi_laplace_scores_req* req, void* stream);
 
+/* One geodesic-ascent step of GIGA (Campbell & Broderick, 2018; run_giga,
+ * baselines.py:306-322, 362-413) from samples ([S][d]), the minibatch rows
+ * ([n_data][d], ones column appended by the caller), labels (n_data floats)
+ * and lw_in (S floats: the coreset's current unit vector, all zeros before
+ * the first step); normalize(v) = v / max(|v|, 1e-12) as F.normalize:
+ *   ll_sn    = y_n f_sn - softplus(f_sn),  cll_sn = ll_sn - mean_s ll_sn
+ *   sum_lls  = sum_n cll_.n,  L = |sum_lls|,  ell = normalize(sum_lls)
+ *   ell_n    = normalize(cll_.n)
+ *   d        = normalize(ell - (ell . lw) lw)
+ *   d_n      = normalize(ell_n - (ell_n . lw) lw)
+ *   score_n  = d . d_n                              -> score_out (n_data)
+ *   n*       = the first argmax of score,  ell* = ell_n*
+ *   zeta0    = ell . ell*,  zeta1 = ell . lw,  zeta2 = ell* . lw
+ *   gamma    = (zeta0 - zeta1 zeta2) / (zeta0 - zeta1 zeta2 + zeta1 - zeta0 zeta2)
+ *   lw_out   = normalize((1 - gamma) lw + gamma ell*)   (S floats, not lw_in)
+ *   scale    = 1 / |(1 - gamma) lw_out + gamma ell*|
+ *   result_out (8 doubles) <- max score, n*, zeta0, zeta1, zeta2, gamma, scale, L
+ *   ll_out ([S][n_data] floats, nullable) <- ll
+ * scale divides the reference's weight update, w <- ((1 - gamma) w + gamma
+ * e_pt) scale; it is taken with the NEW lw because the reference reassigns lw
+ * before it forms that norm.  The attached point is a row of the minibatch
+ * and the samples are fixed over a run, so ell* needs no core rows.
+ * ll is rounded to float before any sum uses it; the sums run in fp64 in a
+ * fixed order with one owner each: bitwise reproducible, no atomics.
+ * Ranges (PSVI_EINVAL outside them): 2 <= S <= 2048, 2 <= d <= 256,
+ * 1 <= n_data <= 2048; lw_out overlapping lw_in is PSVI_EINVAL. */
+typedef struct psvi_giga_step_req {
+    int32_t S, d, n_data;
+    const float* samples;
+    const float* rows;
+    const float* labels;
+    const float* lw_in;
+    float* score_out;
+    float* lw_out;
+    float* ll_out;
+    double* result_out;
+} psvi_giga_step_req;
+int psvi_giga_step(const psvi_giga_step_req* req, void* stream);
+
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's
  * objective, KL included) at fixed eps, world == 1:
