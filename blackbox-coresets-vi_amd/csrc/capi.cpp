@@ -18,34 +18,7 @@
 #include "psvi_internal.hpp"
 
 namespace psvi {
-void net_set_lds_limit();                // kernels_net.hip
-extern int g_net_ablation;               // kernels_net.hip
-extern int g_net_scalar_loads;           // kernels_net.hip
-extern unsigned long long* g_net_stamps; // kernels_net.hip
-extern uint16_t* g_net_draw_planes;      // kernels_net.hip
-extern int g_net_draw_role1;             // kernels_net.hip
-extern int g_net_draw_spare_off;         // kernels_net.hip
-extern int g_upd_ablation;               // kernels_mvn.hip
-extern int g_stream_off;                 // kernels_mvn.hip
-extern int g_stream_bf_off;              // kernels_mvn.hip
-extern unsigned long long* g_bf_stamps;  // kernels_mvn.hip
-extern int g_ks_off;                     // kernels_mvn.hip
-extern int g_fs_off;                     // kernels_mvn.hip
-extern int g_fwd_pair_bf;                  // kernels_mvn.hip
-extern int g_stream_fold_off;              // kernels_mvn.hip
-extern int g_fs_bf_off;                  // kernels_mvn.hip
-extern int g_ks_bf_off;                  // kernels_mvn.hip
-extern int g_lenet_abl;                  // kernels_lenet.hip
-extern int g_net_split_below;            // kernels_net.hip
-extern int g_net_threads;                // kernels_net.hip
-extern int g_net_wg_target;              // kernels_net.hip
-extern int g_net_mloop_off;              // kernels_net.hip
-extern int g_net_geo_off;                // kernels_net.hip
-extern int g_fwd_ablation;               // kernels_mvn.hip
-extern unsigned long long* g_fwd_stamps; // kernels_mvn.hip
-extern unsigned long long* g_upd_stamps; // kernels_mvn.hip
-extern unsigned long long* g_rop_stamps; // kernels_rop.hip
-extern int g_rop_valu;                     // kernels_rop.hip
+Diag g_diag;
 }  // namespace psvi
 
 using namespace psvi;
@@ -188,40 +161,40 @@ const char* psvi_version(void) { return "psvi_hip 0.1.0 (gfx950)"; }
 int psvi_debug_set(int32_t key, int32_t value) {
     switch (key) {
         case PSVI_DBG_LOOP_TIMING: loop_events_clear(); g_loop_every = value; return 0;
-        case PSVI_DBG_NET_ABLATION: g_net_ablation = value; return 0;
-        case PSVI_DBG_UPD_ABLATION: g_upd_ablation = value; return 0;
-        case PSVI_DBG_NET_SPLIT_BELOW: g_net_split_below = value; return 0;
+        case PSVI_DBG_NET_ABLATION: g_diag.net_ablation = value; return 0;
+        case PSVI_DBG_UPD_ABLATION: g_diag.upd_ablation = value; return 0;
+        case PSVI_DBG_NET_SPLIT_BELOW: g_diag.net_split_below = value; return 0;
         case PSVI_DBG_NET_WG_TARGET:
             if (value < 1) return fail(PSVI_EINVAL, "workgroup target must be >= 1");
-            g_net_wg_target = value;
+            g_diag.net_wg_target = value;
             return 0;
-        case PSVI_DBG_FWD_ABLATION: g_fwd_ablation = value; return 0;
+        case PSVI_DBG_FWD_ABLATION: g_diag.fwd_ablation = value; return 0;
         case PSVI_DBG_UPD_CHUNK: g_plan_dbg.upd_chunk_tiles = value; return 0;
-        case PSVI_DBG_UPD_STREAM_OFF: g_stream_off = value; return 0;
-        case PSVI_DBG_STREAM_BF_OFF: g_stream_bf_off = value; return 0;
-        case PSVI_DBG_KSTREAM_OFF: g_ks_off = value; return 0;
+        case PSVI_DBG_UPD_STREAM_OFF: g_diag.stream_off = value; return 0;
+        case PSVI_DBG_STREAM_BF_OFF: g_diag.stream_bf_off = value; return 0;
+        case PSVI_DBG_KSTREAM_OFF: g_diag.ks_off = value; return 0;
         case PSVI_DBG_KSTREAM_WGS: g_plan_dbg.ks_wgs = value; return 0;
-        case PSVI_DBG_FWD_SEG_OFF: g_fs_off = value; return 0;
-        case PSVI_DBG_FWD_SEG_BF_OFF: g_fs_bf_off = value; return 0;
-        case PSVI_DBG_FWD_PAIR_BF: g_fwd_pair_bf = value; return 0;
-        case PSVI_DBG_STREAM_FOLD_OFF: g_stream_fold_off = value; return 0;
-        case PSVI_DBG_KSTREAM_BF_OFF: g_ks_bf_off = value; return 0;
-        case PSVI_DBG_ROP_VALU: g_rop_valu = value; return 0;
-        case PSVI_DBG_NET_SCALAR_LOADS: g_net_scalar_loads = value; return 0;
-        case PSVI_DBG_NET_MLOOP_OFF: g_net_mloop_off = value; return 0;
-        case PSVI_DBG_NET_GEO_OFF: g_net_geo_off = value; return 0;
-        case PSVI_DBG_NET_DRAW_SPARE_OFF: g_net_draw_spare_off = value; return 0;
+        case PSVI_DBG_FWD_SEG_OFF: g_diag.fs_off = value; return 0;
+        case PSVI_DBG_FWD_SEG_BF_OFF: g_diag.fs_bf_off = value; return 0;
+        case PSVI_DBG_FWD_PAIR_BF: g_diag.fwd_pair_bf = value; return 0;
+        case PSVI_DBG_STREAM_FOLD_OFF: g_diag.stream_fold_off = value; return 0;
+        case PSVI_DBG_KSTREAM_BF_OFF: g_diag.ks_bf_off = value; return 0;
+        case PSVI_DBG_ROP_VALU: g_diag.rop_valu = value; return 0;
+        case PSVI_DBG_NET_SCALAR_LOADS: g_diag.net_scalar_loads = value; return 0;
+        case PSVI_DBG_NET_MLOOP_OFF: g_diag.net_mloop_off = value; return 0;
+        case PSVI_DBG_NET_GEO_OFF: g_diag.net_geo_off = value; return 0;
+        case PSVI_DBG_NET_DRAW_SPARE_OFF: g_diag.net_draw_spare_off = value; return 0;
         case PSVI_DBG_NET_DRAW_ROLE1:
             if (value < 0 || value > 32) return fail(PSVI_EINVAL, "0..32");
-            g_net_draw_role1 = value;
+            g_diag.net_draw_role1 = value;
             return 0;
         case PSVI_DBG_STREAM_WGS: g_plan_dbg.stream_wgs = value; return 0;
         case PSVI_DBG_STREAM_COST: g_plan_dbg.stream_cost = value; return 0;
         case PSVI_DBG_STREAM_RR: g_plan_dbg.stream_rr = value; return 0;
-        case PSVI_DBG_LENET_ABLATION: g_lenet_abl = value; return 0;
+        case PSVI_DBG_LENET_ABLATION: g_diag.lenet_abl = value; return 0;
         case PSVI_DBG_NET_THREADS:
             if (value != 0 && value != 256 && value != 512) return fail(PSVI_EINVAL, "256 or 512");
-            g_net_threads = value;
+            g_diag.net_threads = value;
             return 0;
         default: return fail(PSVI_EINVAL, "unknown debug key");
     }
@@ -248,12 +221,12 @@ int psvi_debug_loop_timing(double* out) {
 
 int psvi_debug_set_ptr(int32_t key, void* ptr) {
     switch (key) {
-        case PSVI_DBG_NET_STAMPS: g_net_stamps = (unsigned long long*)ptr; return 0;
-        case PSVI_DBG_NET_DRAW_PLANES: g_net_draw_planes = (uint16_t*)ptr; return 0;
-        case PSVI_DBG_UPD_STAMPS: g_upd_stamps = (unsigned long long*)ptr; return 0;
-        case PSVI_DBG_BF_STAMPS: g_bf_stamps = (unsigned long long*)ptr; return 0;
-        case PSVI_DBG_ROP_STAMPS: g_rop_stamps = (unsigned long long*)ptr; return 0;
-        case PSVI_DBG_FWD_STAMPS: g_fwd_stamps = (unsigned long long*)ptr; return 0;
+        case PSVI_DBG_NET_STAMPS: g_diag.net_stamps = (unsigned long long*)ptr; return 0;
+        case PSVI_DBG_NET_DRAW_PLANES: g_diag.net_draw_planes = (uint16_t*)ptr; return 0;
+        case PSVI_DBG_UPD_STAMPS: g_diag.upd_stamps = (unsigned long long*)ptr; return 0;
+        case PSVI_DBG_BF_STAMPS: g_diag.bf_stamps = (unsigned long long*)ptr; return 0;
+        case PSVI_DBG_ROP_STAMPS: g_diag.rop_stamps = (unsigned long long*)ptr; return 0;
+        case PSVI_DBG_FWD_STAMPS: g_diag.fwd_stamps = (unsigned long long*)ptr; return 0;
         default: return fail(PSVI_EINVAL, "unknown debug key");
     }
 }

@@ -26,8 +26,6 @@
 
 namespace psvi {
 
-int g_lenet_abl = 0;        // psvi_debug_set(PSVI_DBG_LENET_ABLATION, mask): backward parts skipped
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -1604,7 +1602,7 @@ hipError_t launch_lenet(const psvi_plan& p, const float* u, const int32_t* z, co
     ca.r2 = W.r2;
     ca.dx2 = W.dx2;
     ca.part = W.part;
-    ca.abl = g_lenet_abl;
+    ca.abl = g_diag.lenet_abl;
     conv_fwd_mfma<false>(ca, S, M, st);
     const int w3 = p.lay[2].woff, w4 = p.lay[3].woff, w5 = p.lay[4].woff;
     const float* Ws = W.wsamp;

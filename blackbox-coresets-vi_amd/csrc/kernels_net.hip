@@ -1414,10 +1414,6 @@ __global__ __launch_bounds__(256) void net_slot_sum_kernel(const float* __restri
     out[i] = t;
 }
 
-int g_net_threads = 0;        // psvi_debug_set(PSVI_DBG_NET_THREADS, n): 0 = by chunk size
-int g_net_split_below = 256;  // split when a rank has fewer samples than CUs (psvi_debug_set(PSVI_DBG_NET_SPLIT_BELOW, n))
-int g_net_wg_target = 256;    // workgroups a split rank aims for (psvi_debug_set(PSVI_DBG_NET_WG_TARGET, n))
-
 size_t net_plan_geometry(psvi_plan& p) {
     // One workgroup per sample and all M pseudopoints when the samples alone
     // fill the chip.  Otherwise two role workgroups per sample (disjoint
@@ -1426,11 +1422,11 @@ size_t net_plan_geometry(psvi_plan& p) {
     // summed in chunk order).  LDS <= 160 KiB per workgroup.
     const int S_local = std::max(1, p.s_cnt[p.rank]);
     const int M = p.d.M;
-    const bool split = S_local < g_net_split_below;
+    const bool split = S_local < g_diag.net_split_below;
     p.net_roles = (split && p.L > 1) ? 2 : 1;
     int mchunks = 1;
     if (split)
-        while (S_local * p.net_roles * mchunks < g_net_wg_target && (M + mchunks) / (mchunks + 1) >= 16)
+        while (S_local * p.net_roles * mchunks < g_diag.net_wg_target && (M + mchunks) / (mchunks + 1) >= 16)
             ++mchunks;
     // chunks forced by the LDS alone (the samples already fill the chip) are
     // looped inside the workgroups of a full-cov plan (NetArgs::mloop)
@@ -1442,7 +1438,7 @@ size_t net_plan_geometry(psvi_plan& p) {
             p.mchunks = (M + mc - 1) / mc;
             p.mc = mc;
             p.net_lds = bytes;
-            p.net_threads = g_net_threads ? g_net_threads : (rup(mc, 16) >= 48 ? 512 : 256);
+            p.net_threads = g_diag.net_threads ? g_diag.net_threads : (rup(mc, 16) >= 48 ? 512 : 256);
             p.net_mloop = p.family == PSVI_FAMILY_FULLCOV && fill_one && p.mchunks > 1;
             return bytes;
         }
@@ -1490,15 +1486,6 @@ void net_xmap(const psvi_plan& p, std::vector<uint32_t>& xmap, std::vector<NetBa
                 bands.push_back(NetBand{src_base[q] + p.band_coloff[gb], p.rows_tot[q], 0});
             }
 }
-
-int g_net_ablation = 0;  // psvi_debug_set(PSVI_DBG_NET_ABLATION, mask)
-int g_net_mloop_off = 0;  // psvi_debug_set(PSVI_DBG_NET_MLOOP_OFF, 1): a workgroup per pseudopoint chunk + slots (A/B)
-int g_net_scalar_loads = 0;  // psvi_debug_set(PSVI_DBG_NET_SCALAR_LOADS, 1): the scalar load path (A/B)
-int g_net_geo_off = 0;  // psvi_debug_set(PSVI_DBG_NET_GEO_OFF, 1): the run-time geometry for fn2 too (A/B)
-unsigned long long* g_net_stamps = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_NET_STAMPS, buf)
-uint16_t* g_net_draw_planes = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_NET_DRAW_PLANES, buf)
-int g_net_draw_role1 = 17;  // psvi_debug_set(PSVI_DBG_NET_DRAW_ROLE1, n): role 1's 32nds of the fused draw
-int g_net_draw_spare_off = 0;  // psvi_debug_set(PSVI_DBG_NET_DRAW_SPARE_OFF, 1): the whole draw at the end (A/B)
 
 // Every net_kernel instantiation, once.  Mean-field plans take the Gaussian,
 // the Bernoulli or the categorical head; full-cov plans are keyed by (several
@@ -1570,7 +1557,7 @@ void net_set_lds_limit() {
 // full-cov stack with 100-row pseudopoint chunks (Mp = 112), float4 loads;
 // the run-time carve then equals the compile-time one (the same net_carve)
 static bool net_fn2_geo(const psvi_plan& p) {
-    if (g_net_geo_off || p.family != PSVI_FAMILY_FULLCOV || p.L != kFn2Dims.L) return false;
+    if (g_diag.net_geo_off || p.family != PSVI_FAMILY_FULLCOV || p.L != kFn2Dims.L) return false;
     for (int l = 0; l < p.L; ++l)
         if (p.lay[l].din != kFn2Dims.din[l] || p.lay[l].dout != kFn2Dims.dout[l]) return false;
     return net_rup(p.mc, 16) == kFn2Mp && p.net_threads == 512;
@@ -1580,7 +1567,7 @@ static bool net_fn2_geo(const psvi_plan& p) {
 // source block empty or at least one float4 wide (a block's last chunk is
 // loaded at its rows - 4)
 static bool net_vec_ok(const psvi_plan& p) {
-    if (p.lay[0].din % 4 || g_net_scalar_loads) return false;
+    if (p.lay[0].din % 4 || g_diag.net_scalar_loads) return false;
     for (int q = 0; q < p.world; ++q)
         if (p.rows_tot[q] > 0 && p.rows_tot[q] < 4) return false;
     return true;
@@ -1597,8 +1584,8 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
         return hipErrorInvalidValue;
     a.s_begin = s_begin;
     uint16_t* rn_planes = d.planes;
-    if (!rn_planes && g_net_draw_planes && d.out && p.family == PSVI_FAMILY_FULLCOV)
-        rn_planes = g_net_draw_planes;  // diagnostics: the planes of a draw that asked for none
+    if (!rn_planes && g_diag.net_draw_planes && d.out && p.family == PSVI_FAMILY_FULLCOV)
+        rn_planes = g_diag.net_draw_planes;  // diagnostics: the planes of a draw that asked for none
     if (outer) {
         a.outer = outer->mode;
         a.n_pseudo = outer->n_pseudo;
@@ -1641,8 +1628,8 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
     a.gslot = p.family == PSVI_FAMILY_FULLCOV && p.mchunks > 1 ? p.net_slots.dev : nullptr;
     a.gsz = (int64_t)p.s_cnt[p.rank] * p.n_tot;
     a.nroles = p.net_roles;
-    a.abl = g_net_ablation;
-    a.stamps = g_net_stamps;
+    a.abl = g_diag.net_ablation;
+    a.stamps = g_diag.net_stamps;
     for (int l = 0; l < p.L; ++l) {
         a.din[l] = p.lay[l].din;
         a.dout[l] = p.lay[l].dout;
@@ -1681,7 +1668,7 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
     }
     // the inner objective of a full-cov plan whose pseudopoints exceed the LDS
     // loops its chunks inside each workgroup (one x load, no slots, no slot sum)
-    const bool loop = p.net_mloop && a.outer == 0 && !g_net_mloop_off &&
+    const bool loop = p.net_mloop && a.outer == 0 && !g_diag.net_mloop_off &&
                       p.family == PSVI_FAMILY_FULLCOV && net_vec_ok(p);
     a.mloop = loop ? p.mchunks : 1;
     if (loop) a.gslot = nullptr;
@@ -1718,11 +1705,11 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
     }
     {
         // The draw's chunks of 64 quads over the workgroups: role 1 (the
-        // shorter role) takes g_net_draw_role1 / 32 of them, each role's share
+        // shorter role) takes g_diag.net_draw_role1 / 32 of them, each role's share
         // goes evenly (to one chunk) over its workgroups.
         const int64_t nch = (a.rn_q1 - a.rn_q0 + 63) / 64;
         const int64_t nper = (int64_t)grid.x * grid.z;
-        const int64_t c1 = grid.y == 2 ? nch / 32 * g_net_draw_role1 + nch % 32 * g_net_draw_role1 / 32 : 0;
+        const int64_t c1 = grid.y == 2 ? nch / 32 * g_diag.net_draw_role1 + nch % 32 * g_diag.net_draw_role1 / 32 : 0;
         const int64_t c0 = nch - c1;
         if (c0 / nper >= INT32_MAX || c1 / nper >= INT32_MAX) return hipErrorInvalidValue;
         a.rn_cbase1 = 0;
@@ -1731,7 +1718,7 @@ hipError_t launch_net(const psvi_plan& p, const NetLaunch& r, hipStream_t st) {
         a.rn_cbase0 = c1;
         a.rn_per0 = (int)(c0 / nper);
         a.rn_rem0 = (int)(c0 % nper);
-        a.rn_spare = g_net_draw_spare_off ? 0 : 1;
+        a.rn_spare = g_diag.net_draw_spare_off ? 0 : 1;
     }
     const NetVariant* nv = net_variant(p.family, p.lik, p.world > 1, net_vec_ok(p), loop, fn2);
     if (!nv) return hipErrorInvalidValue;

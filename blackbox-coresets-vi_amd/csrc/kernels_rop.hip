@@ -68,8 +68,6 @@ struct RopArgs {
     float* dzd;
 };
 
-unsigned long long* g_rop_stamps = nullptr;  // psvi_debug_set_ptr(PSVI_DBG_ROP_STAMPS, buf)
-
 // layers at most this wide (the loss head) run the 16-lane K-split forms:
 // the 2 x 2 register blocks leave all but a few threads idle there
 constexpr int kRopNarrow = 8;
@@ -1225,10 +1223,6 @@ static size_t rop_mfma_carve(const psvi_plan& p, int rows, RopArgs* a) {
 }
 
 constexpr size_t kRopLds = 160 * 1024;
-// psvi_debug_set(PSVI_DBG_ROP_VALU, 1): the VALU R-op kernel (the form for
-// row blocks past the LDS) on every shape (A/B)
-int g_rop_valu = 0;
-
 // rows per chunk that fit the LDS (0: the model's weights alone do not fit)
 int rop_rows(const psvi_plan& p) {
     for (int rc = 64; rc >= 1; rc >>= 1)
@@ -1274,14 +1268,14 @@ hipError_t launch_net_rop(const psvi_plan& p, const NetRop& r, hipStream_t st) {
     a.u = r.u; a.z = r.targets.slots(); a.w = r.w; a.x = r.x; a.xd = r.xd;
     a.params = r.params; a.vec = r.vec; a.eps = r.eps;
     a.G = r.G; a.Gd = r.Gd; a.du = r.du; a.nlld = r.nlld; a.dzd = r.dzd;
-    a.stamps = g_rop_stamps;
+    a.stamps = g_diag.rop_stamps;
     {
         // the matrix-core form when a row block fits the LDS in one pass
         // rows padded to a 16-multiple: the rows past a block's own are zero
         // (the contraction over rows runs to the 16-multiple)
         const int rows = (((p.d.M + a.nsplit - 1) / a.nsplit) + 15) & ~15;
         const size_t lds = rop_mfma_carve(p, rows, &a) * 4;
-        if (g_rop_valu != 1 && lds <= kRopLds) {
+        if (g_diag.rop_valu != 1 && lds <= kRopLds) {
             a.single = 1;
             const dim3 grid(p.d.S, a.nsplit), block(512);
             const bool fc = p.family == PSVI_FAMILY_FULLCOV;

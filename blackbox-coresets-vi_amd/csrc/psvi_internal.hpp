@@ -660,6 +660,7 @@ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 int build_plan(psvi_plan& p, std::string& err);
 // the network kernel's chunking and LDS size (kernels_net.hip: its LDS layout)
 size_t net_plan_geometry(psvi_plan& p);
+void net_set_lds_limit();  // kernels_net.hip
 // psvi_debug_set values read when a plan is built
 struct PlanDebug {
     int stream_wgs = 0;       // PSVI_DBG_STREAM_WGS: streaming-update workgroups (0 = 256)
@@ -669,6 +670,40 @@ struct PlanDebug {
     int ks_wgs = 0;           // PSVI_DBG_KSTREAM_WGS: K-split update workgroups (0 = 512)
 };
 extern PlanDebug g_plan_dbg;
+// psvi_debug_set / psvi_debug_set_ptr values read when a kernel is launched (and
+// by net_plan_geometry): A/B switches, ablation masks and stamp buffers, all 0 /
+// nullptr in production unless a default says otherwise (psvi_diag.h; capi.cpp)
+struct Diag {
+    using Stamps = unsigned long long*;  // 16 slots per workgroup
+    int net_ablation = 0;         // PSVI_DBG_NET_ABLATION, mask
+    int net_threads = 0;          // PSVI_DBG_NET_THREADS, n: 0 = by chunk size
+    int net_split_below = 256;    // PSVI_DBG_NET_SPLIT_BELOW, n: split when a rank has fewer samples than CUs
+    int net_wg_target = 256;      // PSVI_DBG_NET_WG_TARGET, n: workgroups a split rank aims for
+    int net_mloop_off = 0;        // PSVI_DBG_NET_MLOOP_OFF, 1: a workgroup per pseudopoint chunk + slots (A/B)
+    int net_scalar_loads = 0;     // PSVI_DBG_NET_SCALAR_LOADS, 1: the scalar load path (A/B)
+    int net_geo_off = 0;          // PSVI_DBG_NET_GEO_OFF, 1: the run-time geometry for fn2 too (A/B)
+    int net_draw_role1 = 17;      // PSVI_DBG_NET_DRAW_ROLE1, n: role 1's 32nds of the fused draw
+    int net_draw_spare_off = 0;   // PSVI_DBG_NET_DRAW_SPARE_OFF, 1: the whole draw at the end (A/B)
+    Stamps net_stamps = nullptr;  // PSVI_DBG_NET_STAMPS
+    uint16_t* net_draw_planes = nullptr;  // PSVI_DBG_NET_DRAW_PLANES
+    int fwd_ablation = 0;         // PSVI_DBG_FWD_ABLATION, mask
+    Stamps fwd_stamps = nullptr;  // PSVI_DBG_FWD_STAMPS
+    int fs_off = 0;               // PSVI_DBG_FWD_SEG_OFF, 1: the item-grid sample kernel at S > 128 (A/B)
+    int fs_bf_off = 0;            // PSVI_DBG_FWD_SEG_BF_OFF, 1: the fp32 segmented sample (A/B)
+    int fwd_pair_bf = 1;          // PSVI_DBG_FWD_PAIR_BF, 0: the HVP's sample pair on the fp32 item grid (A/B)
+    int upd_ablation = 0;         // PSVI_DBG_UPD_ABLATION, mask
+    Stamps upd_stamps = nullptr;  // PSVI_DBG_UPD_STAMPS
+    int stream_off = 0;           // PSVI_DBG_UPD_STREAM_OFF, 1: the chunked kernel (A/B)
+    int stream_bf_off = 0;        // PSVI_DBG_STREAM_BF_OFF, 1: the fp32-MFMA streaming kernel (A/B)
+    int stream_fold_off = 0;      // PSVI_DBG_STREAM_FOLD_OFF, 1: the band combine as mvn_fwd_reduce_kernel (A/B)
+    Stamps bf_stamps = nullptr;   // PSVI_DBG_BF_STAMPS
+    int ks_off = 0;               // PSVI_DBG_KSTREAM_OFF, 1: the chunked kernel at S > 128 (A/B)
+    int ks_bf_off = 0;            // PSVI_DBG_KSTREAM_BF_OFF, 1: the fp32 K-split update (A/B)
+    int rop_valu = 0;             // PSVI_DBG_ROP_VALU, 1: the VALU R-op kernel (the form for row blocks past the LDS) on every shape (A/B)
+    Stamps rop_stamps = nullptr;  // PSVI_DBG_ROP_STAMPS
+    int lenet_abl = 0;            // PSVI_DBG_LENET_ABLATION, mask: backward parts skipped
+};
+extern Diag g_diag;
 // the full-cov network kernel's x map and band table (kernels_net.hip)
 void net_xmap(const psvi_plan& p, std::vector<uint32_t>& xmap, std::vector<NetBand>& bands);
 // Per-row targets of the loss head: class labels (categorical plans) or fp32

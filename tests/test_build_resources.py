@@ -39,7 +39,8 @@ def _resources(src, tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-@pytest.mark.parametrize("src", ["kernels_net.hip", "kernels_mvn.hip", "kernels_mf.hip",
+@pytest.mark.parametrize("src", ["kernels_net.hip", "kernels_mvn_fwd.hip", "kernels_mvn_update.hip",
+                                 "kernels_mvn_kstream.hip", "kernels_mvn_stream.hip", "kernels_mf.hip",
                                  "kernels_outer.hip", "kernels_rop.hip", "kernels_lenet.hip"])
 def test_no_scratch_no_spills(src, tmp_path):
     """No scratch memory traffic anywhere.  A VGPR spill is tolerated only into the

@@ -37,7 +37,7 @@ def _case(layers, S, seed):
     return rng, p, m, v
 
 
-# the stream kernel runs at S = 128 (stream_ok in kernels_mvn.hip)
+# the stream kernel runs at S = 128 (stream_ok in kernels_mvn_stream.hip)
 SHAPES = [([(64, 40), (40, 40), (40, 2)], 128),   # C3
           ([(7, 5), (5, 3)], 128),                 # n = 40, 18: one partial band each
           ([(30, 33), (33, 2)], 128),              # n = 1023, 68

@@ -3,7 +3,7 @@
 block (label) counts of MFMA, other VALU, SALU, LDS, global/buffer memory and
 waitcnt instructions; blocks ending in a backward branch are marked LOOP.
 
-  python tools/isa_blocks.py build/asm/kernels_mvn-hip-amdgcn-amd-amdhsa-gfx950.s <kernel substring> [min_insts]
+  python tools/isa_blocks.py build/asm/kernels_mvn_stream-hip-amdgcn-amd-amdhsa-gfx950.s <kernel substring> [min_insts]
 """
 import re
 import sys

@@ -1,6 +1,6 @@
 // Probe: fp32-faithful GEMM tiles on the bf16 matrix cores (three bf16 pieces
 // per operand, six products) against v_mfma_f32_32x32x2_f32, for the two
-// products of the streaming update's tile (kernels_mvn.hip mvn_stream_kernel):
+// products of the streaming update's tile (kernels_mvn_stream.hip mvn_stream_kernel):
 //   dLT[c][r] = sum_s E[s][c] G[s][r]          (K = S = 128)
 //   Y[s][r]   = sum_c E2[s][c] L[r][c]         (K = 64 columns; L = dLT, the
 //                                                accumulator as the B operand)
