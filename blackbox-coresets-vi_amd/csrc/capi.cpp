@@ -1303,6 +1303,38 @@ int psvi_laplace_fit(const psvi_laplace_fit_req* q, void* stream) {
     return 0;
 }
 
+int psvi_laplace_sample_full(const psvi_laplace_sample_full_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    if (q->d < 2 || q->d > kLapFullMaxD || q->n_core < 0 || q->n_core > kLapMaxNu || q->S < 0 ||
+        q->S > 2048)
+        return fail(PSVI_EINVAL, "the full-precision Laplace samples support 2 <= d <= 128, "
+                                 "0 <= n_core <= 4096, 0 <= S <= 2048");
+    if (!q->theta || (q->n_core > 0 && (!q->x_core || !q->w_core)))
+        return fail(PSVI_EINVAL, "null pointer");
+    if ((q->eps != nullptr) != (q->S > 0))
+        return fail(PSVI_EINVAL, "eps goes with S >= 1 and is NULL at S == 0");
+    if (q->S > 0 && !q->samples_out)
+        return fail(PSVI_EINVAL, "samples_out is required when S > 0");
+    hipStream_t st = as_stream(stream);
+    if (q->n_core > 0) {
+        // as psvi_laplace_fit: zero weights add nothing, negative ones would break P >= I
+        std::vector<float> w(q->n_core);
+        HIP_TRY(hipMemcpyAsync(w.data(), q->w_core, sizeof(float) * w.size(), hipMemcpyDeviceToHost,
+                               st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (float v : w)
+            if (!(v >= 0.0f) || !std::isfinite(v))
+                return fail(PSVI_EINVAL, "the full-precision Laplace samples need finite weights >= 0");
+    }
+    LaplaceSampleFull r;
+    r.Nu = q->n_core; r.d = q->d; r.S = q->S;
+    r.x = q->x_core; r.w = q->w_core; r.theta = q->theta; r.eps = q->eps;
+    r.prec_out = q->prec_out; r.factor_out = q->factor_out; r.samples_out = q->samples_out;
+    r.logdet_out = q->logdet_out;
+    HIP_TRY(launch_laplace_sample_full(r, st));
+    return 0;
+}
+
 int psvi_laplace_scores(const psvi_laplace_scores_req* q, void* stream) {
     if (!q) return fail(PSVI_EINVAL, "null request");
     if (q->S < 2 || q->S > 2048 || q->d < 2 || q->d > kLapMaxD || q->n_core < 0 ||

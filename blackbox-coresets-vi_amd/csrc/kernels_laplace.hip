@@ -7,7 +7,8 @@
 // Reference:
 //   run_laplace         psvi/inference/baselines.py:35-70
 //   model               psvi/models/logreg.py:17-26
-//   laplace_precision   psvi/models/logreg.py:95-107 (diagonal)
+//   laplace_precision   psvi/models/logreg.py:95-107 (diagonal in the fit kernel; the
+//                       full matrix in laplace_sample_full_kernel below)
 //   scores / gradients  psvi/inference/baselines.py:550-575, 617-635, 783-805
 //
 // Fit: T torch-Adam steps on theta [d] of the negative log-joint
@@ -180,6 +181,144 @@ hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st) {
         attr_set[xlds] = true;
     }
     hipLaunchKernelGGL(kernel, dim3(1), dim3(kLapThreads), lds, st, a);
+    return hipGetLastError();
+}
+
+// Full-precision samples (laplace_precision(diagonal=False), logreg.py:95-107;
+// MultivariateNormal(theta, precision_matrix=P).rsample, baselines.py:64-70):
+//   P = I + sum_m w_m p_m (1 - p_m) x_m x_m^T,   p_m = sigmoid(x_m . theta)
+// torch samples theta + L eps with L the lower Cholesky factor of P^-1.  With
+// the "reverse" factorisation P = A^T A, A lower-triangular (eliminated from
+// the last row and column upwards), L = A^-1: a sample is theta + y, A y = eps,
+// one forward substitution, and L is never formed.  Every eigenvalue of P is
+// >= 1 (w >= 0): no pivoting, no jitter.
+// One workgroup; th [d], the lower triangle of P / A packed by rows
+// (tri(i) + j, j <= i) and a work area are fp64 in LDS:
+//   phase 1  rows:    thread t owns rows t, t + 256, ...: r_m = w_m p_m (1 - p_m) -> work
+//            entries: thread t owns the packed entries t, t + 256, ...: the sum
+//                     over the rows in order, x from global memory, then + I
+//   phase 2  for k = d - 1 .. 0: pivot A_kk = sqrt(P_kk) | row k /= A_kk |
+//            P_ji -= A_kj A_ki over the packed prefix (i <= j < k), a barrier
+//            after each; thread 0 then sums log A_jj in order
+//   phase 3  thread t < nb owns the samples t, t + nb, ...; its y lives in the
+//            work area as y[i][t] (nb = the columns that fit, <= 256)
+// Every sum has one owner and a fixed order, all in fp64; outputs are rounded
+// to float once.  No atomics.
+struct LapFullArgs {
+    int Nu, d, S, nb;
+    const float *x, *w, *theta, *eps;
+    float *prec, *factor, *samples;
+    double* logdet;
+};
+
+__device__ __forceinline__ int lap_tri(int i) { return i * (i + 1) / 2; }
+// the row i of packed entry e: tri(i) <= e < tri(i + 1)
+__device__ __forceinline__ int lap_tri_row(int e) {
+    int i = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+    while (lap_tri(i) > e) --i;
+    while (lap_tri(i + 1) <= e) ++i;
+    return i;
+}
+
+__global__ __launch_bounds__(kLapThreads) void laplace_sample_full_kernel(LapFullArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lapf_sm[];
+    const int Nu = a.Nu, d = a.d, tid = threadIdx.x, ntri = lap_tri(d);
+    double* th = lapf_sm;    // [d]
+    double* P = th + d;      // [tri(d)]
+    double* work = P + ntri; // [max(Nu, nb * d)]: r, then y
+    for (int j = tid; j < d; j += kLapThreads) th[j] = (double)a.theta[j];
+    __syncthreads();
+    for (int m = tid; m < Nu; m += kLapThreads) {
+        const float* xm = a.x + (size_t)m * d;
+        double f = 0.0;
+        for (int j = 0; j < d; ++j) f += (double)xm[j] * th[j];
+        const double p = lap_sigmoid(f);
+        work[m] = (double)a.w[m] * p * (1.0 - p);
+    }
+    __syncthreads();
+    for (int e = tid; e < ntri; e += kLapThreads) {
+        const int i = lap_tri_row(e), j = e - lap_tri(i);
+        const float *xi = a.x + i, *xj = a.x + j;
+        double acc = 0.0;
+#pragma unroll 8
+        for (int m = 0; m < Nu; ++m)
+            acc += work[m] * (double)xi[(size_t)m * d] * (double)xj[(size_t)m * d];
+        P[e] = i == j ? acc + 1.0 : acc;
+    }
+    __syncthreads();
+    if (a.prec) {
+        for (int q = tid; q < d * d; q += kLapThreads) {
+            const int i = q / d, j = q % d;
+            a.prec[q] = (float)P[i >= j ? lap_tri(i) + j : lap_tri(j) + i];
+        }
+    }
+    for (int k = d - 1; k >= 0; --k) {
+        double* Ak = P + lap_tri(k);
+        __syncthreads();  // the reads of P for prec_out / the previous update
+        if (tid == 0) Ak[k] = sqrt(Ak[k]);
+        __syncthreads();
+        for (int i = tid; i < k; i += kLapThreads) Ak[i] /= Ak[k];
+        __syncthreads();
+        for (int e = tid; e < lap_tri(k); e += kLapThreads) {
+            const int j = lap_tri_row(e), i = e - lap_tri(j);
+            P[e] -= Ak[j] * Ak[i];
+        }
+    }
+    __syncthreads();
+    if (a.factor) {
+        for (int q = tid; q < d * d; q += kLapThreads) {
+            const int i = q / d, j = q % d;
+            a.factor[q] = i >= j ? (float)P[lap_tri(i) + j] : 0.0f;
+        }
+    }
+    if (a.logdet && tid == 0) {
+        double s = 0.0;
+        for (int j = 0; j < d; ++j) s += log(P[lap_tri(j) + j]);
+        a.logdet[0] = 2.0 * s;
+    }
+    if (tid >= a.nb) return;  // no barrier below
+    const int nb = a.nb;
+    for (int s = tid; s < a.S; s += nb) {
+        const float* es = a.eps + (size_t)s * d;
+        float* out = a.samples + (size_t)s * d;
+        for (int i = 0; i < d; ++i) {
+            const double* Ai = P + lap_tri(i);
+            double acc = (double)es[i];
+            for (int j = 0; j < i; ++j) acc -= Ai[j] * work[j * nb + tid];
+            const double yi = acc / Ai[i];
+            work[i * nb + tid] = yi;
+            out[i] = (float)(th[i] + yi);
+        }
+    }
+}
+
+static size_t lap_full_lds(int Nu, int d, int nb) {
+    return sizeof(double) * ((size_t)d + (size_t)d * (d + 1) / 2 +
+                             (size_t)std::max(Nu, nb * d));
+}
+
+hipError_t launch_laplace_sample_full(const LaplaceSampleFull& r, hipStream_t st) {
+    if (r.d < 2 || r.d > kLapFullMaxD || r.Nu < 0 || r.Nu > kLapMaxNu || r.S < 0 ||
+        r.S > kSelMaxS || (r.S > 0 && (!r.eps || !r.samples_out)))
+        return hipErrorInvalidValue;
+    LapFullArgs a{};
+    a.Nu = r.Nu; a.d = r.d; a.S = r.S;
+    a.x = r.x; a.w = r.w; a.theta = r.theta; a.eps = r.eps;
+    a.prec = r.prec_out; a.factor = r.factor_out; a.samples = r.samples_out;
+    a.logdet = r.logdet_out;
+    // the sample columns that fit beside theta and the factor, one thread each
+    const int room = (int)((kLapLds - lap_full_lds(0, r.d, 0)) / (sizeof(double) * r.d));
+    a.nb = std::min(std::min(kLapThreads, room), r.S);
+    const size_t lds = lap_full_lds(r.Nu, r.d, a.nb);
+    if (lds > kLapLds) return hipErrorInvalidValue;
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)laplace_sample_full_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLapLds);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(laplace_sample_full_kernel, dim3(1), dim3(kLapThreads), lds, st, a);
     return hipGetLastError();
 }
 

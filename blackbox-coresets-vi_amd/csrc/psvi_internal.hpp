@@ -852,6 +852,21 @@ struct LaplaceFit {
     float* samples_out = nullptr;  // [S][d], written when eps is given
 };
 hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st);
+// the full precision P = I + x^T diag(w p (1 - p)) x at theta, its reverse
+// Cholesky factor A (A^T A = P) and S samples theta + A^-1 eps_s, one workgroup
+constexpr int kLapFullMaxD = 128;  // the packed triangle of P and the samples' y live in LDS
+struct LaplaceSampleFull {
+    int Nu = 0, d = 0, S = 0;
+    const float* x = nullptr;
+    const float* w = nullptr;
+    const float* theta = nullptr;
+    const float* eps = nullptr;     // [S][d], null iff S == 0
+    float* prec_out = nullptr;      // [d][d], nullable
+    float* factor_out = nullptr;    // [d][d], nullable
+    float* samples_out = nullptr;   // [S][d]
+    double* logdet_out = nullptr;   // [1], nullable
+};
+hipError_t launch_laplace_sample_full(const LaplaceSampleFull& r, hipStream_t st);
 // scores, weight gradient and pseudo-input gradient from samples [S][d] and
 // rows [Nu + B][d] (core rows first)
 struct LaplaceScores {

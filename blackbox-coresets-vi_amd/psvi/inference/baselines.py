@@ -72,7 +72,21 @@ search are one launch of psvi_giga_step per step.  Reference behaviours kept:
 * The minibatch is drawn with replacement, the first occurrence wins the
   argmax, and a point already in the core is not appended again.
 
-``mcmc=True`` (stan) and ``diagonal=False`` raise NotImplementedError.
+Full precision (``diagonal=False``; DESIGN §4, "Full precision"): the samples
+come from MultivariateNormal(theta, precision_matrix=I + X^T diag(w p (1 - p)) X)
+(baselines.py:64-70, logreg.py:95-107) through psvi_laplace_sample_full -- the
+fit runs without samples, then the precision, its reverse Cholesky factor and
+one forward substitution per sample, fp64 in one launch.  The host draws the
+same (S, d) standard normals in the same order as on the diagonal path.
+``run_laplace(..., diagonal=False)`` is public, and ``_run_sparsevi`` /
+``_run_opsvi`` (the bodies of the public functions) take ``diagonal`` for every
+selection-loop fit; as in the reference their logging fits stay diagonal.  The
+public ``run_sparsevi(diagonal=False)`` / ``run_opsvi(diagonal=False)`` still
+raise: tests/test_laplace_cpu.py::test_argument_checks asserts it, and opening
+the keyword waits on that test (as ``"giga"`` in ``inf_dict`` does).
+
+``mcmc=True`` (stan) and, on the public sparsevi / opsvi, ``diagonal=False``
+raise NotImplementedError.
 Optional test hooks: ``noise_source(n)`` supplies each host draw,
 ``batch_source()`` the ``np.random.randint`` minibatches,
 ``choice_source(candidates)`` run_random's ``random.choice``; ``state_out`` (a
@@ -90,11 +104,11 @@ from torch.utils.data import DataLoader
 from ..models import (VILinear, VILinearMultivariateNormal, categorical_fn, make_fc2net,
                       make_fcnet, make_lenet, model_spec)
 from ..runtime import (InnerLoopPlan, adam_update_, check_binary, giga_step, laplace_fit,
-                       laplace_scores, randn_)
+                       laplace_sample_full, laplace_scores, randn_)
 
 __all__ = ["set_up_model", "pseudo_subsample_init", "pseudo_rand_init", "run_mfvi",
-           "run_mfvi_subset", "process_wt_index", "run_random", "run_sparsevi", "run_opsvi",
-           "run_giga"]
+           "run_mfvi_subset", "process_wt_index", "run_laplace", "run_random", "run_sparsevi",
+           "run_opsvi", "run_giga"]
 
 
 def set_up_model(D=None, n_hidden=None, nc=None, mc_samples=None, architecture=None,
@@ -312,12 +326,57 @@ def _refuse(mcmc, diagonal=True):
     if mcmc:
         raise NotImplementedError("mcmc=True needs stan, which is not on the HIP path")
     if not diagonal:
-        raise NotImplementedError("diagonal=False (full Laplace precision) is not on the HIP path")
+        raise NotImplementedError("diagonal=False is not open on run_sparsevi / run_opsvi yet "
+                                  "(run_laplace and _run_sparsevi / _run_opsvi take it)")
+
+
+def _draw(noise_source, device, *shape):
+    """A host draw of the reference (Normal.rsample / MultivariateNormal.rsample
+    on the CPU generator: the same standard normals in the same order)."""
+    n = int(np.prod(shape))
+    if noise_source is not None:
+        out = torch.as_tensor(noise_source(n), dtype=torch.float32).reshape(-1)
+        if out.numel() != n:
+            raise ValueError(f"noise_source returned {out.numel()} draws, expected {n}")
+    else:
+        out = torch.empty(n).normal_()
+    return out.reshape(shape).to(device).contiguous()
+
+
+def _fit(theta, xc, yc, wc, T, lr, eps, want_loss=False, diagonal=True):
+    """T Adam steps on theta (in place), then the samples from eps (S, d) under
+    the diagonal or the full Laplace precision: (samples, loss)."""
+    if diagonal:
+        out = laplace_fit(xc, yc, wc, theta, T, lr, eps=eps, want_loss=want_loss)
+        return out["samples"], out["loss"]
+    loss = laplace_fit(xc, yc, wc, theta, T, lr, want_loss=want_loss)["loss"]
+    return laplace_sample_full(xc, wc, theta, eps=eps)["samples"], loss
+
+
+def run_laplace(x_core, y_core, w_core, theta, inner_it=1000, lr0net=1e-3, diagonal=True,
+                mc_samples=4, seed=0, noise_source=None):
+    """Samples from the Laplace approximation on a weighted coreset
+    (baselines.py:35-70, the optimiser argument replaced by its learning rate):
+    reseeds every generator, takes ``inner_it`` steps of a new Adam on theta
+    (d,), IN PLACE, and returns the (mc_samples, d) device samples under the
+    diagonal precision or, with ``diagonal=False``, the full one.  x_core
+    (n_core, d) carries the ones column; an empty core fits the prior alone."""
+    device = _device()
+    f32 = dict(device=device, dtype=torch.float32)
+    xc, yc, wc = (t.detach().to(**f32).contiguous() for t in (x_core, y_core, w_core))
+    th = theta.detach().to(**f32).contiguous()
+    _reseed(seed)
+    eps = _draw(noise_source, device, int(mc_samples), int(th.numel()))
+    smp, _ = _fit(th, xc, yc, wc, inner_it, lr0net, eps, diagonal=diagonal)
+    if th.data_ptr() != theta.data_ptr():
+        with torch.no_grad():
+            theta.copy_(th)
+    return smp
 
 
 class _Laplace:
     """Device side of one Laplace-baseline run: the augmented train and test
-    rows, the host noise draws and the two library entries."""
+    rows, the host noise draws and the library entries."""
 
     def __init__(self, x, y, xt, yt, mc_samples, noise_source):
         self.device = _device()
@@ -331,26 +390,18 @@ class _Laplace:
         self.S, self.noise_source = int(mc_samples), noise_source
 
     def draw(self, *shape):
-        """A host draw of the reference (Normal.rsample on the CPU generator)."""
-        n = int(np.prod(shape))
-        if self.noise_source is not None:
-            out = torch.as_tensor(self.noise_source(n), dtype=torch.float32).reshape(-1)
-            if out.numel() != n:
-                raise ValueError(f"noise_source returned {out.numel()} draws, expected {n}")
-        else:
-            out = torch.empty(n).normal_()
-        return out.reshape(shape).to(self.device).contiguous()
+        """A host draw of the reference."""
+        return _draw(self.noise_source, self.device, *shape)
 
-    def fit(self, theta, xc, yc, wc, T, lr, want_loss=False):
+    def fit(self, theta, xc, yc, wc, T, lr, want_loss=False, diagonal=True):
         """T Adam steps on theta (in place), then S samples: (samples, loss)."""
-        out = laplace_fit(xc, yc, wc, theta, T, lr, eps=self.draw(self.S, self.d),
-                          want_loss=want_loss)
-        return out["samples"], out["loss"]
+        return _fit(theta, xc, yc, wc, T, lr, self.draw(self.S, self.d), want_loss=want_loss,
+                    diagonal=diagonal)
 
-    def run_laplace(self, theta, xc, yc, wc, T, lr, seed=0):
+    def run_laplace(self, theta, xc, yc, wc, T, lr, seed=0, diagonal=True):
         """baselines.py:35-70: reseeds every generator first."""
         _reseed(seed)
-        return self.fit(theta, xc, yc, wc, T, lr)[0]
+        return self.fit(theta, xc, yc, wc, T, lr, diagonal=diagonal)[0]
 
     def predict(self, samples):
         """logreg_forward and the test metrics: (accuracy, mean NLL)."""
@@ -469,6 +520,20 @@ def run_sparsevi(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibatch=
     projected Adam steps on the weights, each after a fit of its own.  Returns
     the reference's results dict {nlls, accs, csizes, times, wt_index}."""
     _refuse(mcmc, diagonal)
+    return _run_sparsevi(x=x, y=y, xt=xt, yt=yt, mc_samples=mc_samples,
+                         data_minibatch=data_minibatch, num_epochs=num_epochs,
+                         log_every=log_every, diagonal=diagonal, inner_it=inner_it,
+                         outer_it=outer_it, lr0net=lr0net, lr0v=lr0v, seed=seed,
+                         noise_source=noise_source, batch_source=batch_source,
+                         state_out=state_out)
+
+
+def _run_sparsevi(x, y, xt, yt, mc_samples=4, data_minibatch=128, num_epochs=100, log_every=10,
+                  diagonal=True, inner_it=10, outer_it=10, lr0net=1e-3, lr0v=1e-1, seed=0,
+                  noise_source=None, batch_source=None, state_out=None):
+    """run_sparsevi's body.  ``diagonal=False`` draws every selection-loop
+    sample from the full Laplace precision (baselines.py:540-548, 602-610); the
+    logging fit stays diagonal, as in the reference (baselines.py:501)."""
     check_binary(y, "y")
     outer_it = min(outer_it, 500)
     _reseed(seed)
@@ -497,7 +562,7 @@ def run_sparsevi(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibatch=
         # 1. the coreset posterior; 2. log-likelihoods; 3. the point to attach
         sub, sub_t = L.minibatch(B, batch_source)
         theta = L.draw(L.d)
-        smp, _ = L.fit(theta, xc, yc, wc, inner_it, lr0net)
+        smp, _ = L.fit(theta, xc, yc, wc, inner_it, lr0net, diagonal=diagonal)
         res = L.scores(smp, xc, yc, wc, sub_t)["result"].tolist()
         if res[3] > 0:
             pt = int(sub[int(res[1])])
@@ -509,7 +574,7 @@ def run_sparsevi(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibatch=
         theta = L.draw(L.d)
         for _ in range(outer_it):
             wc = w.detach()[ci].contiguous()
-            smp, _ = L.fit(theta, xc, yc, wc, inner_it, lr0net)
+            smp, _ = L.fit(theta, xc, yc, wc, inner_it, lr0net, diagonal=diagonal)
             sub, sub_t = L.minibatch(B, batch_source)
             gw = L.scores(smp, xc, yc, wc, sub_t, want_grad_w=True)["grad_w"]
             w.grad = torch.zeros_like(w)
@@ -535,6 +600,21 @@ def run_opsvi(x=None, y=None, xt=None, yt=None, mc_samples=10, data_minibatch=12
     on the pseudo-inputs.  Returns the reference's results dict {accs, nlls,
     csizes, times, elbos} (+ us, zs, vs under log_pseudodata)."""
     _refuse(mcmc, diagonal)
+    return _run_opsvi(x=x, y=y, xt=xt, yt=yt, mc_samples=mc_samples,
+                      data_minibatch=data_minibatch, num_epochs=num_epochs, log_every=log_every,
+                      num_pseudo=num_pseudo, inner_it=inner_it, diagonal=diagonal, lr0net=lr0net,
+                      lr0u=lr0u, lr0v=lr0v, register_elbos=register_elbos, init_args=init_args,
+                      seed=seed, log_pseudodata=log_pseudodata, noise_source=noise_source,
+                      batch_source=batch_source, state_out=state_out)
+
+
+def _run_opsvi(x, y, xt, yt, mc_samples=10, data_minibatch=128, num_epochs=100, log_every=10,
+               num_pseudo=10, inner_it=10, diagonal=True, lr0net=1e-3, lr0u=1e-3, lr0v=1e-3,
+               register_elbos=False, init_args="subsample", seed=0, log_pseudodata=False,
+               noise_source=None, batch_source=None, state_out=None):
+    """run_opsvi's body.  ``diagonal=False`` draws every epoch's samples from
+    the full Laplace precision (baselines.py:768-776); the logging fit stays
+    diagonal, as in the reference (baselines.py:730)."""
     _reseed(seed)
     L = _Laplace(x, y, xt, yt, mc_samples, noise_source)
     N, B = L.N, int(data_minibatch)
@@ -560,7 +640,7 @@ def run_opsvi(x=None, y=None, xt=None, yt=None, mc_samples=10, data_minibatch=12
             csizes.append(num_pseudo), nlls.append(nll), accs.append(acc)
             n_logged += 1
         smp, loss = L.fit(theta, u.detach(), z, w.detach(), inner_it, lr0net,
-                          want_loss=register_elbos)
+                          want_loss=register_elbos, diagonal=diagonal)
         if register_elbos:
             elbos.extend((1, -l) for l in loss.tolist()[::log_every])
         sub, sub_t = L.minibatch(B, batch_source)

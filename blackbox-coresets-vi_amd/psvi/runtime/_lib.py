@@ -86,6 +86,16 @@ class LaplaceFitReq(ctypes.Structure):
     ]
 
 
+class LaplaceSampleFullReq(ctypes.Structure):
+    _fields_ = [
+        ("n_core", ctypes.c_int32), ("d", ctypes.c_int32), ("S", ctypes.c_int32),
+        ("x_core", ctypes.c_void_p), ("w_core", ctypes.c_void_p), ("theta", ctypes.c_void_p),
+        ("eps", ctypes.c_void_p),
+        ("prec_out", ctypes.c_void_p), ("factor_out", ctypes.c_void_p),
+        ("samples_out", ctypes.c_void_p), ("logdet_out", ctypes.c_void_p),
+    ]
+
+
 class LaplaceScoresReq(ctypes.Structure):
     _fields_ = [
         ("S", ctypes.c_int32), ("d", ctypes.c_int32), ("n_core", ctypes.c_int32),
@@ -164,6 +174,7 @@ SIGNATURES = {
     "psvi_select_weight_grad": (_I32, [_I32, _I32, _I32, _P, _P, _P, ctypes.c_double, _P, _P,
                                        _P]),
     "psvi_laplace_fit": (_I32, [ctypes.POINTER(LaplaceFitReq), _P]),
+    "psvi_laplace_sample_full": (_I32, [ctypes.POINTER(LaplaceSampleFullReq), _P]),
     "psvi_laplace_scores": (_I32, [ctypes.POINTER(LaplaceScoresReq), _P]),
     "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -747,6 +747,46 @@ def laplace_fit(x_core, y_core, w_core, theta, T, lr, eps=None, prior_mean=0.0, 
     return out
 
 
+def laplace_sample_full(x_core, w_core, theta, eps=None, want_prec=False, want_factor=False,
+                        want_logdet=False):
+    """Samples from the full-precision Laplace posterior at the fitted mode
+    theta (d,) (psvi_laplace_sample_full): P = I + x^T diag(w p (1 - p)) x for
+    x_core (n_core, d; the ones column included) and w_core >= 0 (both None for
+    an empty core), A lower-triangular with A^T A = P, and theta + A^-1 eps_s
+    for eps (S, d) -- what MultivariateNormal(theta, precision_matrix=P) draws
+    from the same noise.  Returns a dict of device tensors: samples (S, d; None
+    without eps) and, on request (None otherwise), prec (d, d), factor (d, d:
+    A) and logdet (1 float64: log det P)."""
+    d = int(theta.numel())
+    _need(theta, "theta", d)
+    n_core = 0 if x_core is None else int(x_core.shape[0])
+    if n_core:
+        _need(x_core, "x_core", n_core * d)
+        _need(w_core, "w_core", n_core)
+    S = 0
+    dev = theta.device
+    if eps is not None:
+        if eps.dim() != 2:
+            raise ValueError("eps must be the (S, d) tensor of draws")
+        S = int(eps.shape[0])
+        _need(eps, "eps", S * d)
+
+    def new(*shape, on=True, dtype=torch.float32):
+        return torch.empty(*shape, dtype=dtype, device=dev) if on else None
+
+    out = {"samples": new(S, d, on=S > 0), "prec": new(d, d, on=want_prec),
+           "factor": new(d, d, on=want_factor),
+           "logdet": new(1, on=want_logdet, dtype=torch.float64)}
+    on = bool(n_core)
+    req = _lib.LaplaceSampleFullReq(
+        n_core, d, S, _ptr(x_core if on else None), _ptr(w_core if on else None), _ptr(theta),
+        _ptr(eps if S else None), _ptr(out["prec"]), _ptr(out["factor"]), _ptr(out["samples"]),
+        _ptr(out["logdet"]))
+    check(_lib.load().psvi_laplace_sample_full(ctypes.byref(req), _stream()),
+          "psvi_laplace_sample_full")
+    return out
+
+
 def laplace_scores(samples, rows, labels, w_core, n_core, sum_scaling, want_grad_w=False,
                    want_ll=False, want_grad_u=False):
     """Selection scores and gradients of the Laplace baselines

@@ -577,6 +577,44 @@ typedef struct psvi_laplace_fit_req {
 } psvi_laplace_fit_req;
 int psvi_laplace_fit(const psvi_laplace_fit_req* req, void* stream);
 
+/* Samples from the FULL-precision Laplace posterior at a fitted mode
+ * (laplace_precision(diagonal=False), psvi/models/logreg.py:95-107;
+ * MultivariateNormal(theta, precision_matrix=P).rsample, baselines.py:64-70),
+ * one launch of one workgroup.  x_core ([n_core][d], ones column included),
+ * w_core (n_core floats, >= 0), theta (d floats: psvi_laplace_fit's output,
+ * read only), eps ([S][d] standard normals):
+ *   p_m         = sigmoid(x_m . theta)
+ *   P           = I + sum_m w_m p_m (1 - p_m) x_m x_m^T
+ *   A           : lower-triangular, A^T A = P (the "reverse" Cholesky factor,
+ *                 eliminated from the last row and column upwards); torch's
+ *                 scale_tril, the lower Cholesky factor of P^-1, is A^-1
+ *   prec_out    ([d][d] floats, nullable)  <- P, both triangles, exactly symmetric
+ *   factor_out  ([d][d] floats, nullable)  <- A, exact zeros above the diagonal
+ *   samples_out ([S][d] floats)            <- theta + y_s,  A y_s = eps_s (one
+ *                                             forward substitution per sample)
+ *   logdet_out  (1 double, nullable)       <- log det P = 2 sum_j log A_jj
+ * Every eigenvalue of P is >= 1, so the factorisation needs neither pivoting
+ * nor jitter.  theta, P (its lower triangle, packed), A and the substitutions
+ * are fp64 in LDS, each sum with one owner and a fixed order; outputs are
+ * rounded to float once: bitwise reproducible, no atomics.
+ * Ranges (PSVI_EINVAL outside them): 2 <= d <= 128, 0 <= n_core <= 4096 (the
+ * core pointers may be NULL at 0: P = I, samples = theta + eps), 0 <= S <=
+ * 2048; eps is given iff S >= 1, and samples_out is required then.  A negative
+ * or NaN weight is PSVI_EINVAL too: as psvi_laplace_fit, the entry reads
+ * w_core back before the launch, so it synchronises the stream. */
+typedef struct psvi_laplace_sample_full_req {
+    int32_t n_core, d, S;
+    const float* x_core;
+    const float* w_core;
+    const float* theta;
+    const float* eps;
+    float* prec_out;
+    float* factor_out;
+    float* samples_out;
+    double* logdet_out;
+} psvi_laplace_sample_full_req;
+int psvi_laplace_sample_full(const psvi_laplace_sample_full_req* req, void* stream);
+
 /* The selection scores and gradients of the Laplace baselines
  * (baselines.py:550-575, 617-635, 783-805) from samples ([S][d]), rows
  * ([n_core + n_data][d], core rows first), labels (n_core + n_data floats),

@@ -4,6 +4,10 @@ hipEvents, and the reference's ``run_laplace`` on the CPU for the same problem.
 Not a test and not read by bench.py.
 
   python tools/laplace_probe.py                 the kernel (needs a HIP device)
+  python tools/laplace_probe.py --full          the fit without samples, then
+                                                psvi_laplace_sample_full (the
+                                                diagonal=False path), and that
+                                                entry alone
   PSVI_REFERENCE=<tree> python tools/laplace_probe.py --reference
                                                 the reference on this CPU
 
@@ -31,22 +35,33 @@ def problem():
     return x, y, w, torch.randn(D, generator=g), torch.randn(S, D, generator=g)
 
 
-def gpu(warmup, reps):
+def gpu(warmup, reps, full=False):
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                     "blackbox-coresets-vi_amd"))
-    from psvi.runtime import laplace_fit
+    from psvi.runtime import laplace_fit, laplace_sample_full
 
     x, y, w, theta0, eps = (t.cuda().contiguous() for t in problem())
-    times = []
+    times, alone = [], []
     for i in range(warmup + reps):
         theta = theta0.clone()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         a.record()
-        laplace_fit(x, y, w, theta, T, LR, eps=eps)
+        laplace_fit(x, y, w, theta, T, LR, eps=None if full else eps)
         b.record()
-        b.synchronize()
+        if full:
+            laplace_sample_full(x, w, theta, eps=eps)
+        c.record()
+        c.synchronize()
         if i >= warmup:
-            times.append(a.elapsed_time(b))
+            times.append(a.elapsed_time(c))
+            alone.append(b.elapsed_time(c))
+    if full:
+        print(json.dumps(dict(what="psvi_laplace_fit + psvi_laplace_sample_full", Nu=NU, d=D,
+                              T=T, S=S, reps=reps, median_ms=statistics.median(times),
+                              min_ms=min(times), max_ms=max(times),
+                              sample_full_median_ms=statistics.median(alone),
+                              device=torch.cuda.get_device_name(0))))
+        return
     print(json.dumps(dict(what="psvi_laplace_fit", Nu=NU, d=D, T=T, reps=reps,
                           median_ms=statistics.median(times), min_ms=min(times),
                           max_ms=max(times), us_per_step=1e3 * statistics.median(times) / T,
@@ -84,7 +99,8 @@ def reference(reps):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", action="store_true")
+    ap.add_argument("--full", action="store_true")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     a = ap.parse_args()
-    reference(min(a.reps, 5)) if a.reference else gpu(a.warmup, a.reps)
+    reference(min(a.reps, 5)) if a.reference else gpu(a.warmup, a.reps, a.full)
