@@ -1303,6 +1303,72 @@ int psvi_laplace_fit(const psvi_laplace_fit_req* q, void* stream) {
     return 0;
 }
 
+namespace {
+// the descriptor's ranges of psvi_mfvi_fit and its shape; 0 or an error code
+int mfvi_fit_desc(const psvi_net_desc* d, MfviFitShape& s) {
+    if (!d) return fail(PSVI_EINVAL, "null descriptor");
+    if (d->n_layers < 2 || d->n_layers > kMfFitMaxL)
+        return fail(PSVI_EINVAL, "the MFVI fit supports 2 <= n_layers <= 4 (1..3 hidden layers)");
+    if (d->dims[0] < 1 || d->dims[0] > kMfFitMaxD)
+        return fail(PSVI_EINVAL, "the MFVI fit supports 1 <= dims[0] <= 128");
+    for (int l = 1; l < d->n_layers; ++l)
+        if (d->dims[l] < 1 || d->dims[l] > kMfFitMaxH)
+            return fail(PSVI_EINVAL, "the MFVI fit supports hidden dims in [1, 64]");
+    if (d->dims[d->n_layers] != 1) return fail(PSVI_EINVAL, "the MFVI fit needs one network output");
+    if (d->M < 1 || d->M > kMfFitMaxB) return fail(PSVI_EINVAL, "the MFVI fit supports 1 <= M <= 512");
+    if (d->S < 1 || d->S > kMfFitMaxS) return fail(PSVI_EINVAL, "the MFVI fit supports 1 <= S <= 64");
+    if (!(d->prior_sd > 0.f) || !std::isfinite(d->prior_sd))
+        return fail(PSVI_EINVAL, "prior_sd must be finite and > 0");
+    if (mfvi_fit_shape(*d, s) != 0)
+        return fail(PSVI_EUNSUP, "the MFVI fit's working set does not fit the LDS");
+    return 0;
+}
+}  // namespace
+
+int psvi_mfvi_fit_query(const psvi_net_desc* d, int64_t* out) {
+    MfviFitShape s;
+    if (int rc = mfvi_fit_desc(d, s)) return rc;
+    if (!out) return fail(PSVI_EINVAL, "null pointer");
+    out[0] = s.lds ? 1 : 0;
+    out[1] = (int64_t)s.ws_bytes;
+    out[2] = 2 * (int64_t)s.n_tot;
+    out[3] = s.eps_count;
+    return 0;
+}
+
+int psvi_mfvi_fit(const psvi_mfvi_fit_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    MfviFit r;
+    if (int rc = mfvi_fit_desc(q->desc, r.shape)) return rc;
+    if (q->G < 1 || q->G > kMfFitMaxG) return fail(PSVI_EINVAL, "the MFVI fit supports 1 <= G <= 16");
+    if (q->T < 0 || q->T > kMfFitMaxT) return fail(PSVI_EINVAL, "the MFVI fit supports 0 <= T <= 1048576");
+    if (q->step0 < 0 || (int64_t)q->step0 + q->T > (int64_t(1) << 30))
+        return fail(PSVI_EINVAL, "the MFVI fit supports 0 <= step0, step0 + T <= 2^30");
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    if (!pos(q->lr) || !pos(q->beta1) || !pos(q->beta2) || q->beta1 >= 1.0 || q->beta2 >= 1.0 ||
+        !pos(q->adam_eps) || !pos(q->scale))
+        return fail(PSVI_EINVAL, "bad Adam constants or scale");
+    if (!q->x || !q->y || !q->tau || !q->params || !q->adam_m || !q->adam_v ||
+        (!q->eps && !q->offset))
+        return fail(PSVI_EINVAL, "null pointer");
+    for (int g = 0; g < q->G; ++g) {
+        if (!pos(q->tau[g])) return fail(PSVI_EINVAL, "tau must be finite and > 0");
+        if (!q->eps && (q->offset[g] & 3)) return fail(PSVI_EINVAL, "offset must be a multiple of 4");
+    }
+    const size_t need = r.shape.ws_bytes * (size_t)q->G;
+    if (need > 0 && !q->ws) return fail(PSVI_EINVAL, "null pointer");
+    if (q->ws_bytes < need) return fail(PSVI_ENOSPC, "workspace too small");
+    for (int l = 0; l <= q->desc->n_layers; ++l) r.dims[l] = q->desc->dims[l];
+    r.G = q->G; r.T = q->T; r.step0 = q->step0;
+    r.x = q->x; r.y = q->y; r.scale = q->scale; r.prior_sd = q->desc->prior_sd;
+    r.tau = q->tau; r.offset = q->eps ? nullptr : q->offset; r.seed = q->seed; r.eps = q->eps;
+    r.params = q->params; r.m = q->adam_m; r.v = q->adam_v;
+    r.lr = q->lr; r.beta1 = q->beta1; r.beta2 = q->beta2; r.adam_eps = q->adam_eps;
+    r.loss_out = q->loss_out; r.ws = q->ws;
+    HIP_TRY(launch_mfvi_fit(r, as_stream(stream)));
+    return 0;
+}
+
 int psvi_laplace_sample_full(const psvi_laplace_sample_full_req* q, void* stream) {
     if (!q) return fail(PSVI_EINVAL, "null request");
     if (q->d < 2 || q->d > kLapFullMaxD || q->n_core < 0 || q->n_core > kLapMaxNu || q->S < 0 ||

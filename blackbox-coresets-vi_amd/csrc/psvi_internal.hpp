@@ -897,6 +897,43 @@ struct GigaStep {
     double* result = nullptr;       // [8]
 };
 hipError_t launch_giga_step(const GigaStep& r, hipStream_t st);
+// MFVI regressor fit (kernels_mfvi_fit.hip): T chained steps of a mean-field
+// Gaussian-likelihood MLP on a fixed batch for G members, one workgroup each.
+constexpr int kMfFitThreads = 512;
+constexpr size_t kMfFitLds = 160 * 1024;
+constexpr int kMfFitMaxL = 4;    // affine layers: 1..3 hidden layers and the head
+constexpr int kMfFitMaxG = 16;
+constexpr int kMfFitMaxD = 128, kMfFitMaxH = 64, kMfFitMaxB = 512, kMfFitMaxS = 64;
+constexpr int kMfFitMaxT = 1 << 20;
+// what a descriptor's fit needs: the placement of the state (params / m / v,
+// the accumulators and the batch: LDS, or global memory with the per-member
+// workspace ws_bytes), the rows per chunk and the LDS strides
+struct MfviFitShape {
+    int L = 0, B = 0, S = 0, n_tot = 0, hs = 0, xs = 0, RB = 0;
+    int64_t eps_count = 0;
+    bool lds = false;
+    size_t ws_bytes = 0;
+};
+// 0, or PSVI_EUNSUP when not even one row fits beside the working set
+int mfvi_fit_shape(const psvi_net_desc& d, MfviFitShape& s);
+struct MfviFit {
+    MfviFitShape shape;
+    int dims[kMfFitMaxL + 1] = {};
+    int G = 0, T = 0, step0 = 0;
+    const float* x = nullptr;       // [B][D]
+    const float* y = nullptr;       // [B]
+    double scale = 1.0;
+    float prior_sd = 1.f;
+    const float* tau = nullptr;     // host, [G]
+    const uint64_t* offset = nullptr;  // host, [G]; null with eps
+    uint64_t seed = 0;
+    const float* eps = nullptr;     // [G][T][eps_count], null: Philox
+    float *params = nullptr, *m = nullptr, *v = nullptr;  // [G][2 n_tot], in / out
+    double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8;
+    double* loss_out = nullptr;     // [G][T], nullable
+    void* ws = nullptr;             // G * shape.ws_bytes
+};
+hipError_t launch_mfvi_fit(const MfviFit& r, hipStream_t st);
 // outer objective (kernels_outer.hip)
 hipError_t launch_outer_stats(const psvi_plan& p, const float* params, const float* eps,
                               const float* x, double* stats, hipStream_t st);

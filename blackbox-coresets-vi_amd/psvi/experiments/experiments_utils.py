@@ -14,7 +14,8 @@ from torch.utils.data import Dataset
 
 __all__ = ["SynthDataset", "split_data", "make_four_class_dataset", "make_synthetic",
            "make_synthetic_normal", "make_mnist_shaped", "read_dataset", "rec_dd",
-           "write_to_files"]
+           "write_to_files", "read_regression_dataset", "hyperparams_for_regression",
+           "update_hyperparams_dict", "make_synth_regr"]
 
 
 class SynthDataset(Dataset):
@@ -142,6 +143,105 @@ def read_dataset(dnm, method_args):
     x, y, xt, yt = X[:-test_size], Y[:-test_size], X[-test_size:], Y[-test_size:]
     N, D = x.shape
     return x, y, xt, yt, N, D, SynthDataset(x, y), SynthDataset(xt, yt), nc
+
+
+def hyperparams_for_regression():
+    """experiments_utils.py:281-296: the grid of candidate precisions tau per
+    regression dataset ("synth_regr" is this project's offline set)."""
+    return {
+        "concrete": [0.025, 0.05, 0.075],
+        "energy": [0.25, 0.5, 0.75],
+        "power": [0.05, 0.1, 0.15],
+        "kin8nm": [150, 200, 250],
+        "protein": [0.025, 0.05, 0.075],
+        "naval": [30000, 40000, 50000],
+        "yacht": [0.25, 0.5, 0.75],
+        "boston": [0.1, 0.15, 0.2],
+        "wine": [2.5, 3.0, 3.5],
+        "year": [0.1, 1.0, 10.0],
+        "synth_regr": [0.1, 1.0, 10.0],
+    }
+
+
+# local files of the UCI sets that parse without extra packages (the
+# reference's names, experiments_utils.py:229-264); (file, loader)
+_REGRESSION_FILES = {
+    "yacht": ("yacht_hydrodynamics.data", lambda f: np.loadtxt(f)),
+    "boston": ("housing.data", lambda f: np.loadtxt(f)),
+    "protein": ("CASP.csv", lambda f: np.loadtxt(f, delimiter=",", skiprows=1)),
+    "wine": ("winequality-red.csv", lambda f: np.loadtxt(f, delimiter=";", skiprows=1)),
+    "year": ("YearPredictionMSD.txt", lambda f: np.loadtxt(f, delimiter=",")),
+    "naval": (os.path.join("UCI CBM Dataset", "data.txt"), lambda f: np.loadtxt(f)),
+}
+
+
+def make_synth_regr(num_datapoints=400, D=5, seed=0):
+    """The offline regression set "synth_regr" (not in the reference): X ~ N(0,
+    I_D), y = 3 + 2 sin(x . a) + x . b + 0.3 noise, from numpy's RandomState(seed)."""
+    rs = np.random.RandomState(seed)
+    X = rs.randn(num_datapoints, D)
+    a, b = rs.randn(D) / np.sqrt(D), rs.randn(D) / np.sqrt(D)
+    Y = 3.0 + 2.0 * np.sin(X @ a) + X @ b + 0.3 * rs.randn(num_datapoints)
+    return X, Y[:, None]
+
+
+def read_regression_dataset(dnm, method_args):
+    """experiments_utils.py:159-214 without downloads: returns (x, y, xv, yv, xt,
+    yt, N, D, train_dataset, val_dataset, test_dataset, y_mean, y_std, taus).
+    Split (-1, 0.1, num_test) from seed ``method_args["seed"]``; inputs
+    normalised by the training statistics; training targets normalised, the
+    validation / test targets in original units.  "synth_regr" is generated
+    (``synth_regr_n`` / ``synth_regr_d`` rows / columns); a UCI name is read from
+    ``method_args["data_folder"]`` when its file is there."""
+    seed = method_args.get("seed", 42)
+    if dnm == "synth_regr":
+        X, Y = make_synth_regr(method_args.get("synth_regr_n", 400),
+                               method_args.get("synth_regr_d", 5), seed)
+    elif dnm in hyperparams_for_regression():
+        folder = method_args.get("data_folder")
+        path = os.path.join(folder, _REGRESSION_FILES[dnm][0]) if (
+            folder and dnm in _REGRESSION_FILES) else None
+        if path is None or not os.path.exists(path):
+            raise NotImplementedError(
+                f"dataset {dnm!r} is a remote download in the reference: offline, it is read "
+                "from method_args['data_folder'] only (yacht, boston, protein, wine, year, naval "
+                "as plain text files)")
+        data = _REGRESSION_FILES[dnm][1](path)
+        X, Y = (data[:, :-2], data[:, -2:-1]) if dnm == "naval" else (data[:, :-1], data[:, -1:])
+    else:
+        raise ValueError(f"Unsupported dataset: {dnm}")
+    np.random.seed(seed)
+    indices = split_data(len(X), p_split=(-1, 0.1, method_args.get("num_test", 0.15)))
+    taus = hyperparams_for_regression()[dnm]
+    x, y, xv, yv, xt, yt = (X[indices["train"]], Y[indices["train"]], X[indices["val"]],
+                            Y[indices["val"]], X[indices["test"]], Y[indices["test"]])
+    N, D = x.shape
+    x_mean, y_mean, x_std, y_std = np.mean(x, 0), np.mean(y), np.std(x, 0), np.std(y)
+
+    def norm(a):
+        return torch.from_numpy(((a - x_mean) / x_std).astype(np.float32))
+
+    train_dataset = SynthDataset(norm(x), torch.from_numpy(((y - y_mean) / y_std).astype(np.float32)))
+    val_dataset = SynthDataset(norm(xv), torch.from_numpy(yv.astype(np.float32)))
+    test_dataset = SynthDataset(norm(xt), torch.from_numpy(yt.astype(np.float32)))
+    return (x, y, xv, yv, xt, yt, N, D, train_dataset, val_dataset, test_dataset,
+            torch.tensor(y_mean), torch.tensor(y_std), taus)
+
+
+def update_hyperparams_dict(dnm, best_tau, fnm="opt_regr_hyperparams.json",
+                            results_folder="results"):
+    """experiments_utils.py:838-849 (a stub there, aimed at psvi/data/): record
+    the selected precision of a dataset in <results_folder>/<fnm>."""
+    os.makedirs(results_folder, exist_ok=True)
+    path = os.path.join(results_folder, fnm)
+    opt_taus = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            opt_taus = json.load(f)
+    opt_taus[dnm] = float(best_tau)
+    with open(path, "w") as f:
+        json.dump(opt_taus, f)
+    return opt_taus
 
 
 def rec_dd():

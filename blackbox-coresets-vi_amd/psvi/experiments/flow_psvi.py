@@ -12,20 +12,20 @@ every rank holds the same u, v and network after every step); the MFVI
 baselines have no sample-sharded form and run whole on every rank.  Rank 0
 alone writes the results files."""
 from ..inference import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV, PSVILearnV,
-                         PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, run_mfvi, run_mfvi_subset,
-                         run_opsvi, run_random, run_sparsevi, run_sparsevi_with_bb_elbo)
-from .experiments_utils import read_dataset, rec_dd, write_to_files
+                         PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, PSVI_regressor,
+                         PSVIAV_regressor, PSVILearnV_regressor, run_mfvi, run_mfvi_regressor,
+                         run_mfvi_subset, run_mfvi_subset_regressor, run_opsvi, run_random,
+                         run_sparsevi, run_sparsevi_with_bb_elbo)
+from .experiments_utils import read_dataset, read_regression_dataset, rec_dd, write_to_files
 
 
 def _psvi(cls):
     return lambda *a, **kw: cls(*a, **kw).run_psvi(*a, **kw)
 
 
-# flow_psvi.py:306-354.  Not wired here: the regression variants -- their
-# classes run on the HIP path (psvi.inference.PSVI_regressor,
-# PSVILearnV_regressor, PSVIAV_regressor), but the reference's regression
-# datasets are remote downloads and read_dataset returns no y_mean / y_std --
-# and giga (psvi.inference.run_giga runs on the HIP path; call it directly).  sparsebbvi runs on it
+# flow_psvi.py:306-354.  The regression variants have their own table and
+# driver below (regressor_inf_dict, regressor_experiment_driver).  Not wired
+# here: giga (psvi.inference.run_giga runs on the HIP path; call it directly).  sparsebbvi runs on it
 # (Bernoulli plans, one output), and so do the Laplace baselines random,
 # sparsevi and opsvi (psvi_laplace_fit, psvi_laplace_scores).
 inf_dict = {
@@ -101,6 +101,72 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
                         **(dict(outer_it=method_args["outer_it"])
                            if nm_alg == "sparsevi" else {}))
     if write and rank == 0:
+        return write_to_files(results, method_args.get("fnm", "results"),
+                              method_args.get("results_folder", "results"))
+    return results
+
+
+# flow_psvi.py:336-353: the regression methods, looked up as nm_alg + "_regressor"
+regressor_inf_dict = {
+    "psvi_regressor": _psvi(PSVI_regressor),
+    "psvi_learn_v_regressor": _psvi(PSVILearnV_regressor),
+    "psvi_alpha_v_regressor": _psvi(PSVIAV_regressor),
+    "mfvi_regressor": run_mfvi_regressor,
+    "mfvi_subset_regressor": run_mfvi_subset_regressor,
+}
+
+
+def regressor_experiment_driver(datasets, methods, method_args, write=True):
+    """flow_psvi.regressor_experiment_driver (flow_psvi.py:459-549): BNN
+    regression over read_regression_dataset's sets ("synth_regr", or a UCI set
+    read from method_args["data_folder"]).  methods name the algorithms without
+    the suffix ("psvi", "psvi_learn_v", "psvi_alpha_v", "mfvi", "mfvi_subset");
+    results[dataset][method][size][trial].  As in the reference the dataset's
+    split uses seed 42 and num_test 0.15, the architecture is 'regressor_net'
+    and the PSVI regressors run at their own tau (method_args["tau"], default
+    0.1) while the MFVI baselines search the dataset's tau grid."""
+    results = rec_dd()
+    for dnm in datasets:
+        method_args["seed"], method_args["num_test"] = 42, .15
+        (x, y, xv, yv, xt, yt, N, D, train_dataset, val_dataset, test_dataset, y_mean, y_std,
+         taus) = read_regression_dataset(dnm, method_args)
+        for nm_alg in methods:
+            if nm_alg + "_regressor" not in regressor_inf_dict:
+                raise NotImplementedError(f"method {nm_alg!r} has no regression form on the "
+                                          "HIP path")
+            inf_alg = regressor_inf_dict[nm_alg + "_regressor"]
+            compute_weights_entropy = (not nm_alg.startswith("mfvi_subset")
+                                       and method_args.get("compute_weights_entropy", True))
+            sizes = (method_args["coreset_sizes"]
+                     if nm_alg.startswith(("psvi", "mfvi_subset")) else [-1])
+            extra = dict(tau=method_args["tau"]) if (
+                nm_alg.startswith("psvi") and "tau" in method_args) else {}
+            for t in range(method_args["num_trials"]):
+                for ps in sizes:
+                    results[dnm][nm_alg][ps][t] = inf_alg(
+                        **extra,
+                        mc_samples=method_args["mc_samples"],
+                        num_epochs=method_args["num_epochs"],
+                        data_minibatch=method_args["data_minibatch"],
+                        D=D, N=N, tr=t, x=x, y=y, xv=xv, yv=yv, xt=xt, yt=yt,
+                        inner_it=method_args["inner_it"],
+                        logistic_regression=False,
+                        trainer=method_args["trainer"],
+                        log_every=method_args["log_every"],
+                        register_elbos=method_args.get("register_elbos", False),
+                        lr0u=method_args["lr0u"], lr0net=method_args["lr0net"],
+                        lr0v=method_args["lr0v"],
+                        init_args=method_args.get("init_at", "subsample"),
+                        init_sd=method_args["init_sd"], num_pseudo=ps, seed=t,
+                        compute_weights_entropy=compute_weights_entropy,
+                        architecture=method_args.get("architecture", "regressor_net"),
+                        log_pseudodata=method_args.get("log_pseudodata", False),
+                        n_hidden=method_args.get("n_hidden", 40),
+                        n_layers=method_args.get("n_layers", 1),
+                        train_dataset=train_dataset, val_dataset=val_dataset,
+                        test_dataset=test_dataset, dnm=dnm, y_mean=y_mean, y_std=y_std,
+                        taus=taus, results_folder=method_args.get("results_folder", "results"))
+    if write:
         return write_to_files(results, method_args.get("fnm", "results"),
                               method_args.get("results_folder", "results"))
     return results

@@ -3,5 +3,6 @@ from .psvi_classes import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV,  # 
                            PSVILearnV, PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, HipInnerELBO,
                            PSVI_regressor, PSVILearnV_regressor, PSVIAV_regressor)
 from .baselines import (run_mfvi, run_mfvi_subset, run_random, run_sparsevi,  # noqa: F401,E402
-                        run_opsvi, run_giga, run_laplace, process_wt_index)
+                        run_opsvi, run_giga, run_laplace, process_wt_index, fit,
+                        run_mfvi_regressor, run_mfvi_subset_regressor)
 from .sparsebbvi import run_sparsevi_with_bb_elbo  # noqa: F401,E402

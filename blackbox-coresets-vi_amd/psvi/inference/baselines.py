@@ -14,6 +14,43 @@ averages the LOGITS over samples (baselines.py:898-906) and runs the model's
 torch forward on the device (not the hot path).  There is no CPU fallback:
 the training step raises without the HIP library or a device.
 
+MFVI regression baselines ("MFVI regressor fit"):
+
+  fit                        baselines.py:1283-1346  the ELBO fit and its predictive logs
+  run_mfvi_regressor         baselines.py:1066-1169  MFVI on the training set, tau by validation
+  run_mfvi_subset_regressor  baselines.py:1172-1278  MFVI on a fixed random subset
+
+A fit is psvi_mfvi_fit: every Adam step of the mean-field Gaussian-likelihood
+MLP in one launch per segment between logging checkpoints (``log_every == -1``:
+one launch for the whole fit), ``elbos`` read from its per-step losses
+afterwards.  The predictive log is psvi_evaluate_regression with no
+pseudopoints and uniform weights: the mean prediction over the samples in the
+targets' units, the squared error and the log-density with scale 1 / sqrt(tau).
+Model selection fits every candidate tau in ONE call (one workgroup per tau).
+Reference behaviours kept:
+
+* ``fit`` takes ``next(iter(train_loader))`` of a loader built with
+  ``shuffle=False`` at every step: the same first minibatch, scaled by
+  ``n_train / B``, for the whole fit (the subset variant: its one subset
+  batch).  This is what makes the single-launch fit exact.
+* The loss sums the NLL over the S samples too; ``elbos`` holds -loss before
+  each step; ``times`` one entry per logging checkpoint.
+* ``bpe = max(1, int(n_train / data_minibatch))`` and ``epochs = num_epochs *
+  bpe`` steps; a logging checkpoint at ``it % log_every == 0``, or at the last
+  step alone when ``log_every == -1``.
+* Each candidate tau gets a newly initialised net, drawn from the continuing
+  torch generator in tau order, then the final fit another one (the loaders'
+  own draws of a base seed are kept out of that stream); ``best_tau``
+  moves only on a strictly larger last validation log-likelihood.
+* The subset is ``random.sample(range(n_train), num_pseudo)`` after the reseed,
+  its scale ``n_train / num_pseudo`` (n_train the whole training set); it
+  selects tau only on request.
+* The Philox offsets continue from fit to fit as the sequential fits would
+  consume the stream (training steps, then the evaluation draws).
+The nets are make_regressor_net's (``n_hidden`` units, ``n_layers`` hidden
+layers, default 2 as the reference's set_up_model builds 'regressor_net');
+the predictive log needs mc_samples >= 2 (psvi_evaluate_regression).
+
 Laplace coreset baselines ("Laplace baselines"):
 
   run_random    baselines.py:118-203   uniform random coreset, weights N / |core|
@@ -102,13 +139,13 @@ import torch.nn as nn
 from torch.utils.data import DataLoader
 
 from ..models import (VILinear, VILinearMultivariateNormal, categorical_fn, make_fc2net,
-                      make_fcnet, make_lenet, model_spec)
+                      make_fcnet, make_lenet, make_regressor_net, model_spec)
 from ..runtime import (InnerLoopPlan, adam_update_, check_binary, giga_step, laplace_fit,
-                       laplace_sample_full, laplace_scores, randn_)
+                       laplace_sample_full, laplace_scores, mfvi_fit, randn_)
 
 __all__ = ["set_up_model", "pseudo_subsample_init", "pseudo_rand_init", "run_mfvi",
            "run_mfvi_subset", "process_wt_index", "run_laplace", "run_random", "run_sparsevi",
-           "run_opsvi", "run_giga"]
+           "run_opsvi", "run_giga", "fit", "run_mfvi_regressor", "run_mfvi_subset_regressor"]
 
 
 def set_up_model(D=None, n_hidden=None, nc=None, mc_samples=None, architecture=None,
@@ -309,6 +346,220 @@ def run_mfvi_subset(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibat
     stepper.sync_model()
     return {"accs": accs, "nlls": nlls, "times": times[1:], "elbos": elbos,
             "csizes": [num_pseudo] * (mul_fact * num_epochs)}
+
+
+# ------------------------------------------------------- MFVI regression baselines
+class _Noise:
+    """Where a fit's noise comes from: ``eps_source(n)`` (n floats per training
+    step or evaluation draw, in the reference's order) or the library's Philox
+    stream (seed, a running offset)."""
+
+    def __init__(self, seed=0, offset=0, eps_source=None):
+        self.seed, self.offset, self.source = int(seed), int(offset), eps_source
+
+
+def _fit_members(nets, taus, train_loader, pred_loader, revert_norm, log_every, epochs, device,
+                 lr, noise, n_train=None):
+    """fit for G = len(nets) members that share everything but tau, their
+    parameters and their noise: one psvi_mfvi_fit call per segment."""
+    G, epochs = len(nets), int(epochs)
+    fam, layers, prior_sd, S = model_spec(nets[0])
+    if fam != "meanfield" or layers[-1][1] != 1:
+        raise NotImplementedError("fit runs mean-field nets with one output (make_regressor_net)")
+    if n_train is None:
+        n_train = len(train_loader.dataset)
+    # iterating a DataLoader draws its base seed from torch's generator: keep that out of
+    # the stream the nets are initialised from
+    with torch.random.fork_rng(devices=[]):
+        xb, yb = next(iter(train_loader))
+        pred_batches = list(pred_loader)
+    B = int(xb.shape[0])
+    x = xb.detach().to(device, torch.float32).reshape(B, -1).contiguous()
+    y = yb.detach().to(device, torch.float32).reshape(-1).contiguous()
+    scale = n_train / B
+    zero = torch.zeros(())
+    y_mean = float(revert_norm(zero))
+    y_std = float(revert_norm(zero + 1.0)) - y_mean
+    plists = [list(net.parameters()) for net in nets]
+    with torch.no_grad():
+        params = torch.stack([nn.utils.parameters_to_vector(pl).detach().to(device, torch.float32)
+                              for pl in plists]).contiguous()
+    m, v = torch.zeros_like(params), torch.zeros_like(params)
+    E = S * sum(i * o + o for i, o in layers)
+    stride = (E + 3) // 4 * 4
+    pred = [(xt.detach().to(device, torch.float32).reshape(int(xt.shape[0]), -1).contiguous(),
+             yt.detach().to(device, torch.float32).reshape(-1).contiguous())
+            for xt, yt in pred_batches]
+    plans = {}
+    if log_every > 0:
+        marks = [e for e in range(epochs) if e % log_every == 0]
+    else:
+        marks = [epochs - 1] if epochs > 0 else []
+    ends = [e + 1 for e in marks]
+    if epochs > 0 and (not ends or ends[-1] != epochs):
+        ends.append(epochs)
+    # a member's draws in the reference's order: each segment's steps, then its evaluation
+    seg_T = [b - a for a, b in zip([0] + ends[:-1], ends)]
+    logs = [e - 1 in marks for e in ends]
+    per_member = sum(T + (len(pred) if lg else 0) for T, lg in zip(seg_T, logs))
+    if noise.source is not None:
+        drawn = [[(noise.source(T * E).to(device, torch.float32).reshape(T, E),
+                   [noise.source(E).to(device, torch.float32).contiguous() for _ in pred]
+                   if lg else []) for T, lg in zip(seg_T, logs)] for _ in range(G)]
+    offs = [noise.offset + g * per_member * stride for g in range(G)]
+    noise.offset += G * per_member * stride
+    res = [dict(rmses=[], lls=[], times=[0], elbos=[], scale=1.0 / np.sqrt(tau)) for tau in taus]
+    t_start = time.time()
+    losses, done = [], 0
+    for k, (T, lg) in enumerate(zip(seg_T, logs)):
+        if noise.source is not None:
+            eps = torch.stack([drawn[g][k][0] for g in range(G)]).contiguous()
+            out = mfvi_fit(layers, S, x, y, scale, taus, params, T, lr, adam_m=m, adam_v=v,
+                           step0=done, eps=eps, prior_sd=prior_sd)
+        else:
+            out = mfvi_fit(layers, S, x, y, scale, taus, params, T, lr, adam_m=m, adam_v=v,
+                           step0=done, seed=noise.seed, offsets=offs, prior_sd=prior_sd)
+            offs = [o + T * stride for o in offs]
+        losses.append(out["loss"])
+        done += T
+        if not lg:
+            continue
+        for g, tau in enumerate(taus):
+            se, ll, total = 0.0, 0.0, 0
+            for b, (xt, yt) in enumerate(pred):
+                Bt = int(xt.shape[0])
+                key = (Bt, float(tau))
+                if key not in plans:
+                    plans[key] = InnerLoopPlan("meanfield", layers, S, Bt, prior_sd=prior_sd,
+                                               likelihood=("gaussian", tau))
+                if noise.source is not None:
+                    eps_e = drawn[g][k][1][b]
+                else:
+                    eps_e = randn_(torch.empty(E, device=device), noise.seed, offs[g])
+                    offs[g] += stride
+                stats, _ = plans[key].evaluate_regression(0, xt, yt, yt, eps_e, params[g],
+                                                          y_mean=y_mean, y_std=y_std,
+                                                          correction=False)
+                stats = stats.tolist()
+                se, ll, total = se + stats[2], ll + stats[3], total + Bt
+            r = res[g]
+            r["times"].append(r["times"][-1] + time.time() - t_start)
+            r["lls"].append(ll / float(total))
+            r["rmses"].append(float(np.sqrt(se / float(total))))
+    allloss = torch.cat(losses, 1).cpu() if losses else torch.zeros(G, 0)
+    for g, r in enumerate(res):
+        r["elbos"] = (-allloss[g]).tolist()
+        r["times"] = r["times"][1:]
+        with torch.no_grad():
+            nn.utils.vector_to_parameters(params[g].to(plists[g][0].device, plists[g][0].dtype),
+                                          plists[g])
+    return res
+
+
+def fit(net=None, optim_vi=None, train_loader=None, pred_loader=None, revert_norm=None,
+        log_every=-1, tau=1e-2, epochs=40, device=None, lr=None, seed=0, offset=0,
+        eps_source=None):
+    """The reference's fit (baselines.py:1283-1346) on psvi_mfvi_fit: ``epochs``
+    torch-Adam steps of the mean-field ELBO on the loader's first minibatch,
+    the predictive rmse / log-likelihood of ``pred_loader`` at the logging
+    checkpoints.  The learning rate is ``lr`` or ``optim_vi``'s (a new Adam:
+    its moments start at zero here); ``revert_norm`` must be the affine map
+    y * y_std + y_mean.  Noise: ``eps_source(n)`` or the Philox stream (seed,
+    offset).  ``net`` ends with the fitted parameters.  Returns {rmses, lls,
+    times, elbos, scale}."""
+    device = _device()
+    if lr is None:
+        if optim_vi is None:
+            raise ValueError("fit needs lr or optim_vi")
+        lr = optim_vi.param_groups[0]["lr"]
+    return _fit_members([net], [float(tau)], train_loader, pred_loader, revert_norm, log_every,
+                        epochs, device, float(lr), _Noise(seed, offset, eps_source))[0]
+
+
+def _regressor_net(D, n_hidden, n_layers, mc_samples, init_sd, nc=1):
+    return make_regressor_net(D, n_hidden, nc, n_layers=n_layers, linear_class=VILinear,
+                              nonl_class=nn.ReLU, mc_samples=mc_samples, init_sd=init_sd)
+
+
+def _run_regressor(train_loader, n_train, mc_samples, data_minibatch, num_epochs, log_every, D,
+                   lr0net, seed, n_hidden, n_layers, val_dataset, test_dataset, nc, y_mean, y_std,
+                   taus, init_sd, model_selection, dnm, eps_source, results_folder):
+    device = _device()
+    if nc != 1:
+        raise NotImplementedError("the regression baselines have one network output (nc=1)")
+    if not taus:
+        raise ValueError("taus must hold at least one precision")
+    test_loader = DataLoader(test_dataset, batch_size=data_minibatch, shuffle=False)
+    val_loader = DataLoader(val_dataset, batch_size=data_minibatch, shuffle=False)
+    bpe = max(1, int(n_train / data_minibatch))  # batches per epoch
+    y_mean, y_std = float(y_mean), float(y_std)
+
+    def revert_norm(y_pred):
+        return y_pred * y_std + y_mean
+
+    noise = _Noise(seed, 0, eps_source)
+    best_tau, best_ll = taus[0], -float("inf")
+    if model_selection:
+        nets = [_regressor_net(D, n_hidden, n_layers, mc_samples, init_sd) for _ in taus]
+        fits = _fit_members(nets, [float(t) for t in taus], train_loader, val_loader, revert_norm,
+                            -1, num_epochs * bpe, device, lr0net, noise, n_train)
+        for tau, tau_fit in zip(taus, fits):
+            if tau_fit["lls"][-1] > best_ll:
+                best_tau, best_ll = tau, tau_fit["lls"][-1]
+    if dnm is not None:
+        from ..experiments.experiments_utils import update_hyperparams_dict
+
+        update_hyperparams_dict(dnm, best_tau, results_folder=results_folder)
+    net = _regressor_net(D, n_hidden, n_layers, mc_samples, init_sd)
+    return _fit_members([net], [float(best_tau)], train_loader, test_loader, revert_norm,
+                        log_every, num_epochs * bpe, device, lr0net, noise, n_train)[0]
+
+
+def run_mfvi_regressor(mc_samples=4, data_minibatch=128, num_epochs=100, log_every=10, D=None,
+                       lr0net=1e-3, seed=0, architecture=None, n_hidden=None, train_dataset=None,
+                       val_dataset=None, test_dataset=None, nc=1, y_mean=None, y_std=None,
+                       taus=None, init_sd=1e-6, model_selection=True, dnm=None, n_layers=2,
+                       eps_source=None, results_folder="results", **kwargs):
+    """MFVI for BNN regression on the training set (baselines.py:1066-1169): tau
+    chosen on the validation set over ``taus`` (all candidates in one
+    psvi_mfvi_fit call), then the fit of the chosen tau logged on the test set.
+    Returns {rmses, lls, times, elbos, scale}."""
+    if architecture not in (None, "regressor_net"):
+        raise NotImplementedError(f"architecture {architecture!r}: the regression baselines "
+                                  "build 'regressor_net'")
+    _device()
+    random.seed(seed), np.random.seed(seed), torch.manual_seed(seed)
+    train_loader = DataLoader(train_dataset, batch_size=data_minibatch, shuffle=False)
+    return _run_regressor(train_loader, len(train_dataset), mc_samples, data_minibatch,
+                          num_epochs, log_every, D, lr0net, seed, n_hidden, n_layers, val_dataset,
+                          test_dataset, nc, y_mean, y_std, taus, init_sd, model_selection, dnm,
+                          eps_source, results_folder)
+
+
+def run_mfvi_subset_regressor(mc_samples=4, data_minibatch=128, num_epochs=100, log_every=10,
+                              D=None, lr0net=1e-3, seed=0, architecture=None, n_hidden=None,
+                              train_dataset=None, val_dataset=None, test_dataset=None, nc=1,
+                              y_mean=None, y_std=None, init_sd=1e-6, num_pseudo=100, taus=None,
+                              model_selection=False, n_layers=2, eps_source=None, **kwargs):
+    """MFVI on a fixed random subset of num_pseudo training rows
+    (baselines.py:1172-1278), loss scale n_train / num_pseudo with n_train the
+    whole training set's size, as run_mfvi_subset scales its subset (the
+    reference's fit reads the length of the loader it is given, which for the
+    subset loader is num_pseudo itself: scale 1).  Returns fit's dict plus
+    csizes = [num_pseudo]."""
+    if architecture not in (None, "regressor_net"):
+        raise NotImplementedError(f"architecture {architecture!r}: the regression baselines "
+                                  "build 'regressor_net'")
+    _device()
+    random.seed(seed), np.random.seed(seed), torch.manual_seed(seed)
+    sample_idcs = random.sample(range(len(train_dataset)), num_pseudo)
+    subset = torch.utils.data.Subset(train_dataset, sample_idcs)
+    subset_loader = DataLoader(subset, batch_size=num_pseudo, shuffle=False)
+    results = _run_regressor(subset_loader, len(train_dataset), mc_samples, data_minibatch, num_epochs, log_every, D, lr0net, seed,
+                             n_hidden, n_layers, val_dataset, test_dataset, nc, y_mean, y_std,
+                             taus, init_sd, model_selection, None, eps_source, "results")
+    results["csizes"] = [num_pseudo]
+    return results
 
 
 # ---------------------------------------------------------------- Laplace baselines

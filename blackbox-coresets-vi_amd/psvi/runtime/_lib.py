@@ -86,6 +86,24 @@ class LaplaceFitReq(ctypes.Structure):
     ]
 
 
+class MfviFitReq(ctypes.Structure):
+    _fields_ = [
+        ("desc", ctypes.POINTER(NetDesc)),
+        ("G", ctypes.c_int32), ("T", ctypes.c_int32), ("step0", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("scale", ctypes.c_double),
+        ("tau", ctypes.c_void_p),
+        ("params", ctypes.c_void_p), ("adam_m", ctypes.c_void_p), ("adam_v", ctypes.c_void_p),
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+        ("adam_eps", ctypes.c_double),
+        ("eps", ctypes.c_void_p),
+        ("seed", ctypes.c_uint64),
+        ("offset", ctypes.c_void_p),
+        ("loss_out", ctypes.c_void_p),
+        ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
 class LaplaceSampleFullReq(ctypes.Structure):
     _fields_ = [
         ("n_core", ctypes.c_int32), ("d", ctypes.c_int32), ("S", ctypes.c_int32),
@@ -174,6 +192,8 @@ SIGNATURES = {
     "psvi_select_weight_grad": (_I32, [_I32, _I32, _I32, _P, _P, _P, ctypes.c_double, _P, _P,
                                        _P]),
     "psvi_laplace_fit": (_I32, [ctypes.POINTER(LaplaceFitReq), _P]),
+    "psvi_mfvi_fit": (_I32, [ctypes.POINTER(MfviFitReq), _P]),
+    "psvi_mfvi_fit_query": (_I32, [ctypes.POINTER(NetDesc), ctypes.POINTER(_I64)]),
     "psvi_laplace_sample_full": (_I32, [ctypes.POINTER(LaplaceSampleFullReq), _P]),
     "psvi_laplace_scores": (_I32, [ctypes.POINTER(LaplaceScoresReq), _P]),
     "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),

@@ -747,6 +747,87 @@ def laplace_fit(x_core, y_core, w_core, theta, T, lr, eps=None, prior_mean=0.0, 
     return out
 
 
+def _mfvi_desc(layers, S, B, prior_sd):
+    layers = [tuple(int(x) for x in l) for l in layers]
+    if not 1 <= len(layers) <= _lib.MAX_LAYERS:
+        raise ValueError("1..8 layers supported")
+    for a, b in zip(layers[:-1], layers[1:]):
+        if a[1] != b[0]:
+            raise ValueError(f"layer sizes do not chain: {layers}")
+    d = NetDesc()
+    d.n_layers = len(layers)
+    for i, v in enumerate([layers[0][0]] + [o for _, o in layers]):
+        d.dims[i] = v
+    d.S, d.M, d.prior_sd = int(S), int(B), float(prior_sd)
+    return d
+
+
+def mfvi_fit_query(layers, S, B, prior_sd=1.0):
+    """What psvi_mfvi_fit does with a network (psvi_mfvi_fit_query; no device
+    needed): a dict with placement ("lds": params / adam_m / adam_v, the
+    gradient accumulators and the batch stay in LDS; "global": they are read
+    and written in global memory), ws_bytes (per member), param_count and
+    eps_count."""
+    d = _mfvi_desc(layers, S, B, prior_sd)
+    out = (ctypes.c_int64 * 4)()
+    check(_lib.load().psvi_mfvi_fit_query(ctypes.byref(d), out), "psvi_mfvi_fit_query")
+    return {"placement": "lds" if out[0] else "global", "ws_bytes": int(out[1]),
+            "param_count": int(out[2]), "eps_count": int(out[3])}
+
+
+def mfvi_fit(layers, S, x, y, scale, taus, params, T, lr, adam_m=None, adam_v=None, step0=0,
+             eps=None, seed=0, offsets=None, prior_sd=1.0, betas=(0.9, 0.999), adam_eps=1e-8,
+             want_loss=True):
+    """The fit of the MFVI regression baselines (psvi_mfvi_fit): T chained steps
+    of a mean-field Gaussian-likelihood MLP (layers [(in, out), ...], one
+    output, S samples) on the fixed batch x (B, D) / y (B), loss = scale *
+    sum_{s,b} NLL(tau_g) + KL, each followed by one torch.optim.Adam step, for
+    G = len(taus) independent members in one launch.  params (G, P) is updated
+    in place; adam_m / adam_v (G, P; zeros when None: a new fit) too, with
+    step0 the Adam steps already taken.  eps: (G, T, eps_count) device tensor
+    in the library's eps layout, or None for the Philox stream: member g's step
+    t takes what randn_(seed, offsets[g] + t * round_up(eps_count, 4)) writes
+    (offsets: G multiples of 4; default 0).  Returns a dict of device tensors:
+    params, adam_m, adam_v (the tensors updated in place) and loss (G, T
+    float64: the loss before each step; None unless want_loss)."""
+    taus = [float(v) for v in taus]
+    G, T = len(taus), int(T)
+    if x is None or x.dim() != 2:
+        raise ValueError("x must be the (B, D) batch")
+    B = int(x.shape[0])
+    q = mfvi_fit_query(layers, S, B, prior_sd)
+    P, E = q["param_count"], q["eps_count"]
+    _need(x, "x", B * int(layers[0][0]))
+    _need(y, "y", B)
+    _need(params, "params", G * P)
+    dev = params.device
+    if adam_m is None:
+        adam_m = torch.zeros(G, P, dtype=torch.float32, device=dev)
+    if adam_v is None:
+        adam_v = torch.zeros(G, P, dtype=torch.float32, device=dev)
+    _need(adam_m, "adam_m", G * P)
+    _need(adam_v, "adam_v", G * P)
+    if eps is not None:
+        _need(eps, "eps", G * T * E)
+    if offsets is None:
+        offsets = [0] * G
+    if len(offsets) != G:
+        raise ValueError("offsets must hold one Philox offset per member")
+    tau_h = (ctypes.c_float * G)(*taus)
+    off_h = (ctypes.c_uint64 * G)(*[int(o) for o in offsets])
+    loss = torch.empty(G, T, dtype=torch.float64, device=dev) if want_loss else None
+    ws = torch.empty(max(G * q["ws_bytes"], 1), dtype=torch.uint8, device=dev)
+    d = _mfvi_desc(layers, S, B, prior_sd)
+    req = _lib.MfviFitReq(
+        ctypes.pointer(d), G, T, int(step0), _ptr(x), _ptr(y), float(scale),
+        ctypes.cast(tau_h, ctypes.c_void_p), _ptr(params), _ptr(adam_m), _ptr(adam_v), float(lr),
+        float(betas[0]), float(betas[1]), float(adam_eps), _ptr(eps), int(seed) & (2**64 - 1),
+        ctypes.cast(off_h, ctypes.c_void_p), _ptr(loss), _ptr(ws), ws.numel())
+    check(_lib.load().psvi_mfvi_fit(ctypes.byref(req), _stream()), "psvi_mfvi_fit")
+    _wrote(params, adam_m, adam_v)
+    return {"params": params, "adam_m": adam_m, "adam_v": adam_v, "loss": loss}
+
+
 def laplace_sample_full(x_core, w_core, theta, eps=None, want_prec=False, want_factor=False,
                         want_logdet=False):
     """Samples from the full-precision Laplace posterior at the fitted mode

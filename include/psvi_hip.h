@@ -692,6 +692,74 @@ typedef struct psvi_giga_step_req {
 } psvi_giga_step_req;
 int psvi_giga_step(const psvi_giga_step_req* req, void* stream);
 
+/* ---- MFVI regression baselines (fit, run_mfvi_regressor) -------------------
+ * The whole fit of a mean-field Gaussian-likelihood MLP on a FIXED batch (fit,
+ * psvi/inference/baselines.py:1283-1346: every step takes next(iter(loader)) of
+ * an unshuffled loader), one launch, for G independent members -- one per
+ * candidate precision tau (run_mfvi_regressor's model selection,
+ * baselines.py:1117-1144) -- each on one persistent workgroup; nothing is
+ * shared between members, so a member's numbers depend on its own tau, offset
+ * and eps only, not on G or on its index.
+ * desc: the network (make_regressor_net, neural_net.py:300-331: Linear-ReLU
+ * ... Linear): dims[n_layers] == 1, S samples, M = the batch rows B, prior_sd.
+ * Each member runs T steps of
+ *   loss = scale sum_{s,b} [tau_g / 2 (f_sb - y_b)^2 + log(2 pi / tau_g) / 2]
+ *          + sum_layers KL(q || N(0, prior_sd^2))        (summed over s, not averaged)
+ * with the mean-field gradient of psvi_elbo_grad, each followed by one
+ * torch.optim.Adam step (PSVI_ADAM_TORCH arithmetic in fp32) with step number
+ * step0 + t + 1.  A new fit passes step0 = 0 and zeroed adam_m / adam_v; a fit
+ * split over calls carries params, adam_m, adam_v, step0 + T and (Philox mode)
+ * offset + T * round_up(EPS_COUNT, 4) to the next call and gives the numbers of
+ * one call bit for bit.
+ *   x ([B][D]), y ([B]): the batch, device fp32;  scale: n_train / B
+ *   tau    (G floats, HOST memory, finite and > 0)
+ *   params, adam_m, adam_v ([G][P] device floats, in / out), P =
+ *          PSVI_Q_PARAM_COUNT of a mean-field plan of desc (out[2] of the query)
+ *   eps    ([G][T][EPS_COUNT] device floats in the library's eps layout), or
+ *          NULL: member g's step t takes exactly what psvi_randn(seed,
+ *          offset[g] + t * round_up(EPS_COUNT, 4)) writes; offset (G uint64,
+ *          HOST memory, each a multiple of 4).  The two modes agree bit for bit.
+ *   loss_out ([G][T] device doubles, nullable) <- the loss before each step
+ *   ws     G * out[1] bytes of device scratch (may be NULL when out[1] == 0)
+ * tau and offset are read on the host during the call; every other pointer is
+ * a device pointer as everywhere else.
+ * Numerics: the network, the gradient sums and Adam accumulate in fp32 (the
+ * arithmetic of the step-by-step path), the per-row NLL terms, the sum of the
+ * KL terms and the bias corrections in fp64.  Every sum has one owner and a
+ * fixed order, the loss meets in a fixed tree: run-to-run bitwise equal; no
+ * atomics.
+ * Placement: params / adam_m / adam_v, the gradient accumulators and the batch
+ * stay in LDS when they fit the 160 KiB beside the working set (two n_tot
+ * vectors and a chunk of min(B, 16) rows' activations); otherwise they are
+ * read and written in global memory (the accumulators in ws).
+ * psvi_mfvi_fit_query: out[0] = 1 (LDS) / 0 (global memory), out[1] = ws bytes
+ * per member, out[2] = P, out[3] = EPS_COUNT; no device needed.
+ * Ranges (PSVI_EINVAL outside them): 2 <= n_layers <= 4 (1..3 hidden layers),
+ * dims[0] <= 128, hidden dims <= 64, dims[n_layers] == 1, 1 <= M <= 512,
+ * 1 <= S <= 64, prior_sd > 0, 1 <= G <= 16, 0 <= T <= 1048576, 0 <= step0,
+ * step0 + T <= 2^30, scale / lr / adam_eps finite and > 0, 0 < betas < 1;
+ * ws_bytes below G * out[1] is PSVI_ENOSPC. */
+typedef struct psvi_mfvi_fit_req {
+    const psvi_net_desc* desc;
+    int32_t G, T, step0;
+    const float* x;
+    const float* y;
+    double scale;
+    const float* tau;
+    float* params;
+    float* adam_m;
+    float* adam_v;
+    double lr, beta1, beta2, adam_eps;
+    const float* eps;
+    uint64_t seed;
+    const uint64_t* offset;
+    double* loss_out;
+    void* ws;
+    size_t ws_bytes;
+} psvi_mfvi_fit_req;
+int psvi_mfvi_fit(const psvi_mfvi_fit_req* req, void* stream);
+int psvi_mfvi_fit_query(const psvi_net_desc* desc, int64_t* out);
+
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's
  * objective, KL included) at fixed eps, world == 1:
