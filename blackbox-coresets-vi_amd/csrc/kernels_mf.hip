@@ -198,33 +198,62 @@ __global__ __launch_bounds__(256) void mf_update_kernel(MfUpdArgs a) {
 // Given the adjoints lt, lm, lv of (p', m', v') and the step's m', v', g:
 //   lg <- adjoint of g;  lm <- adjoint of m;  lv <- adjoint of v
 // (p's adjoint is lt + H^T lg: psvi_hvp).
+// The arithmetic is double, constants included.  lg is the difference of two
+// nearly equal terms wherever the step barely depends on g's size (a fresh
+// state: m' ~ g, v' ~ g^2, so m'/sqrt(v') ~ sign g; step 1 of every reverse
+// pass cancels to ~1e-5 of either term), and fp32 rounding of the terms, or of
+// 1 - beta, then costs lg up to 1e-2 of its value.  The kernel stays bound by
+// its seven fp32 streams.
+struct AdamAdjC {
+    double lr, b1, b2, eps, omb1, omb2;
+    double inv_bc1, inv_sqrt_bc2, inv_bc2;  // 1/(1-b1^t), 1/sqrt(1-b2^t), 1/(1-b2^t)
+    int kind;
+};
+
+static AdamAdjC make_adam_adjoint(const psvi_adam_hp* hp) {
+    AdamAdjC a{};
+    a.lr = decimal_of(hp->lr);
+    a.b1 = decimal_of(hp->beta1);
+    a.b2 = decimal_of(hp->beta2);
+    a.eps = decimal_of(hp->eps);
+    a.omb1 = 1.0 - a.b1;
+    a.omb2 = 1.0 - a.b2;
+    const double bc2 = 1.0 - std::pow(a.b2, (double)hp->step);
+    a.inv_bc1 = 1.0 / (1.0 - std::pow(a.b1, (double)hp->step));
+    a.inv_sqrt_bc2 = 1.0 / std::sqrt(bc2);
+    a.inv_bc2 = 1.0 / bc2;
+    a.kind = hp->kind;
+    return a;
+}
+
 __global__ __launch_bounds__(256) void adam_adjoint_kernel(int64_t n, const float* lt, float* lm,
                                                            float* lv, const float* m,
                                                            const float* v, const float* g,
-                                                           float* lg, AdamC a) {
+                                                           float* lg, AdamAdjC a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float mm = m[i], vv = v[i], t = lt[i];
-    float dm, dv;
+    const double mm = m[i], vv = v[i], t = lt[i];
+    double dm, dv;
     if (a.kind == PSVI_ADAM_HIGHER) {
-        const float sq = sqrtf(vv + 1e-8f), D = sq * a.inv_sqrt_bc2 + a.eps;
-        dm = -t * a.lr_bc1 / D;
-        dv = t * a.lr_bc1 * mm / (D * D) * (0.5f * a.inv_sqrt_bc2 / sq);
-    } else {
-        const float q = sqrtf(vv * a.inv_bc2), D = q + a.eps;
+        const double sq = sqrt(vv + 1e-8), D = sq * a.inv_sqrt_bc2 + a.eps;
         dm = -t * a.lr * a.inv_bc1 / D;
-        dv = t * a.lr * mm * a.inv_bc1 / (D * D) * (0.5f * a.inv_bc2 / fmaxf(q, 1e-30f));
+        dv = t * a.lr * a.inv_bc1 * mm / (D * D) * (0.5 * a.inv_sqrt_bc2 / sq);
+    } else {
+        const double q = sqrt(vv * a.inv_bc2), D = q + a.eps;
+        dm = -t * a.lr * a.inv_bc1 / D;
+        dv = t * a.lr * mm * a.inv_bc1 / (D * D) * (0.5 * a.inv_bc2 / fmax(q, 1e-30));
     }
-    const float lm2 = lm[i] + dm, lv2 = lv[i] + dv;
-    lg[i] = lm2 * a.omb1 + lv2 * 2.f * a.omb2 * g[i];
-    lm[i] = a.b1 * lm2;
-    lv[i] = a.b2 * lv2;
+    const double lm2 = lm[i] + dm, lv2 = lv[i] + dv;
+    lg[i] = (float)(lm2 * a.omb1 + lv2 * 2.0 * a.omb2 * (double)g[i]);
+    lm[i] = (float)(a.b1 * lm2);
+    lv[i] = (float)(a.b2 * lv2);
 }
 
 hipError_t launch_adam_adjoint(int64_t n, const float* lt, float* lm, float* lv, const float* m,
                                const float* v, const float* g, float* lg,
                                const psvi_adam_hp* hp, hipStream_t st) {
-    const AdamC a = make_adam(hp);
+    if (n <= 0) return hipSuccess;
+    const AdamAdjC a = make_adam_adjoint(hp);
     hipLaunchKernelGGL(adam_adjoint_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
                        lt, lm, lv, m, v, g, lg, a);
     return hipGetLastError();

@@ -813,7 +813,7 @@ class PSVI:
                 wp = self.N * torch.exp(a) * torch.softmax(v, 0)
             else:
                 wp = self.N * self.f(v, 0)
-            gs = torch.autograd.grad(wp, hp, grad_outputs=dw.to(wp.dtype).reshape(wp.shape))
+            gs = torch.autograd.grad(wp, hp, grad_outputs=dw.to(wp).reshape(wp.shape))
         return gs[0], (gs[1] if alpha is not None else None)
 
     @staticmethod

@@ -809,7 +809,9 @@ int psvi_hvp_ex(const psvi_plan* plan, const float* u, const int32_t* z, const f
  * (p', adam_m, adam_v) with Adam step hp->step; given lt = adjoint of p' and
  * lm / lv = adjoints of (adam_m, adam_v) (in/out: replaced by the adjoints of
  * the step's incoming m, v), writes lg_out = adjoint of grad.  The adjoint of
- * p is lt + H^T lg_out (psvi_hvp at p). */
+ * p is lt + H^T lg_out (psvi_hvp at p).  Evaluated in double from the fp32
+ * buffers: lg_out's two terms cancel almost fully on a fresh Adam state.
+ * n = 0 is a no-op that returns 0. */
 int psvi_adam_adjoint(int64_t n, const float* lt, float* lm, float* lv, const float* adam_m,
                       const float* adam_v, const float* grad, float* lg_out,
                       const psvi_adam_hp* hp, void* stream);

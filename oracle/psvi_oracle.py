@@ -838,6 +838,24 @@ def adam_higher_adjoint(lt, lm, lv, m, v, g, t, lr, beta1=0.9, beta2=0.999, eps=
     return lg, beta1 * lm2, beta2 * lv2
 
 
+def adam_hypergrad_adjoint(lt, lm, lv, m, v, g, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Reverse of one hypergrad adam_step (diff_optimizers.py:184-213)
+        m' = b1 m + (1-b1) g,  v' = b2 v + (1-b2) g^2 + 1e-12,
+        p' = p - lr (m'/bc1) / (sqrt(v'/bc2) + eps):
+    same arguments and returns as adam_higher_adjoint, m and v being the
+    stored m', v' (the 1e-12 included)."""
+    bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
+    q = np.sqrt(v / bc2)
+    D = q + eps
+    lm2 = lm - lt * lr / (bc1 * D)
+    lv2 = lv + lt * lr * (m / bc1) / (D * D) * 0.5 / (bc2 * q)
+    lg = lm2 * (1.0 - beta1) + lv2 * 2.0 * (1.0 - beta2) * g
+    return lg, beta1 * lm2, beta2 * lv2
+
+
+def adam_adjoint(kind, *a, **k):
+    return (adam_higher_adjoint if kind == "higher" else adam_hypergrad_adjoint)(*a, **k)
+
 
 def nested_step(family, layers, params0, u, z, v, N, xb, yb, eps_inner, eps_outer, S, T,
                 lr0net, lr0u, lr0v, prior_sd=1.0, variant=None):

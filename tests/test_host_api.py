@@ -267,7 +267,7 @@ def test_chain_w_gives_v_and_alpha_gradients():
     gv, ga = ps._chain_w(dw)
     v = ps.v.detach().double().requires_grad_(True)
     a = ps.alpha.detach().double().requires_grad_(True)
-    (100 * torch.exp(a) * torch.softmax(v, 0) * dw).sum().backward()
+    (100 * torch.exp(a) * torch.softmax(v, 0) * dw.to(v.device)).sum().backward()
     assert torch.allclose(gv.double(), v.grad, rtol=1e-5)
     assert torch.allclose(ga.double(), a.grad, rtol=1e-5)
     ps2 = _variant("PSVILearnV")
