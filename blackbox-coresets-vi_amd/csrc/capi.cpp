@@ -1439,6 +1439,30 @@ int psvi_giga_step(const psvi_giga_step_req* q, void* stream) {
     return 0;
 }
 
+int psvi_coreset_draw(const psvi_coreset_draw_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    if (!q->w || !q->idx_out || !q->status_out) return fail(PSVI_EINVAL, "null pointer");
+    if (q->mode != PSVI_DRAW_REPLACE && q->mode != PSVI_DRAW_NOREPLACE)
+        return fail(PSVI_EINVAL, "mode is PSVI_DRAW_REPLACE or PSVI_DRAW_NOREPLACE");
+    if (q->offset % 4) return fail(PSVI_EINVAL, "draw offset must be a multiple of 4");
+    if (q->M < 1 || q->n < 1 || q->n > kDrawMaxN || q->D < 0)
+        return fail(PSVI_EINVAL, "the coreset draw supports M >= 1, 1 <= n <= 2^24, D >= 0");
+    if ((q->rows && !q->rows_out) || (q->targets && !q->targets_out))
+        return fail(PSVI_EINVAL, "rows / targets given without their output");
+    if (q->M > kDrawMaxM)
+        return fail(PSVI_EUNSUP, "the coreset draw holds its weights in LDS: M <= 4096");
+    if (q->mode == PSVI_DRAW_NOREPLACE && q->n > q->M)
+        return fail(PSVI_EINVAL, "a draw without replacement takes n <= M");
+    CoresetDraw r;
+    r.w = q->w; r.M = q->M; r.n = q->n; r.replace = q->mode == PSVI_DRAW_REPLACE;
+    r.seed = q->seed; r.offset = q->offset;
+    r.rows = q->rows; r.D = q->D; r.targets = q->targets;
+    r.idx_out = q->idx_out; r.rows_out = q->rows_out; r.targets_out = q->targets_out;
+    r.status_out = q->status_out;
+    HIP_TRY(launch_coreset_draw(r, as_stream(stream)));
+    return 0;
+}
+
 int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,

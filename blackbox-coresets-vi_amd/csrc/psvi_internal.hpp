@@ -897,6 +897,25 @@ struct GigaStep {
     double* result = nullptr;       // [8]
 };
 hipError_t launch_giga_step(const GigaStep& r, hipStream_t st);
+// coreset rows drawn in proportion to their weights (kernels_draw.hip), with
+// the gather of the drawn rows and targets
+constexpr int kDrawMaxM = 4096;       // the fp64 prefix / the sort's keys live in LDS
+constexpr int64_t kDrawMaxN = 1 << 24;
+struct CoresetDraw {
+    const float* w = nullptr;  // [M]
+    int M = 0;
+    int64_t n = 0;
+    bool replace = true;
+    uint64_t seed = 0, offset = 0;
+    const float* rows = nullptr;    // [M][D], nullable
+    int64_t D = 0;
+    const void* targets = nullptr;  // [M] 4-byte slots, nullable
+    int32_t* idx_out = nullptr;     // [n]
+    float* rows_out = nullptr;      // [n][D]
+    void* targets_out = nullptr;    // [n]
+    int32_t* status_out = nullptr;  // [1]
+};
+hipError_t launch_coreset_draw(const CoresetDraw& r, hipStream_t st);
 // MFVI regressor fit (kernels_mfvi_fit.hip): T chained steps of a mean-field
 // Gaussian-likelihood MLP on a fixed batch for G members, one workgroup each.
 constexpr int kMfFitThreads = 512;

@@ -70,7 +70,16 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
                                        and method_args.get("compute_weights_entropy", True))
             sizes = (method_args["coreset_sizes"]
                      if nm_alg.startswith(("psvi", "opsvi", "mfvi_subset")) else [-1])
-            extra = shard if nm_alg.startswith("psvi") else {}
+            extra = dict(shard) if nm_alg.startswith("psvi") else {}
+            if nm_alg.startswith("psvi"):
+                # flow_psvi.py's continual-learning arguments; absent: off, as before
+                extra.update({k: method_args.get(k, False)
+                              for k in ("prune", "increment", "reset", "retrain_on_coreset")})
+                extra.update({k: method_args.get(k)
+                              for k in ("prune_interval", "prune_sizes", "increment_interval",
+                                        "increment_sizes")})
+                extra.update(reset_interval=method_args.get("reset_interval", 10),
+                             lr0joint=method_args.get("lr0joint", 1e-3))
             for t in range(method_args["num_trials"]):
                 for ps in sizes:
                     results[dnm][nm_alg][ps][t] = inf_dict[nm_alg](

@@ -72,6 +72,16 @@ with ``learn_z`` raises NotImplementedError as the reference does
 (psvi_classes.py:619-620).  With samples sharded over ranks (world > 1) the
 soft-label outer objective runs on ``ShardedOuter`` (``HipOuterRowsELBO``).
 
+  * run_psvi's continual-learning switches (psvi_classes.py:118-125, 823-832,
+    928-1003, 1110-1128, 1177-1217): ``reset`` (weight_reset every
+    reset_interval steps), ``prune`` (prune_coreset + weight_reset every
+    prune_interval steps, the fixed-u classes), ``increment`` (a new class, a
+    larger coreset and the next task's data every increment_interval steps)
+    and ``retrain_on_coreset`` (retrain: the network refitted on the coreset
+    alone, fused psvi_inner_loop chunks).  Where the reference draws coreset
+    rows with torch.multinomial, ``psvi_coreset_draw`` draws them on this
+    instance's Philox stream.  World 1, the classifiers only.
+
 There is no CPU fallback: a missing libpsvi_hip.so or GPU raises.
 """
 import contextlib
@@ -254,9 +264,31 @@ class PSVI:
                  mc_samples=None, learn_v=False, f=lambda *x: x[0], distr_fn=categorical_fn,
                  nc=None, register_elbos=True, inner_it=10, log_every=10, lr0net=1e-3,
                  device_id=None, learn_z=False, compute_weights_entropy=True, world=1, rank=0,
-                 comm=None, **kwargs):
+                 comm=None, prune=False, prune_interval=None, prune_sizes=None, increment=False,
+                 increment_interval=None, increment_sizes=None, reset=False, reset_interval=10,
+                 retrain_on_coreset=False, **kwargs):
         if distr_fn is not categorical_fn:
             raise NotImplementedError("the HIP inner loop implements the categorical likelihood")
+        self.prune, self.prune_interval, self.prune_sizes = bool(prune), prune_interval, prune_sizes
+        self.increment, self.increment_interval = bool(increment), increment_interval
+        self.increment_sizes = increment_sizes
+        self.reset, self.reset_interval = bool(reset), reset_interval
+        self.retrain_on_coreset = bool(retrain_on_coreset)
+        switches = [k for k in ("prune", "increment", "reset", "retrain_on_coreset")
+                    if getattr(self, k)]
+        if switches and int(world) > 1:
+            raise NotImplementedError(f"{', '.join(switches)} with world > 1: pruning, increments, "
+                                      "resets and retraining run on one GPU")
+        if self.increment and learn_z:
+            raise NotImplementedError("increment with learn_z: the reference concatenates one-hot "
+                                      "label logits with scalar labels, which cannot work")
+        for k in ("prune", "increment", "reset"):
+            sizes = getattr(self, k + "_sizes", True)
+            if getattr(self, k) and (not getattr(self, k + "_interval") or not sizes):
+                raise ValueError(f"{k}=True needs {k}_interval"
+                                 + ("" if k == "reset" else f" and {k}_sizes"))
+        if self.increment:
+            num_pseudo = increment_sizes[0]     # psvi_classes.py:170
         torch.manual_seed(seed)
         # as the reference: cuda when present (the HIP path then refuses anything else)
         self.device = torch.device(f"cuda:{device_id}" if device_id is not None else
@@ -265,11 +297,8 @@ class PSVI:
         self.train_dataset = kwargs.get("train_dataset")
         self.test_dataset = kwargs.get("test_dataset")
         self.init_dataset = kwargs.get("init_dataset")
-        for k in ("prune", "increment", "retrain_on_coreset", "reset"):
-            if kwargs.get(k):
-                raise NotImplementedError(f"{k}=True (coreset pruning / incremental learning / "
-                                          "retraining / resets) is not on the HIP path")
         self.chosen_indices = []
+        self.draw_log = []   # (kind, outer step, drawn coreset indices) of every prune / increment
         self.model = model
         self.num_pseudo = num_pseudo if num_pseudo is not None else (
             u.shape[0] if u is not None else None)
@@ -1247,6 +1276,179 @@ class PSVI:
             self.z = torch.nn.functional.one_hot(self.z.long(), num_classes=self.nc).float()
             self.z.requires_grad_(True)
 
+    # ------------------------------ resets, pruning, increments, retraining
+    def _drop_plans(self, resident_only=False):
+        """Forget what the plans hold of a network or a coreset that is gone:
+        a resident inner-loop state (the network was re-initialised), or the
+        plans themselves (M or the class count changed: they are keyed by
+        shape, so the next call builds new ones)."""
+        for plan in self._plans.values():
+            if hasattr(plan, "_resident"):
+                plan._resident = None
+        if not resident_only:
+            self._plans = {}
+            self._labels_ok = None
+
+    def weight_reset(self):
+        """psvi_classes.py:1110-1128: every VI layer back to its initialisation
+        (reset_parameters_variational: nn.Linear's draw of the means from the
+        host generator, the standard deviations at init_sd).  As in the
+        reference a full-covariance layer refuses (NotImplementedError)."""
+        for layer in self.model.modules():
+            if hasattr(layer, "reset_parameters_variational"):
+                layer.reset_parameters_variational()
+        self._drop_plans(resident_only=True)
+
+    def _coreset_draw(self, n, replacement):
+        """n coreset rows drawn in proportion to f(v) on this instance's Philox
+        stream (psvi_coreset_draw), where the reference calls
+        torch.multinomial: (idx, u[idx], z[idx]); the stream moves on by the
+        consumed length."""
+        from ..runtime import coreset_draw
+
+        if self.world > 1:
+            raise NotImplementedError("coreset draws run on one GPU (world 1)")
+        with torch.no_grad():
+            w = self.f(self.v, 0).detach().to(self.device, torch.float32).reshape(-1).contiguous()
+        M = int(w.numel())
+        u = self.u.detach().to(self.device, torch.float32).reshape(M, -1).contiguous()
+        z = self.z.detach().to(self.device).reshape(-1)
+        zt = z if z.dtype in (torch.int32, torch.float32) else z.to(torch.float32)
+        idx, rows, targets, used = coreset_draw(w, n, replacement, self.seed, self._eps_offset,
+                                                rows=u, targets=zt.contiguous())
+        self._eps_offset += used
+        return idx, rows.reshape(n, *self.u.shape[1:]).to(self.u.dtype), targets.to(z.dtype)
+
+    def prune_coreset(self, to_size, lr0v=1e-3, lr0net=1e-4):
+        """psvi_classes.py:1177-1192: keep to_size pseudopoints drawn without
+        replacement in proportion to f(v); v restarts at zeros, optim_v and
+        optim_net are rebuilt.  The reference marks it 'only for the fixed u
+        methods' (its optim_u keeps pointing at the old u): served for the
+        classes that do not learn u."""
+        if self._learn_u:
+            raise NotImplementedError(f"{type(self).__name__} learns u: pruning serves the fixed-u "
+                                      "classes PSVIFixedU / PSVIAFixedU (psvi_classes.py:1181)")
+        keep, u, z = self._coreset_draw(int(to_size), replacement=False)
+        self.draw_log.append(("prune", getattr(self, "_outer_it", None), keep.cpu()))
+        self.num_pseudo = int(to_size)
+        self.v = torch.zeros(self.num_pseudo, dtype=self.v.dtype,
+                             device=self.v.device).requires_grad_(True)
+        self.optim_v = torch.optim.Adam([self.v], lr0v)
+        self.u, self.z = u, z
+        self.optim_net = torch.optim.Adam(list(self.model.parameters()), lr0net)
+        self._drop_plans()
+
+    def increment_coreset(self, to_size, lr0v=1e-3, lr0u=1e-3, lr0net=1e-4, variance=1.,
+                          new_class=2, increment_idx=1):
+        """psvi_classes.py:1194-1217: grow the coreset to to_size for a new
+        class.  Each new point weighs sum(v) / to_size; the new rows are the
+        noisy empirical mean of the current training set labelled new_class
+        (init_args 'random') or a random subset of the new task's dataset
+        ('subsample'), drawn from the host generator as in pseudo_*_init;
+        optim_v, optim_u and optim_net are rebuilt."""
+        extra = int(to_size) - int(self.v.numel())
+        if extra < 0:
+            raise ValueError(f"increment_coreset to {to_size} < {self.v.numel()} pseudopoints")
+        self.num_pseudo = int(to_size)
+        with torch.no_grad():
+            ones = torch.ones(extra, device=self.v.device, dtype=self.v.dtype)
+            self.v = torch.cat((self.v, 1. / (self.v.numel() + extra) * self.v.sum() * ones))
+        self.v = self.v.detach().requires_grad_(True)
+        self.optim_v = torch.optim.Adam([self.v], lr0v)
+        if self.init_args == "random":
+            x, _ = self._xy(self.train_loader.dataset)
+            mean = x.reshape(x.shape[0], -1).mean(0)
+            new_us = mean + variance * torch.randn(extra, self.D)
+            new_zs = new_class * torch.ones(extra)
+        else:
+            x, y = self._xy(self.incremental_train_datasets[increment_idx])
+            pick = torch.randperm(x.shape[0])[:extra]
+            new_us, new_zs = x[pick].reshape(extra, -1), y[pick]
+        u0 = self.u.detach()
+        self.u = torch.cat((u0, new_us.to(u0).reshape(extra, *u0.shape[1:])))
+        self.u = self.u.detach().requires_grad_(True)
+        self.z = torch.cat((self.z.detach(), new_zs.to(self.z)))
+        self.optim_u = torch.optim.Adam([self.u], lr0u)
+        self.optim_net = torch.optim.Adam(list(self.model.parameters()), lr0net)
+        self._drop_plans()
+
+    def retrain(self, num_steps=None, lr=1e-3, log=None):
+        """psvi_classes.py:968-1003: re-initialise the network and fit it to
+        the coreset alone: num_steps steps of the inner objective under
+        torch.optim.Adam (fresh state, learning rate lr).  The steps between
+        two evaluations run fused on the Philox stream, one
+        psvi_inner_loop per chunk of log_every steps (PSVI_ADAM_TORCH
+        arithmetic, the step count and the Adam state carried over); ``log``
+        is called before each chunk with the parameters written into the
+        model (run_psvi: evaluate(correction=False))."""
+        T = self.num_epochs if num_steps is None else int(num_steps)
+        self.weight_reset()
+        model = self.model
+        plan = self._plan(model)
+        u, z, w = self._data(plan)
+        plist = list(model.parameters())
+        with torch.no_grad():
+            params = nn.utils.parameters_to_vector(plist).detach().to(torch.float32).clone()
+        m, v2 = torch.zeros_like(params), torch.zeros_like(params)
+        ws = torch.empty(plan.loop_ws_bytes, dtype=torch.uint8, device=params.device)
+        chunk = max(int(self.log_every), 1)
+        for t0 in range(0, T, chunk):
+            if log is not None:
+                log(t0)
+            n = min(chunk, T - t0)
+            plan.inner_loop(u, z, w, params, m, v2, n, lr, kind="torch", step0=t0 + 1,
+                            seed=self.seed, offset=self._eps_offset, ws=ws)
+            self._eps_offset += n * plan.eps_stride
+            with torch.no_grad():
+                nn.utils.vector_to_parameters(params.to(plist[0].dtype), plist)
+        self._anomaly_check("retrain", params)
+
+    def _incremental_setup(self):
+        """psvi_classes.py:823-832: one training set per task (classes 0 and 1,
+        then one new class at a time), test sets over the classes so far; the
+        run starts as a 2-class problem."""
+        from torch.utils.data import DataLoader
+
+        for ds in (self.train_dataset, self.test_dataset):
+            if not hasattr(ds, "subset_where") or not hasattr(ds, "concatenate"):
+                raise NotImplementedError("increment=True needs datasets with subset_where / "
+                                          "concatenate (psvi.experiments.SynthDataset)")
+        tasks = range(1, self.nc)
+        self.incremental_train_datasets = [
+            self.train_dataset.subset_where(cs=list(range(c + 1)) if c == 1 else [c])
+            for c in tasks]
+        self.incremental_test_datasets = [
+            self.test_dataset.subset_where(cs=list(range(c + 1))) for c in tasks]
+        self.train_loader = DataLoader(self.incremental_train_datasets[0],
+                                       batch_size=self.data_minibatch, shuffle=True)
+        self.test_loader = DataLoader(self.incremental_test_datasets[0],
+                                      batch_size=self.data_minibatch, shuffle=False)
+        self.train_data_so_far = len(self.train_loader.dataset)
+        self.nc = 2
+
+    def _increment_task(self, increment_idx, lr0v, lr0u, lr0net):
+        """psvi_classes.py:946-965: summarise the tasks so far by
+        train_data_so_far rows drawn with replacement from the coreset in
+        proportion to f(v), add a class, rebuild the network, grow the coreset
+        and train on the new task's data plus the summary."""
+        from torch.utils.data import DataLoader
+
+        idx, rows, targets = self._coreset_draw(self.train_data_so_far, replacement=True)
+        self.draw_log.append(("increment", getattr(self, "_outer_it", None), idx.cpu()))
+        self.nc += 1
+        self.set_up_model()
+        self.increment_coreset(to_size=self.increment_sizes[increment_idx], lr0v=lr0v, lr0u=lr0u,
+                               lr0net=lr0net, new_class=increment_idx + 1,
+                               increment_idx=increment_idx)
+        task = self.incremental_train_datasets[increment_idx]
+        tx, ty = torch.as_tensor(task.data), torch.as_tensor(task.targets)
+        grown = task.concatenate(rows.detach().cpu().to(tx.dtype).reshape(-1, *tx.shape[1:]),
+                                 targets.detach().cpu().to(ty.dtype))
+        self.train_loader = DataLoader(grown, batch_size=self.data_minibatch, shuffle=True)
+        self.test_loader = DataLoader(self.incremental_test_datasets[increment_idx],
+                                      batch_size=self.data_minibatch, shuffle=False)
+        self.train_data_so_far = len(grown)
+
     def run_psvi(self, init_args="subsample", trainer="nested", n_layers=1,
                  logistic_regression=True, n_hidden=None, architecture=None, log_every=10,
                  inner_it=10, data_minibatch=None, lr0net=1e-3, lr0u=1e-3, lr0joint=1e-3,
@@ -1269,11 +1471,16 @@ class PSVI:
         self.log_every, self.log_pseudodata = log_every, log_pseudodata
         self.data_minibatch, self.inner_it, self.num_epochs = data_minibatch, inner_it, num_epochs
         self.gamma = gamma
+        if self.prune and self._learn_u:
+            raise NotImplementedError(f"{type(self).__name__} learns u: pruning serves the fixed-u "
+                                      "classes PSVIFixedU / PSVIAFixedU (psvi_classes.py:1181)")
         epoch_quarter = (self.N // self.data_minibatch) // 4
         self.train_loader = DataLoader(self.train_dataset, batch_size=self.data_minibatch,
                                        shuffle=True)
         self.test_loader = DataLoader(self.test_dataset, batch_size=self.data_minibatch,
                                       shuffle=False)
+        if self.increment:
+            self._incremental_setup()
         self.set_up_model()
         (self.pseudo_subsample_init if init_args == "subsample" else self.pseudo_rand_init)()
         self.setup_optimizers(lr0net=lr0net, lr0u=lr0u, lr0v=lr0v, lr0joint=lr0joint,
@@ -1290,29 +1497,51 @@ class PSVI:
             [], [], [], [], [], [], [], [], [], [], [0]
         t_start = time.time()
         lpit = list(range(num_epochs))[::log_every]
+
+        def log_eval(it, retraining=False):
+            kw = dict(correction=False) if retraining else {}
+            acc, nll, iw_ent, ness, v_ent = self.evaluate(**kw)
+            if log_pseudodata and it in lpit and self.D == 2:
+                grid.append(self.pred_on_grid(**kw).detach().cpu().numpy().T)
+            with torch.no_grad():
+                nlls.append(nll.item())
+                accs.append(acc.item())
+                csizes.append(self.num_pseudo)
+                times.append(times[-1] + time.time() - t_start)
+                vs.append((self.f(self.v, 0) if retraining else self.v).clone().cpu().detach()
+                          .numpy())
+                if iw_ent is not None:
+                    went.append(iw_ent.item())
+                if ness is not None:
+                    ness_l.append(ness.item())
+                if v_ent is not None:
+                    vent.append(v_ent.item())
+                if log_pseudodata:
+                    us.append(self.u.clone().cpu().detach().numpy())
+                    zs.append(self.z.clone().cpu().detach().numpy())
+
         for it in range(num_epochs):
+            self._outer_it = it
             xbatch, ybatch = next(iter(self.train_loader))
             xbatch, ybatch = xbatch.to(self.device), ybatch.to(self.device)
             if it % log_every == 0:
-                acc, nll, iw_ent, ness, v_ent = self.evaluate()
-                if log_pseudodata and it in lpit and self.D == 2:
-                    grid.append(self.pred_on_grid().detach().cpu().numpy().T)
-                with torch.no_grad():
-                    nlls.append(nll.item())
-                    accs.append(acc.item())
-                    csizes.append(self.num_pseudo)
-                    times.append(times[-1] + time.time() - t_start)
-                    vs.append(self.v.clone().cpu().detach().numpy())
-                    if iw_ent is not None:
-                        went.append(iw_ent.item())
-                    if ness is not None:
-                        ness_l.append(ness.item())
-                    if v_ent is not None:
-                        vent.append(v_ent.item())
-                    if log_pseudodata:
-                        us.append(self.u.clone().cpu().detach().numpy())
-                        zs.append(self.z.clone().cpu().detach().numpy())
+                log_eval(it)
+            if self.reset and it % self.reset_interval == 0:     # psvi_classes.py:928-930
+                self.weight_reset()
             psvi_step(xbatch, ybatch)
+            # psvi_classes.py:934-942: prune to the next budget, then a fresh network
+            if (self.prune and it > 0 and it % self.prune_interval == 0
+                    and prune_idx < len(self.prune_sizes)):
+                self.prune_coreset(to_size=self.prune_sizes[prune_idx], lr0v=lr0v, lr0net=lr0net)
+                prune_idx += 1
+                self.weight_reset()
+            # psvi_classes.py:944-965: a new class, a larger coreset, the next task's data
+            if (self.increment and it > 0 and it % self.increment_interval == 0
+                    and increment_idx < len(self.increment_sizes) - 1):
+                increment_idx += 1
+                self._increment_task(increment_idx, lr0v, lr0u, lr0net)
+        if self.retrain_on_coreset:                                # psvi_classes.py:968-1003
+            self.retrain(num_epochs, lr0joint, log=lambda it: log_eval(it, retraining=True))
         torch.cuda.synchronize()
         self.results.update(
             accs=accs, nlls=nlls, csizes=csizes, times=times[1:], elbos=self.elbos, went=went,
@@ -1421,6 +1650,11 @@ class PSVIAV(PSVILearnV):
         self.results.setdefault("alpha", []).append(self.alpha.clone().cpu().detach().numpy())
         return super().evaluate(**kwargs)
 
+    def increment_coreset(self, lr0alpha=1e-3, **kwargs):
+        """psvi_classes.py:1501-1503: alpha's Adam restarts with the coreset's."""
+        super().increment_coreset(**kwargs)
+        self.optim_alpha = torch.optim.Adam([self.alpha], lr0alpha)
+
 
 class PSVIFixedU(PSVILearnV):
     """Fixed pseudopoint locations (psvi_classes.py:1622-1740): u is frozen
@@ -1526,6 +1760,11 @@ class PSVI_regressor(PSVI):
                  logistic_regression=False, world=1, **kwargs):
         if int(world) > 1:
             raise NotImplementedError("the regressors run on one GPU (Gaussian plans: world 1)")
+        for k in ("prune", "increment", "reset", "retrain_on_coreset"):
+            if kwargs.get(k):
+                raise NotImplementedError(f"{k}=True: the regressors' run_psvi has no pruning, "
+                                          "increments, resets or retraining "
+                                          "(psvi_classes.py:2095-2218)")
         if not float(tau) > 0:
             raise ValueError("tau must be positive")
         super().__init__(u=u, z=z, N=N, D=D, num_pseudo=num_pseudo, seed=seed,

@@ -137,6 +137,24 @@ class GigaStepReq(ctypes.Structure):
     ]
 
 
+DRAW_REPLACE = 0
+DRAW_NOREPLACE = 1
+DRAW_MAX_M = 4096
+DRAW_MAX_N = 1 << 24
+
+
+class CoresetDrawReq(ctypes.Structure):
+    _fields_ = [
+        ("w", ctypes.c_void_p),
+        ("M", ctypes.c_int32), ("n", ctypes.c_int32), ("mode", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+        ("rows", ctypes.c_void_p), ("D", ctypes.c_int32),
+        ("targets", ctypes.c_void_p),
+        ("idx_out", ctypes.c_void_p), ("rows_out", ctypes.c_void_p),
+        ("targets_out", ctypes.c_void_p), ("status_out", ctypes.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -197,6 +215,7 @@ SIGNATURES = {
     "psvi_laplace_sample_full": (_I32, [ctypes.POINTER(LaplaceSampleFullReq), _P]),
     "psvi_laplace_scores": (_I32, [ctypes.POINTER(LaplaceScoresReq), _P]),
     "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),
+    "psvi_coreset_draw": (_I32, [ctypes.POINTER(CoresetDrawReq), _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -932,6 +932,55 @@ def giga_step(samples, rows, labels, lw, want_ll=False):
     return out
 
 
+DRAW_STATUS = {1: "a weight is negative or not finite", 2: "the weights sum to zero",
+               3: "fewer positive weights than rows to draw without replacement"}
+
+
+def coreset_draw(w, n, replacement, seed, offset, rows=None, targets=None):
+    """n coreset indices drawn in proportion to the weights w (M floats) on the
+    Philox stream (seed, offset) (psvi_coreset_draw): independently
+    (replacement=True, inverse CDF) or n distinct ones in the order they are
+    drawn (replacement=False, Efraimidis-Spirakis keys).  rows (M, D float32) /
+    targets (M, int32 or float32) are gathered by the indices on the device.
+    Returns (idx int32 (n), rows_out or None, targets_out or None, consumed):
+    consumed is the length of the stream the draw used, 4 ceil(n / 4) with and
+    4 ceil(M / 4) without replacement -- add it to offset for the next draw.
+    Reads the status word once on the host; raises ValueError naming the
+    condition when the weights admit no such draw."""
+    if w is None or w.dim() != 1:
+        raise ValueError("w must be a vector of M weights")
+    M, n = int(w.numel()), int(n)
+    _need(w, "w", M)
+    if M < 1 or n < 1 or n > _lib.DRAW_MAX_N:
+        raise ValueError(f"coreset_draw: M >= 1 and 1 <= n <= 2^24 (got M = {M}, n = {n})")
+    if not replacement and n > M:
+        raise ValueError(f"cannot draw {n} distinct rows out of {M}")
+    dev = w.device
+    D, rows_out, targets_out = 0, None, None
+    if rows is not None:
+        if rows.dim() != 2 or int(rows.shape[0]) != M:
+            raise ValueError(f"rows must be ({M}, D)")
+        D = int(rows.shape[1])
+        _need(rows, "rows", M * D)
+        rows_out = torch.empty(n, D, dtype=torch.float32, device=dev)
+    if targets is not None:
+        if targets.dtype not in (torch.int32, torch.float32):
+            raise ValueError("targets must be int32 or float32 (4-byte slots)")
+        _need(targets, "targets", M, targets.dtype)
+        targets_out = torch.empty(n, dtype=targets.dtype, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    req = _lib.CoresetDrawReq(
+        _ptr(w), M, n, _lib.DRAW_REPLACE if replacement else _lib.DRAW_NOREPLACE,
+        int(seed) & (2**64 - 1), int(offset), _ptr(rows) if D > 0 else None, D, _ptr(targets),
+        _ptr(idx), _ptr(rows_out) if D > 0 else None, _ptr(targets_out), _ptr(status))
+    check(_lib.load().psvi_coreset_draw(ctypes.byref(req), _stream()), "psvi_coreset_draw")
+    st = int(status.item())
+    if st:
+        raise ValueError(f"coreset_draw: {DRAW_STATUS.get(st, f'status {st}')}")
+    return idx, rows_out, targets_out, 4 * (((n if replacement else M) + 3) // 4)
+
+
 def randn_(out, seed, offset=0):
     """Fill a float32 device tensor with N(0,1) (Philox4x32-10 + Box-Muller)."""
     _need(out, "out", None)

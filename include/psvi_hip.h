@@ -692,6 +692,60 @@ typedef struct psvi_giga_step_req {
 } psvi_giga_step_req;
 int psvi_giga_step(const psvi_giga_step_req* req, void* stream);
 
+/* ---- coreset draws (PSVI.prune_coreset / the incremental-learning schedule) --
+ * n indices of coreset rows drawn in proportion to the weights w (M floats,
+ * f(v) of the PSVI classes), where the reference calls torch.multinomial
+ * (psvi_classes.py:946-965, 1177-1192) -- on the library's own Philox stream,
+ * so that a run stays a function of its seed, a CPU restatement predicts the
+ * draw and every rank of a multi-GPU run draws the same rows.
+ * Word j of the stream (seed, offset), offset a multiple of 4, is element
+ * j % 4 of Philox4x32-10 at counter offset / 4 + j / 4 with key seed: the
+ * indexing of psvi_randn.  Its uniform is U_j = (word_j + 0.5) 2^-32, exact in
+ * fp64 and strictly inside (0, 1).  Both modes decide in fp64.
+ * PSVI_DRAW_REPLACE (independent draws):  C_i = the inclusive fp64 prefix sum
+ *   of w in index order; draw j takes t = U_j C_{M-1} and returns the smallest
+ *   i with C_i > t, clamped to the last index with w_i > 0 -- a row of zero
+ *   weight is never returned.  The prefix is summed in runs of consecutive
+ *   weights whose totals are added in run order: a fixed association, the same
+ *   in every launch, that differs from a strictly sequential sum by fp64
+ *   rounding only (not at all when the sums are exact).
+ *   Consumes 4 ceil(n / 4) words of the stream.
+ * PSVI_DRAW_NOREPLACE (n distinct rows; Efraimidis-Spirakis sampling, the law
+ *   of drawing one row at a time in proportion to the remaining weights, as
+ *   torch.multinomial(replacement=False)):  key_i = log(U_i) / w_i for
+ *   w_i > 0, -inf for w_i == 0; the n largest keys win and come out in
+ *   descending key order.  Equal keys are ordered by the lower index first
+ *   (with equal weights two equal 32-bit words make a tie).
+ *   Consumes 4 ceil(M / 4) words of the stream, whatever n.
+ * Optional gather: rows ([M][D] floats) -> rows_out ([n][D]) and targets (M
+ * 4-byte slots: int32 labels or fp32 values, copied as bits) -> targets_out
+ * (n), both by idx_out.
+ * status_out (one device int32): 0 ok; 1 a weight is negative or not finite;
+ * 2 the weights sum to zero; 3 NOREPLACE with fewer than n positive weights.
+ * On a non-zero status every idx_out entry is -1 and rows_out / targets_out are
+ * not written.  The call itself returns 0 then: the status is the caller's to
+ * read (one host read; a draw runs once per prune / increment, never per step).
+ * Refused without a launch: PSVI_EINVAL for a NULL w / idx_out / status_out,
+ * offset % 4 != 0, an unknown mode, M < 1, n < 1, n > 2^24, D < 0, rows /
+ * targets without their output, n > M under NOREPLACE; PSVI_EUNSUP for
+ * M > 4096 (the prefix and the sort's keys live in LDS).
+ * Bitwise reproducible: no atomics on anything that decides an index. */
+#define PSVI_DRAW_REPLACE   0
+#define PSVI_DRAW_NOREPLACE 1
+typedef struct psvi_coreset_draw_req {
+    const float* w;
+    int32_t M, n, mode;
+    uint64_t seed, offset;
+    const float* rows;      /* nullable */
+    int32_t D;
+    const void* targets;    /* nullable */
+    int32_t* idx_out;
+    float* rows_out;        /* required with rows */
+    void* targets_out;      /* required with targets */
+    int32_t* status_out;
+} psvi_coreset_draw_req;
+int psvi_coreset_draw(const psvi_coreset_draw_req* req, void* stream);
+
 /* ---- MFVI regression baselines (fit, run_mfvi_regressor) -------------------
  * The whole fit of a mean-field Gaussian-likelihood MLP on a FIXED batch (fit,
  * psvi/inference/baselines.py:1283-1346: every step takes next(iter(loader)) of
