@@ -117,6 +117,10 @@ int plan_to_device(psvi_plan& p) {
     if (p.family == PSVI_FAMILY_MEANFIELD &&
         !p.mf_slots.alloc(sizeof(float) * (size_t)std::max(1, p.s_cnt[p.rank]) * p.mchunks * p.n_tot))
         return fail(PSVI_EUNSUP, "cannot allocate the mean-field gradient slots");
+    // (psvi_plan_create_lik releases it again on a Gaussian or Bernoulli plan)
+    if (p.family == PSVI_FAMILY_MEANFIELD && p.world == 1 &&
+        !p.pred_scratch.alloc(predict_scratch_bytes(p.n_tot)))
+        return fail(PSVI_EUNSUP, "cannot allocate the predictive scores' scratch");
     if (fullcov && p.fuse_sample && p.tiles_total > 0 && !p.aux.create())
         return fail(PSVI_EUNSUP, "cannot create the inner loop's conversion stream");
     if (p.eps_planes_ok) {
@@ -304,6 +308,7 @@ int psvi_plan_create_lik(int32_t family, const psvi_net_desc* d, int32_t world, 
         return fail(PSVI_EINVAL, "the Gaussian precision tau must be positive and finite");
     if (int rc = psvi_plan_create(family, d, world, rank, out)) return rc;
     (*out)->lik = lik->kind;
+    (*out)->pred_scratch.release();  // psvi_predict_scores runs categorical plans only
     if (gauss) (*out)->lik_tau = lik->tau;
     return 0;
 }
@@ -1366,6 +1371,38 @@ int psvi_mfvi_fit(const psvi_mfvi_fit_req* q, void* stream) {
     r.lr = q->lr; r.beta1 = q->beta1; r.beta2 = q->beta2; r.adam_eps = q->adam_eps;
     r.loss_out = q->loss_out; r.ws = q->ws;
     HIP_TRY(launch_mfvi_fit(r, as_stream(stream)));
+    return 0;
+}
+
+int psvi_predict_scores(const psvi_predict_scores_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    const psvi_plan* p = q->plan;
+    if (!p) return fail(PSVI_EINVAL, "null plan");
+    if (p->family != PSVI_FAMILY_MEANFIELD || p->lik != PSVI_LIK_CATEGORICAL || p->world != 1)
+        return fail(PSVI_ESTATE, "the predictive scores need a mean-field categorical plan of world 1");
+    if (q->n_rows < 1 || q->rows_per_draw < 1)
+        return fail(PSVI_EINVAL, "n_rows and rows_per_draw must be >= 1");
+    if (!q->x || !q->eps || !q->params) return fail(PSVI_EINVAL, "null pointer");
+    const int n_state = (q->last_acc != nullptr) + (q->forgetting != nullptr) + (q->never_learnt != nullptr);
+    if (n_state != 0 && n_state != 3)
+        return fail(PSVI_EINVAL, "last_acc, forgetting and never_learnt are given together or not at all");
+    if (!q->mean_logits && !q->least_conf && !q->entropy && !q->el2n && !q->correct && !n_state &&
+        !q->stats_out)
+        return fail(PSVI_EINVAL, "no output requested");
+    if ((q->el2n || q->correct || n_state || q->stats_out) && !q->z)
+        return fail(PSVI_EINVAL, "el2n, correct, the forgetting state and stats_out need the labels z");
+    PredictScores r;
+    if (predict_shape(*p, q->rows_per_draw, r.shape) != 0)
+        return fail(PSVI_EUNSUP, "a layer of the network does not fit the predictive scores' LDS "
+                                 "budget: one unit's weights and one row's activations exceed 160 KiB");
+    if (!p->on_device) return fail(PSVI_ESTATE, "plan was created without a HIP device");
+    r.n_rows = q->n_rows; r.rpd = q->rows_per_draw;
+    r.x = q->x; r.z = q->z; r.eps = q->eps; r.params = q->params;
+    r.mean_logits = q->mean_logits; r.least_conf = q->least_conf; r.entropy = q->entropy;
+    r.el2n = q->el2n; r.correct = q->correct;
+    r.last_acc = q->last_acc; r.forgetting = q->forgetting; r.never_learnt = q->never_learnt;
+    r.stats_out = q->stats_out;
+    HIP_TRY(launch_predict_scores(*p, r, as_stream(stream)));
     return 0;
 }
 

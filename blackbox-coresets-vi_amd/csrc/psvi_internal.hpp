@@ -486,6 +486,10 @@ struct DevBuffer {
     ~DevBuffer() {
         if (dev) (void)hipFree(dev);
     }
+    void release() {
+        if (dev) (void)hipFree(dev);
+        dev = nullptr;
+    }
     bool alloc(size_t bytes, bool zero = false) {
         if (hipMalloc((void**)&dev, bytes) != hipSuccess) {
             dev = nullptr;
@@ -615,6 +619,9 @@ struct psvi_plan {
     // [s_cnt[rank]][mchunks][n_tot]; one writer per element, summed in a fixed
     // order by the update (run-to-run bitwise reproducible, no float atomics)
     psvi::DevBuffer<float> mf_slots;
+    // mean-field categorical, world 1: psvi_predict_scores's scratch (the
+    // workgroups' statistics partials, then softplus(rho); predict_scratch_bytes)
+    psvi::DevBuffer<void> pred_scratch;
     // full-cov with pseudopoint chunks: per-chunk dW slots [mchunks][s_cnt[rank]][n_tot],
     // added in chunk order into g_send (no float atomics)
     psvi::DevBuffer<float> net_slots;
@@ -953,6 +960,37 @@ struct MfviFit {
     void* ws = nullptr;             // G * shape.ws_bytes
 };
 hipError_t launch_mfvi_fit(const MfviFit& r, hipStream_t st);
+// predictive scores of the MFVI selection baselines (kernels_predict.hip): the
+// mean-logit forward of a mean-field categorical plan over n_rows rows, rows
+// [k rpd, (k + 1) rpd) on eps block k, and the scores read off its softmax
+constexpr int kPredThreads = 256;
+constexpr size_t kPredLds = 160 * 1024;
+constexpr int kPredMaxGrid = 2048;  // workgroups (and statistics partials) of a launch
+constexpr int kPredMaxRows = 64;    // rows of a group: its inputs, activations and logit sums in LDS
+// bytes of a plan's scratch: the partials, then softplus(rho) in weight-space order
+inline size_t predict_scratch_bytes(int n_tot) {
+    return sizeof(double) * 2 * kPredMaxGrid + sizeof(float) * (size_t)n_tot;
+}
+struct PredictShape {
+    int L = 0, S = 0, D = 0, C = 0, n_tot = 0, hs = 0, xs = 0;
+    int RG = 0;          // rows per group
+    int wcap = 0;        // floats of the W tile
+    int ut[kMaxL] = {};  // output units per tile of every layer
+    int64_t eps_count = 0;
+};
+// 0, or PSVI_EUNSUP when one unit's weights of some layer do not fit beside one row
+int predict_shape(const psvi_plan& p, int64_t rpd, PredictShape& s);
+struct PredictScores {
+    PredictShape shape;
+    int64_t n_rows = 0, rpd = 0;
+    const float *x = nullptr, *eps = nullptr, *params = nullptr;
+    const int32_t* z = nullptr;
+    float *mean_logits = nullptr, *least_conf = nullptr, *entropy = nullptr, *el2n = nullptr,
+          *correct = nullptr;
+    float *last_acc = nullptr, *forgetting = nullptr, *never_learnt = nullptr;
+    double* stats_out = nullptr;
+};
+hipError_t launch_predict_scores(const psvi_plan& p, const PredictScores& r, hipStream_t st);
 // outer objective (kernels_outer.hip)
 hipError_t launch_outer_stats(const psvi_plan& p, const float* params, const float* eps,
                               const float* x, double* stats, hipStream_t st);

@@ -6,5 +6,5 @@ from .experiments_utils import (SynthDataset, make_four_class_dataset, make_mnis
                                 split_data, write_to_files, read_regression_dataset,
                                 hyperparams_for_regression, update_hyperparams_dict,
                                 make_synth_regr)
-from .flow_psvi import (experiment_driver, inf_dict, regressor_experiment_driver,  # noqa: F401
-                        regressor_inf_dict)
+from .flow_psvi import (experiment_driver, extended_inf_dict, inf_dict,  # noqa: F401
+                        regressor_experiment_driver, regressor_inf_dict)

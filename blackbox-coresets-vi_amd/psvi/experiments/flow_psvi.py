@@ -1,6 +1,7 @@
 """flow_psvi.experiment_driver (psvi/experiments/flow_psvi.py:357-454) over the
-methods the HIP path runs: the PSVI variants' run_psvi, the MFVI baselines
-and the sparse black-box VI coreset construction.  No CLI: method_args is the reference's dict of parsed arguments.
+methods the HIP path runs: the PSVI variants' run_psvi, the MFVI baselines,
+the sparse black-box VI coreset construction and, from the extended driver
+(psvi_experiments.py), the MFVI selection by predictive scores.  No CLI: method_args is the reference's dict of parsed arguments.
 
 Multi-GPU (one process per GPU): every rank calls
 experiment_driver with the same arguments and its ``world`` / ``rank`` (or
@@ -15,7 +16,7 @@ from ..inference import (PSVI, PSVIAV, PSVIAFixedU, PSVIFixedU, PSVIFreeV, PSVIL
                          PSVI_Ablated, PSVI_No_IW, PSVI_No_Rescaling, PSVI_regressor,
                          PSVIAV_regressor, PSVILearnV_regressor, run_mfvi, run_mfvi_regressor,
                          run_mfvi_subset, run_mfvi_subset_regressor, run_opsvi, run_random,
-                         run_sparsevi, run_sparsevi_with_bb_elbo)
+                         run_selection_with_mfvi, run_sparsevi, run_sparsevi_with_bb_elbo)
 from .experiments_utils import read_dataset, read_regression_dataset, rec_dd, write_to_files
 
 
@@ -47,6 +48,16 @@ inf_dict = {
 }
 
 
+# psvi_experiments.py:430-460, the extended driver's additions to that table
+# that run on the HIP path (its "el2n" and "kmeans" do not: ten-seed score files
+# nothing writes, sklearn).  A table of its own: inf_dict is flow_psvi.py's, and
+# tests/test_giga_cpu.py and tests/test_mfvi_regr_cpu.py pin its keys.
+# experiment_driver looks a method up in both.
+extended_inf_dict = {
+    "mfvi_selection": run_selection_with_mfvi,
+}
+
+
 def experiment_driver(datasets, methods, method_args, write=True, world=None, rank=None,
                       comm=None):
     """For each dataset, method, trial and coreset size: run the method with
@@ -62,15 +73,25 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
     for dnm in datasets:
         x, y, xt, yt, N, D, train_dataset, test_dataset, nc = read_dataset(dnm, method_args)
         for nm_alg in methods:
-            if nm_alg not in inf_dict:
+            if nm_alg not in inf_dict and nm_alg not in extended_inf_dict:
                 raise NotImplementedError(f"method {nm_alg!r} is not on the HIP path")
+            inf_alg = inf_dict.get(nm_alg) or extended_inf_dict[nm_alg]
             logistic_regression = method_args.get(
                 "logistic_regression", method_args.get("architecture") == "logreg")
             compute_weights_entropy = (not nm_alg.startswith(("opsvi", "mfvi_subset"))
                                        and method_args.get("compute_weights_entropy", True))
             sizes = (method_args["coreset_sizes"]
-                     if nm_alg.startswith(("psvi", "opsvi", "mfvi_subset")) else [-1])
+                     if nm_alg.startswith(("psvi", "opsvi", "mfvi_subset", "mfvi_selection"))
+                     else [-1])
             extra = dict(shard) if nm_alg.startswith("psvi") else {}
+            if nm_alg == "mfvi_selection":
+                # psvi_experiments.py:558-566, with its parser's defaults
+                extra.update(
+                    mfvi_selection_method=method_args.get("mfvi_selection_method", "kmeans"),
+                    pretrain_epochs=method_args.get("pretrain_epochs", 5),
+                    data_folder=method_args.get("data_folder"),
+                    load_from_saved=method_args.get("load_from_saved", False),
+                    loaded_from_psvi=method_args.get("loaded_from_psvi", True))
             if nm_alg.startswith("psvi"):
                 # flow_psvi.py's continual-learning arguments; absent: off, as before
                 extra.update({k: method_args.get(k, False)
@@ -82,7 +103,7 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
                              lr0joint=method_args.get("lr0joint", 1e-3))
             for t in range(method_args["num_trials"]):
                 for ps in sizes:
-                    results[dnm][nm_alg][ps][t] = inf_dict[nm_alg](
+                    results[dnm][nm_alg][ps][t] = inf_alg(
                         **extra,
                         mc_samples=method_args["mc_samples"],
                         num_epochs=method_args["num_epochs"],

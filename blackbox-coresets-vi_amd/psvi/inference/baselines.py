@@ -122,6 +122,29 @@ public ``run_sparsevi(diagonal=False)`` / ``run_opsvi(diagonal=False)`` still
 raise: tests/test_laplace_cpu.py::test_argument_checks asserts it, and opening
 the keyword waits on that test (as ``"giga"`` in ``inf_dict`` does).
 
+MFVI selection ("MFVI selection"):
+
+  MfviSelect               baselines.py:1515-1727  select_data, evaluate_coreset
+  run_selection_with_mfvi  baselines.py:1855-1952  pretrain, score, pick, train on the subset
+
+The selection is psvi.inference.utils.CoresetSelect (its module docstring lists
+what it keeps of the reference); the training on the chosen rows is
+``_MFVIStepper.step`` with one weight per row, the tests one
+psvi_predict_scores launch per batch.  Reference behaviours kept:
+
+* ``evaluate_coreset`` steps once per batch of 128 of the chosen rows and calls
+  ``zero_grad`` once per outer iteration only: within an iteration the batches'
+  gradients accumulate from step to step (visible only when num_pseudo > 128).
+* ``elbos`` holds minus the LAST batch's loss of every iteration; ``accs`` /
+  ``nlls`` hold the last test only (a one-entry list each; None if no test
+  ran); ``times`` is 0; ``csizes`` repeats num_pseudo; ``wt_index`` maps
+  str(row index) to its weight n_train / num_pseudo, in the permuted order.
+* The net is built in the constructor, after a reseed, before the selection.
+Divergences: ``loaded_from_psvi=True`` (a new keyword, passed through to
+CoresetSelect, the reference's default there) falls back to computing the
+scores; "incremental", the k-means / submodular methods, architecture="lenet"
+and log_pseudodata raise NotImplementedError.
+
 ``mcmc=True`` (stan) and, on the public sparsevi / opsvi, ``diagonal=False``
 raise NotImplementedError.
 Optional test hooks: ``noise_source(n)`` supplies each host draw,
@@ -141,11 +164,12 @@ from torch.utils.data import DataLoader
 from ..models import (VILinear, VILinearMultivariateNormal, categorical_fn, make_fc2net,
                       make_fcnet, make_lenet, make_regressor_net, model_spec)
 from ..runtime import (InnerLoopPlan, adam_update_, check_binary, giga_step, laplace_fit,
-                       laplace_sample_full, laplace_scores, mfvi_fit, randn_)
+                       laplace_sample_full, laplace_scores, mfvi_fit, predict_scores, randn_)
 
 __all__ = ["set_up_model", "pseudo_subsample_init", "pseudo_rand_init", "run_mfvi",
            "run_mfvi_subset", "process_wt_index", "run_laplace", "run_random", "run_sparsevi",
-           "run_opsvi", "run_giga", "fit", "run_mfvi_regressor", "run_mfvi_subset_regressor"]
+           "run_opsvi", "run_giga", "fit", "run_mfvi_regressor", "run_mfvi_subset_regressor",
+           "MfviSelect", "run_selection_with_mfvi"]
 
 
 def set_up_model(D=None, n_hidden=None, nc=None, mc_samples=None, architecture=None,
@@ -223,28 +247,62 @@ class _MFVIStepper:
                                           prior_sd=self.prior_sd)
         return self.plans[B]
 
-    def step(self, xb, yb, scale):
-        """loss = scale * sum_{s,b} NLL + KL (VILinear modules) and one
-        torch.optim.Adam step; returns the loss (device float64)."""
+    def _rows(self, xb, yb):
         B = int(xb.shape[0])
-        plan = self._plan(B)
         u = xb.detach().to(self.device, torch.float32).reshape(B, -1).contiguous()
         z = yb.detach().to(self.device)
         if z.is_floating_point() and not torch.equal(z, z.round()):
             raise ValueError("labels must hold class ids")
-        z = z.to(torch.int32).contiguous()
-        w = torch.full((B,), float(scale), device=self.device)
+        return B, u, z.to(torch.int32).contiguous()
+
+    def _draw(self, plan, blocks=1):
+        """The noise of ``blocks`` forward passes, one after the other."""
         if self.eps_source is not None:
-            eps = self.eps_source(plan.eps_count).to(self.device, torch.float32).contiguous()
-        else:
-            eps = torch.empty(plan.eps_count, device=self.device)
+            eps = [self.eps_source(plan.eps_count).to(self.device, torch.float32)
+                   for _ in range(blocks)]
+            return (eps[0] if blocks == 1 else torch.cat(eps)).contiguous()
+        eps = torch.empty(blocks * plan.eps_count, device=self.device)
+        if plan.eps_stride == plan.eps_count:  # the blocks are one stretch of the stream
             randn_(eps, self.seed, self.offset)
+            self.offset += blocks * plan.eps_stride
+            return eps
+        for k in range(blocks):
+            randn_(eps[k * plan.eps_count:(k + 1) * plan.eps_count], self.seed, self.offset)
             self.offset += plan.eps_stride
+        return eps
+
+    def step(self, xb, yb, scale, weights=None, accumulate=None):
+        """loss = sum_b w_b sum_s NLL + KL (VILinear modules), w_b = scale or
+        ``weights`` (one per row), and one torch.optim.Adam step; returns the
+        loss (device float64).  ``accumulate`` (a zeroed parameter-sized tensor
+        the caller keeps) receives the gradient on top of what it holds, and
+        the step takes the sum: an optimiser whose zero_grad runs less often
+        than its step."""
+        B, u, z = self._rows(xb, yb)
+        plan = self._plan(B)
+        if weights is None:
+            w = torch.full((B,), float(scale), device=self.device)
+        else:
+            w = weights.detach().to(self.device, torch.float32).reshape(B).contiguous()
+        eps = self._draw(plan)
         loss, grad = plan.elbo_grad(u, z, w, eps, self.params,
                                     include_kl=self.fam != "fullcov")
+        if accumulate is not None:
+            grad = accumulate.add_(grad)
         self.t += 1
         adam_update_(self.params, grad, self.m, self.v, step=self.t, lr=self.lr, kind="torch")
         return loss
+
+    def predict(self, x, y, rows_per_draw, want=(), state=None, stats=False):
+        """The mean-logit predictive of the rows x in one psvi_predict_scores
+        launch, fresh weights per ``rows_per_draw`` rows (psvi.runtime.predict_scores)."""
+        if self.fam != "meanfield":
+            raise NotImplementedError("the predictive scores run mean-field stacks only")
+        n, u, z = self._rows(x, y)
+        plan = next(iter(self.plans.values())) if self.plans else self._plan(1)  # M is not read
+        eps = self._draw(plan, -(-n // int(rows_per_draw)))
+        return predict_scores(plan, u, z, eps, self.params, rows_per_draw, want=want,
+                              state=state, stats=stats)
 
     def sync_model(self):
         with torch.no_grad():
@@ -913,3 +971,129 @@ def _run_opsvi(x, y, xt, yt, mc_samples=10, data_minibatch=128, num_epochs=100, 
         results["zs"] = [z.cpu().numpy()] * n_logged
         results["vs"] = [w.detach().cpu().numpy()] * n_logged
     return results
+
+
+# ------------------------------------------------------------- MFVI selection
+class MfviSelect:
+    """MFVI on a subset of the training rows chosen by CoresetSelect
+    (baselines.py:1515-1727): ``select_data`` pretrains, scores and picks the
+    rows, ``evaluate_coreset`` trains this object's own net on the weighted
+    subset and returns the reference's results dict."""
+
+    def __init__(self, x=None, y=None, xt=None, yt=None, dnm=None, train_dataset=None,
+                 test_dataset=None, data_minibatch=128, num_pseudo=100, nc=2,
+                 architecture="logistic_regression", D=None, n_hidden=100, mc_samples=4,
+                 init_sd=None, lr0net=1e-3, num_epochs=100, log_every=10,
+                 distr_fn=categorical_fn, seed=0, mul_fact=2, log_pseudodata=False,
+                 score_method="kmeans", pretrain_epochs=5, data_folder=None,
+                 load_from_saved=False, train_weights=True, distance_fn="euclidean",
+                 last_layer_only=False, loaded_from_psvi=True, eps_source=None):
+        if log_pseudodata:
+            raise NotImplementedError("log_pseudodata (grid predictions) is not on the HIP path")
+        if architecture == "lenet":
+            raise NotImplementedError('architecture="lenet": psvi_predict_scores runs the affine '
+                                      "mean-field stacks only")
+        self.x, self.y, self.xt, self.yt, self.dnm = x, y, xt, yt, dnm
+        self.train_dataset, self.test_dataset = train_dataset, test_dataset
+        self.data_minibatch, self.num_pseudo, self.nc = data_minibatch, num_pseudo, nc
+        self.architecture, self.D, self.n_hidden = architecture, D, n_hidden
+        self.mc_samples, self.init_sd, self.lr0net = mc_samples, init_sd, lr0net
+        self.num_epochs, self.log_every, self.distr_fn = num_epochs, log_every, distr_fn
+        self.seed, self.mul_fact, self.log_pseudodata = seed, mul_fact, log_pseudodata
+        self.score_method, self.pretrain_epochs = score_method, pretrain_epochs
+        self.data_folder, self.load_from_saved = data_folder, load_from_saved
+        self.train_weights, self.distance_fn = train_weights, distance_fn
+        self.last_layer_only, self.loaded_from_psvi = last_layer_only, loaded_from_psvi
+        self.eps_source = eps_source
+        self.wt_vec = len(self.train_dataset) / self.num_pseudo * torch.ones(self.num_pseudo)
+        self._setup()
+
+    def select_data(self):
+        from .utils import CoresetSelect
+
+        select_method = CoresetSelect(
+            train_dataset=self.train_dataset, score_method=self.score_method,
+            test_dataset=self.test_dataset, num_pseudo=self.num_pseudo, nc=self.nc,
+            architecture=self.architecture, D=self.D, n_hidden=self.n_hidden,
+            distr_fn=self.distr_fn, mc_samples=self.mc_samples, init_sd=self.init_sd,
+            data_minibatch=self.data_minibatch, pretrain_epochs=self.pretrain_epochs,
+            lr0net=self.lr0net, log_every=10, data_folder=self.data_folder,
+            load_from_saved=self.load_from_saved, dnm=self.dnm, distance_fn=self.distance_fn,
+            last_layer_only=self.last_layer_only, loaded_from_psvi=self.loaded_from_psvi,
+            eps_source=self.eps_source)
+        select_method.select_data()
+        self.chosen_dataset = select_method.chosen_dataset
+        self.wt_index = select_method.wt_index
+
+    def _setup(self):
+        self.device = _device()
+        random.seed(self.seed), np.random.seed(self.seed), torch.manual_seed(self.seed)
+        self.net = set_up_model(architecture=self.architecture, D=self.D, n_hidden=self.n_hidden,
+                                nc=self.nc, mc_samples=self.mc_samples,
+                                init_sd=self.init_sd).to(self.device)
+
+    def _test(self, stepper):
+        """The last test alone is kept: one launch per batch of a newly shuffled loader."""
+        test_loader = DataLoader(self.test_dataset, batch_size=self.data_minibatch,
+                                 pin_memory=True, shuffle=True)
+        total, stats = 0, torch.zeros(2, dtype=torch.float64, device=self.device)
+        for xt, yt in test_loader:
+            stats += stepper.predict(xt, yt, int(xt.shape[0]), stats=True)["stats"]
+            total += yt.size(0)
+        corrects, test_nll = stats.tolist()
+        return [corrects / float(total)], [test_nll / float(total)]
+
+    def evaluate_coreset(self):
+        """baselines.py:1660-1727: per iteration one step per batch of 128 of the
+        chosen rows, under ONE zero_grad: the batches' gradients add up across
+        the steps of an iteration (visible when num_pseudo > 128)."""
+        elbos_mfvi, accs_mfvi, nlls_mfvi = [], None, None
+        stepper = _MFVIStepper(self.net, self.device, self.lr0net, self.seed, self.eps_source)
+        items = [self.chosen_dataset[i] for i in range(len(self.chosen_dataset))]
+        xs = torch.stack([torch.as_tensor(it[1]) for it in items])
+        ys = torch.as_tensor([float(it[2]) for it in items])
+        ws = torch.as_tensor([float(it[3]) for it in items])
+        batches = [(xs[lo:lo + 128], ys[lo:lo + 128], ws[lo:lo + 128])
+                   for lo in range(0, len(items), 128)]
+        acc = torch.zeros_like(stepper.params) if len(batches) > 1 else None
+        for i in range(self.mul_fact * self.num_epochs):
+            if acc is not None:
+                acc.zero_()
+            for xb, yb, wb in batches:
+                loss = stepper.step(xb, yb, None, weights=wb, accumulate=acc)
+            elbos_mfvi.append(-loss.item())
+            if i % self.log_every == 0:
+                accs_mfvi, nlls_mfvi = self._test(stepper)
+        stepper.sync_model()
+        return {"accs": accs_mfvi, "nlls": nlls_mfvi, "times": 0, "elbos": elbos_mfvi,
+                "csizes": [self.num_pseudo] * (self.mul_fact * self.num_epochs),
+                "wt_index": self.wt_index}
+
+
+def run_selection_with_mfvi(x=None, y=None, xt=None, yt=None, mc_samples=4, data_minibatch=128,
+                            num_epochs=100, log_every=10, D=None, lr0net=1e-3, mul_fact=2,
+                            seed=0, distr_fn=categorical_fn, log_pseudodata=False,
+                            train_dataset=None, test_dataset=None, num_pseudo=100,
+                            init_args="subsample", architecture=None, n_hidden=None, nc=2,
+                            dnm=None, init_sd=None, mfvi_selection_method="kmeans",
+                            pretrain_epochs=5, data_folder=None, load_from_saved=False,
+                            distance_fn="euclidean", last_layer_only=False,
+                            loaded_from_psvi=True, eps_source=None, **kwargs):
+    """Pretrain by MFVI, score every training row, keep the top rows per class,
+    train MFVI on that weighted subset (baselines.py:1855-1952).  Returns
+    {accs, nlls, times, elbos, csizes, wt_index}."""
+    if mfvi_selection_method == "incremental":
+        raise NotImplementedError('mfvi_selection_method "incremental" starts from a k-means '
+                                  "selection (sklearn), which is not on the HIP path")
+    mfvi_select = MfviSelect(
+        x=x, y=y, xt=xt, yt=yt, dnm=dnm, train_dataset=train_dataset, test_dataset=test_dataset,
+        data_minibatch=data_minibatch, num_pseudo=num_pseudo, nc=nc, architecture=architecture,
+        D=D, n_hidden=n_hidden, mc_samples=mc_samples, init_sd=init_sd, lr0net=lr0net,
+        num_epochs=num_epochs, log_every=log_every, distr_fn=categorical_fn, seed=seed,
+        mul_fact=mul_fact, log_pseudodata=log_pseudodata, score_method=mfvi_selection_method,
+        pretrain_epochs=pretrain_epochs, data_folder=data_folder,
+        load_from_saved=load_from_saved, distance_fn=distance_fn,
+        last_layer_only=last_layer_only, loaded_from_psvi=loaded_from_psvi,
+        eps_source=eps_source)
+    mfvi_select.select_data()
+    return mfvi_select.evaluate_coreset()

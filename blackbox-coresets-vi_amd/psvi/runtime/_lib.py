@@ -155,6 +155,20 @@ class CoresetDrawReq(ctypes.Structure):
     ]
 
 
+class PredictScoresReq(ctypes.Structure):
+    _fields_ = [
+        ("plan", ctypes.c_void_p),
+        ("n_rows", ctypes.c_int32), ("rows_per_draw", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("z", ctypes.c_void_p), ("eps", ctypes.c_void_p),
+        ("params", ctypes.c_void_p),
+        ("mean_logits", ctypes.c_void_p), ("least_conf", ctypes.c_void_p),
+        ("entropy", ctypes.c_void_p), ("el2n", ctypes.c_void_p), ("correct", ctypes.c_void_p),
+        ("last_acc", ctypes.c_void_p), ("forgetting", ctypes.c_void_p),
+        ("never_learnt", ctypes.c_void_p),
+        ("stats_out", ctypes.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -216,6 +230,7 @@ SIGNATURES = {
     "psvi_laplace_scores": (_I32, [ctypes.POINTER(LaplaceScoresReq), _P]),
     "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),
     "psvi_coreset_draw": (_I32, [ctypes.POINTER(CoresetDrawReq), _P]),
+    "psvi_predict_scores": (_I32, [ctypes.POINTER(PredictScoresReq), _P]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -932,6 +932,63 @@ def giga_step(samples, rows, labels, lw, want_ll=False):
     return out
 
 
+PREDICT_OUTPUTS = ("mean_logits", "least_conf", "entropy", "el2n", "correct")
+_PREDICT_NEED_Z = ("el2n", "correct")
+
+
+def predict_scores(plan, x, z, eps, params, rows_per_draw, want=PREDICT_OUTPUTS, state=None,
+                   stats=False):
+    """The scoring pass of the MFVI selection baselines (psvi_predict_scores):
+    the mean-logit forward of a mean-field categorical plan over the rows x
+    (n_rows, D) in one launch, rows [k rpd, (k + 1) rpd) on eps block k of eps
+    (ceil(n_rows / rpd) blocks of plan.eps_count floats).  ``want`` names the
+    per-row outputs (PREDICT_OUTPUTS); ``state`` = (last_acc, forgetting,
+    never_learnt), three float32 (n_rows,) device tensors, is updated in place
+    as MeanFieldVI.after_epoch does; ``stats=True`` adds ``stats`` (2 float64:
+    the number of correct rows, sum_j -log p_j[z_j]).  z (int32 class ids) may
+    be None when nothing asked for reads labels; a label outside [0, C) is
+    refused here (PSVI_EINVAL), the one check the library leaves to its caller.
+    Returns a dict of device tensors."""
+    if not isinstance(plan, InnerLoopPlan):
+        raise ValueError("plan must be an InnerLoopPlan")
+    want = tuple(want)
+    bad = [k for k in want if k not in PREDICT_OUTPUTS]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}: choose from {PREDICT_OUTPUTS}")
+    rpd = int(rows_per_draw)
+    if x is None or x.dim() != 2 or int(x.shape[0]) < 1:
+        raise ValueError("x must be (n_rows, D) with n_rows >= 1")
+    if rpd < 1:
+        raise ValueError("rows_per_draw must be >= 1")
+    n_rows, C = int(x.shape[0]), plan.layers[-1][1]
+    _need(x, "x", n_rows * plan.in_features)
+    _need(eps, "eps", -(-n_rows // rpd) * plan.eps_count)
+    _need(params, "params", plan.param_count)
+    if state is not None:
+        if len(state) != 3:
+            raise ValueError("state is (last_acc, forgetting, never_learnt)")
+        for t, nm in zip(state, ("last_acc", "forgetting", "never_learnt")):
+            _need(t, nm, n_rows)
+    need_z = stats or state is not None or any(k in _PREDICT_NEED_Z for k in want)
+    if z is not None:
+        _need(z, "z", n_rows, torch.int32)
+        if need_z and (int(z.min()) < 0 or int(z.max()) >= C):
+            raise _lib.PsviError(f"psvi_predict_scores failed (PSVI_EINVAL): a label lies outside "
+                                 f"[0, {C})")
+    dev = x.device
+    out = {k: torch.empty((n_rows, C) if k == "mean_logits" else (n_rows,), dtype=torch.float32,
+                          device=dev) for k in want}
+    if stats:
+        out["stats"] = torch.empty(2, dtype=torch.float64, device=dev)
+    st = state if state is not None else (None, None, None)
+    req = _lib.PredictScoresReq(plan.handle, n_rows, rpd, _ptr(x), _ptr(z), _ptr(eps), _ptr(params),
+                                *(_ptr(out.get(k)) for k in PREDICT_OUTPUTS),
+                                *(_ptr(t) for t in st), _ptr(out.get("stats")))
+    check(plan.lib.psvi_predict_scores(ctypes.byref(req), _stream()), "psvi_predict_scores")
+    _wrote(*st)
+    return out
+
+
 DRAW_STATUS = {1: "a weight is negative or not finite", 2: "the weights sum to zero",
                3: "fewer positive weights than rows to draw without replacement"}
 

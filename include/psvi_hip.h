@@ -814,6 +814,59 @@ typedef struct psvi_mfvi_fit_req {
 int psvi_mfvi_fit(const psvi_mfvi_fit_req* req, void* stream);
 int psvi_mfvi_fit_query(const psvi_net_desc* desc, int64_t* out);
 
+/* ---- predictive scores (the MFVI data-selection baselines) ----------------
+ * The scoring pass of run_selection_with_mfvi (reference
+ * psvi/inference/baselines.py:1515-1952; MeanFieldVI.test / after_epoch,
+ * psvi/inference/utils.py:342-387; ScoreSelection._get_uncertainty_score,
+ * utils.py:992-1084): a forward pass of the plan's S-sample mean-field
+ * categorical net over n_rows rows in ONE launch, and per row
+ *   mean_logits = mean over s of logits_s;  p = softmax_c(mean_logits)
+ *   least_conf  = 1 - max_c p            entropy = -sum_c p log(p + 1e-20)
+ *   el2n        = | p - onehot(z) |_2    correct = 1.0 if argmax_c mean_logits == z
+ * (the softmax of the mean logit, not the mean of softmaxes; the first index
+ * among equal maxima, as torch.argmax), and with the three state vectors,
+ * MeanFieldVI.after_epoch's forgetting update in its order:
+ *   forgetting += (last_acc > correct); last_acc = correct;
+ *   never_learnt = min(never_learnt, 1 - correct).
+ * stats_out[0] <- sum_j correct_j, stats_out[1] <- sum_j -log p_j[z_j]
+ * (written, not accumulated).
+ * eps holds one block of EPS_COUNT floats (psvi_elbo_grad's layout) per
+ * rows_per_draw rows: rows [k rpd, (k + 1) rpd) use block k, as the reference
+ * draws fresh weights for every minibatch of an unshuffled loader.  The plan's
+ * M is not read; its scratch serves one call at a time.
+ * Numerics: fp32 network and scores, every dot product from the bias over the
+ * inputs in ascending order, the mean over s in ascending s; stats_out in
+ * double: a fixed tree per group of rows, then the workgroups' partials in
+ * a fixed strided-then-tree order by a last one-workgroup kernel.  Every per-row output has one
+ * writer; no atomics; two runs are bitwise equal.  [S][n_rows][C] logits are
+ * never written to memory.
+ * Errors: PSVI_ESTATE for a full-covariance, LeNet, Gaussian or Bernoulli plan
+ * or world > 1; PSVI_EINVAL for n_rows / rows_per_draw < 1, null x / eps /
+ * params, no output requested, the state pointers not given together, or an
+ * output that reads labels without z; PSVI_EUNSUP when one unit's weights of a
+ * layer and one row's activations exceed the 160 KiB of LDS.  Labels outside
+ * [0, C) are not detected here (a row with one counts as wrong, with
+ * -log p = 0): the caller checks them. */
+typedef struct psvi_predict_scores_req {
+    const psvi_plan* plan;     /* mean-field, categorical, world 1; its M is NOT read   */
+    int32_t n_rows;            /* >= 1, any value                                         */
+    int32_t rows_per_draw;     /* >= 1: rows [k*rpd, (k+1)*rpd) use eps block k           */
+    const float*   x;          /* [n_rows][D]                                             */
+    const int32_t* z;          /* [n_rows] class ids; nullable if no output needs labels  */
+    const float*   eps;        /* [ceil(n_rows/rpd)][EPS_COUNT], psvi_elbo_grad's layout  */
+    const float*   params;
+    float* mean_logits;        /* [n_rows][C]   mean over s of logits_s      (nullable)   */
+    float* least_conf;         /* [n_rows]  1 - max_c p                      (nullable)   */
+    float* entropy;            /* [n_rows]  -sum_c p log(p + 1e-20)          (nullable)   */
+    float* el2n;               /* [n_rows]  | p - onehot(z) |_2              (nullable)   */
+    float* correct;            /* [n_rows]  1.0 if argmax_c mean logit == z  (nullable)   */
+    float* last_acc;           /* [n_rows] in/out, forgetting state          (nullable)   */
+    float* forgetting;         /* [n_rows] in/out                            (nullable)   */
+    float* never_learnt;       /* [n_rows] in/out                            (nullable)   */
+    double* stats_out;         /* [2]: correct count, sum_j -log p_j[z_j]    (nullable)   */
+} psvi_predict_scores_req;
+int psvi_predict_scores(const psvi_predict_scores_req* req, void* stream);
+
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's
  * objective, KL included) at fixed eps, world == 1:
