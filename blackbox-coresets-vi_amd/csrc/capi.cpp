@@ -132,6 +132,31 @@ int plan_to_device(psvi_plan& p) {
     return 0;
 }
 
+}  // namespace
+
+// The opt-ins made so far: a short list behind a mutex (thread ranks reach it
+// together; a handful of kernels on a handful of devices).
+hipError_t psvi::allow_dynamic_lds(const void* kernel, size_t bytes) {
+    struct Done {
+        const void* kernel;
+        int dev;
+        size_t bytes;
+    };
+    static std::mutex mu;
+    static std::vector<Done> done;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Done& d : done)
+        if (d.kernel == kernel && d.dev == dev && d.bytes >= bytes) return hipSuccess;
+    const hipError_t e =
+        hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) done.push_back({kernel, dev, bytes});
+    return e;
+}
+
+namespace {
+
 hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Diagnostics (PSVI_DBG_LOOP_TIMING): HIP events around the network and the
@@ -255,9 +280,9 @@ int psvi_plan_create(int32_t family, const psvi_net_desc* d, int32_t world, int3
         return fail(PSVI_EINVAL, "world/rank out of range (world <= 8)");
     int ndev = 0;
     const bool have_dev = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-    if (have_dev) {
-        static std::once_flag once;
-        std::call_once(once, net_set_lds_limit);
+    if (have_dev) {  // on the device the tables go to
+        HIP_TRY(net_allow_lds());
+        HIP_TRY(rop_allow_lds());
     }
     psvi_plan* p = new psvi_plan();
     p->family = family;

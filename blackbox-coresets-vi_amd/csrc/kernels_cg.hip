@@ -37,24 +37,6 @@ constexpr int kCgBlocks = 1024;  // grid of the reductions (4 per CU)
 // [5] beta, [6] alpha
 enum { kRtr = 0, kPap = 1, kRnrn = 2, kDone = 3, kAeff = 4, kBeta = 5, kAlpha = 6 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
-// block sum in wave order (fixed: run-to-run bitwise), valid in thread 0
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    v = wave_sum_d(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kCgThreads / 64; ++i) t += red[i];
-    return t;
-}
-
 // The grid sum's hand-off: thread 0 holds this block's partial.  Every thread
 // calls it; returns true in thread 0 of the last-arriving block, with the
 // total in *tot.  The last block reads the slots with all its threads (four
@@ -76,7 +58,7 @@ __device__ __forceinline__ bool grid_sum(double part, double* slots, unsigned* c
         const unsigned b = threadIdx.x + i * kCgThreads;
         v[i] = b < gridDim.x ? __hip_atomic_load(slots + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     }
-    const double t = block_sum_d((v[0] + v[1]) + (v[2] + v[3]), red);
+    const double t = block_sum<kCgThreads>((v[0] + v[1]) + (v[2] + v[3]), red);
     if (threadIdx.x == 0) {
         *tot = t;
         __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -106,7 +88,7 @@ __global__ __launch_bounds__(kCgThreads) void cg_pap_kernel(int64_t n, const flo
     for (int64_t i = (int64_t)blockIdx.x * kCgThreads + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * kCgThreads)
         acc += p[i] * cg_ap(hv1[i], hv2[i], lr);
-    const double part = block_sum_d(acc, red);
+    const double part = block_sum<kCgThreads>(acc, red);
     double tot;
     __syncthreads();  // red reused by the grid sum
     if (grid_sum(part, slots, cnt, &tot, red)) state[kPap] = tot;
@@ -126,7 +108,7 @@ __global__ __launch_bounds__(kCgThreads) void cg_residual_kernel(int64_t n, cons
         r[i] = rn;
         acc += rn * rn;
     }
-    const double part = block_sum_d(acc, red);
+    const double part = block_sum<kCgThreads>(acc, red);
     double rnrn;
     __syncthreads();  // red reused by the grid sum
     if (grid_sum(part, slots, cnt, &rnrn, red)) {

@@ -36,7 +36,6 @@
 // log-likelihood vectors, the greedy pick and the line-search step, one
 // workgroup over the same float-rounded ll (giga_step_kernel below).
 #include "psvi_internal.hpp"
-#include "select_reduce.hpp"
 
 namespace psvi {
 
@@ -173,13 +172,7 @@ hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st) {
     const bool xlds = lap_fit_lds(r.Nu, a.ds, true) <= kLapLds;
     const size_t lds = lap_fit_lds(r.Nu, a.ds, xlds);
     auto kernel = xlds ? laplace_fit_kernel<true> : laplace_fit_kernel<false>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[xlds]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLapLds);
-        if (e != hipSuccess) return e;
-        attr_set[xlds] = true;
-    }
+    if (hipError_t e = allow_dynamic_lds((const void*)kernel, kLapLds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(1), dim3(kLapThreads), lds, st, a);
     return hipGetLastError();
 }
@@ -311,13 +304,9 @@ hipError_t launch_laplace_sample_full(const LaplaceSampleFull& r, hipStream_t st
     a.nb = std::min(std::min(kLapThreads, room), r.S);
     const size_t lds = lap_full_lds(r.Nu, r.d, a.nb);
     if (lds > kLapLds) return hipErrorInvalidValue;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)laplace_sample_full_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLapLds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = allow_dynamic_lds((const void*)laplace_sample_full_kernel, kLapLds);
+        e != hipSuccess)
+        return e;
     hipLaunchKernelGGL(laplace_sample_full_kernel, dim3(1), dim3(kLapThreads), lds, st, a);
     return hipGetLastError();
 }
@@ -367,7 +356,7 @@ __global__ __launch_bounds__(kSelThreads) void laplace_scores_kernel(LapScoreArg
         resid[s] = a.scale * data - core;
         rsum += resid[s];
     }
-    const double rbar = sel_sum(rsum, red) / S;
+    const double rbar = tree_sum<kSelThreads>(rsum, red) / S;
     // per column: cll_.j . resid and |cll_.j|, samples in order
     double best = -INFINITY, bestc = -INFINITY;
     int besti = 0x7fffffff;
@@ -392,8 +381,8 @@ __global__ __launch_bounds__(kSelThreads) void laplace_scores_kernel(LapScoreArg
             }
         }
     }
-    bestc = sel_max(bestc, red);
-    sel_argmax_first(best, besti, red, redi);
+    bestc = tree_max<kSelThreads>(bestc, red);
+    tree_argmax_first<kSelThreads>(best, besti, red, redi);
     if (tid == 0) {
         a.result[0] = red[0];
         a.result[1] = (double)(redi[0] == 0x7fffffff ? 0 : redi[0]);
@@ -444,7 +433,7 @@ struct GigaArgs {
 
 // One geodesic-ascent step of GIGA in one workgroup.  A thread owns whole
 // columns (data rows: n = tid, tid + 512, ...) or whole samples (s = tid, ...);
-// the vectors over the samples meet in the fixed trees of select_reduce.hpp.
+// the vectors over the samples meet in the fixed trees of block_reduce.hpp.
 //   columns: mean_n, 1 / max(|cll_.n|, 1e-12), ell_n . lw            -> LDS
 //   samples: sum_lls_s -> L, ell, zeta1, d = normalize(ell - zeta1 lw) -> LDS
 //   columns: score_n = d . normalize(ell_n - (ell_n . lw) lw), first argmax n*
@@ -486,19 +475,19 @@ __global__ __launch_bounds__(kSelThreads) void giga_step_kernel(GigaArgs a) {
         ell[s] = sum;
         sq += sum * sum;
     }
-    const double L = sqrt(sel_sum(sq, red));
+    const double L = sqrt(tree_sum<kSelThreads>(sq, red));
     double z1 = 0.0;
     for (int s = tid; s < S; s += kSelThreads) {
         ell[s] /= fmax(L, 1e-12);
         z1 += ell[s] * (double)a.lw[s];
     }
-    z1 = sel_sum(z1, red);
+    z1 = tree_sum<kSelThreads>(z1, red);
     sq = 0.0;
     for (int s = tid; s < S; s += kSelThreads) {
         dd[s] = ell[s] - z1 * (double)a.lw[s];
         sq += dd[s] * dd[s];
     }
-    const double dnorm = fmax(sqrt(sel_sum(sq, red)), 1e-12);
+    const double dnorm = fmax(sqrt(tree_sum<kSelThreads>(sq, red)), 1e-12);
     for (int s = tid; s < S; s += kSelThreads) dd[s] /= dnorm;
     __syncthreads();
     double best = -INFINITY;
@@ -517,7 +506,7 @@ __global__ __launch_bounds__(kSelThreads) void giga_step_kernel(GigaArgs a) {
             besti = n;
         }
     }
-    sel_argmax_first(best, besti, red, redi);
+    tree_argmax_first<kSelThreads>(best, besti, red, redi);
     const double smax = red[0];
     const int ns = redi[0] == 0x7fffffff ? 0 : redi[0];
     // every thread is past its reads of d (the barriers of the argmax): dd takes ell*
@@ -527,15 +516,15 @@ __global__ __launch_bounds__(kSelThreads) void giga_step_kernel(GigaArgs a) {
         z0 += ell[s] * dd[s];
         z2 += dd[s] * (double)a.lw[s];
     }
-    z0 = sel_sum(z0, red);
-    z2 = sel_sum(z2, red);
+    z0 = tree_sum<kSelThreads>(z0, red);
+    z2 = tree_sum<kSelThreads>(z2, red);
     const double gamma = (z0 - z1 * z2) / (z0 - z1 * z2 + z1 - z0 * z2);
     sq = 0.0;
     for (int s = tid; s < S; s += kSelThreads) {
         ell[s] = (1.0 - gamma) * (double)a.lw[s] + gamma * dd[s];
         sq += ell[s] * ell[s];
     }
-    const double tnorm = fmax(sqrt(sel_sum(sq, red)), 1e-12);
+    const double tnorm = fmax(sqrt(tree_sum<kSelThreads>(sq, red)), 1e-12);
     // the reference scales the weights by the norm taken with the NEW lw
     // (baselines.py:405-413: lw is reassigned before the norm is formed)
     sq = 0.0;
@@ -545,7 +534,7 @@ __global__ __launch_bounds__(kSelThreads) void giga_step_kernel(GigaArgs a) {
         const double u = (1.0 - gamma) * l + gamma * dd[s];
         sq += u * u;
     }
-    const double unorm = sqrt(sel_sum(sq, red));
+    const double unorm = sqrt(tree_sum<kSelThreads>(sq, red));
     if (tid == 0) {
         a.result[0] = smax;
         a.result[1] = (double)ns;
@@ -568,13 +557,8 @@ hipError_t launch_giga_step(const GigaStep& r, hipStream_t st) {
     a.score = r.score; a.lw_out = r.lw_out; a.ll = r.ll_out; a.result = r.result;
     // above the 64 KiB a launch gets unasked at the range's far corner
     constexpr size_t max_lds = sizeof(double) * (3 * (size_t)kLapMaxRows + 2 * (size_t)kSelMaxS);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)giga_step_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = allow_dynamic_lds((const void*)giga_step_kernel, max_lds); e != hipSuccess)
+        return e;
     const size_t lds = sizeof(double) * (3 * (size_t)r.n_data + 2 * (size_t)r.S);
     hipLaunchKernelGGL(giga_step_kernel, dim3(1), dim3(kSelThreads), lds, st, a);
     return hipGetLastError();

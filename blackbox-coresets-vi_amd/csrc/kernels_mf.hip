@@ -388,13 +388,8 @@ __global__ __launch_bounds__(256) void mf_nkl_kernel(MfNklArgs a) {
             acc += -0.5 * (double)th * th * a.inv_s0sq + (double)logf(sp) + 0.5 * (double)e * e;
         }
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.nkl[s] = red[0] - (double)a.n_tot * a.log_s0;
+    acc = tree_sum<256>(acc, red);
+    if (threadIdx.x == 0) a.nkl[s] = acc - (double)a.n_tot * a.log_s0;
 }
 
 // one thread per element: the sums over s in sample order, one writer per slot

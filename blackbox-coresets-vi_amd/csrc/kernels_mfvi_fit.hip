@@ -247,13 +247,8 @@ __global__ __launch_bounds__(kMfFitThreads) void mfvi_fit_kernel(MfFitArgs a) {
                 sv_[prho] = vv;
             }
         if (a.loss) {
-            red[tid] = lpart;
-            __syncthreads();
-            for (int o = NT / 2; o > 0; o >>= 1) {
-                if (tid < o) red[tid] += red[tid + o];
-                __syncthreads();
-            }
-            if (tid == 0) a.loss[(size_t)g * a.T + t] = red[0];
+            const double loss = tree_sum<NT>(lpart, red);
+            if (tid == 0) a.loss[(size_t)g * a.T + t] = loss;
         }
         __syncthreads();
     }
@@ -341,13 +336,7 @@ hipError_t launch_mfvi_fit(const MfviFit& r, hipStream_t st) {
     a.loss = r.loss_out;
     a.ws = (float*)r.ws;
     auto kernel = s.lds ? mfvi_fit_kernel<true> : mfvi_fit_kernel<false>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[s.lds]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfFitLds);
-        if (e != hipSuccess) return e;
-        attr_set[s.lds] = true;
-    }
+    if (hipError_t e = allow_dynamic_lds((const void*)kernel, kMfFitLds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(r.G), dim3(kMfFitThreads), mffit_lds(s, s.lds, s.RB), st, a);
     return hipGetLastError();
 }

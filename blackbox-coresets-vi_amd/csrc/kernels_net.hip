@@ -1546,11 +1546,12 @@ static const NetVariant* net_variant(int family, int lik, bool multi, bool vec, 
     return nullptr;
 }
 
-void net_set_lds_limit() {
+hipError_t net_allow_lds() {
     // gfx950: up to 160 KiB of LDS per workgroup
     for (const NetVariant& v : kNetVariants)
-        (void)hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
+        if (hipError_t e = allow_dynamic_lds((const void*)v.kernel, 160 * 1024); e != hipSuccess)
+            return e;
+    return hipSuccess;
 }
 
 // The fixed fn2 geometry (NetGeo<1 / 2>) applies: the 64 -> 40 -> 40 -> 2

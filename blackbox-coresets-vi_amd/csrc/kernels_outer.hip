@@ -52,35 +52,6 @@ struct OuterArgs {
     float* grad_u;         // [n_pseudo][D] nullable
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
-// block-wide double sum, result in every thread; `red` >= 16 doubles of LDS
-__device__ __forceinline__ double block_sum_all(double v, double* red) {
-    v = wave_sum_d(v);
-    const int lane = threadIdx.x & 63, wid = wave_id(), nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < nw; ++i) t += red[i];
-    return t;
-}
-__device__ __forceinline__ double block_max_all(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, kWave));
-    const int lane = threadIdx.x & 63, wid = wave_id(), nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = -INFINITY;
-    for (int i = 0; i < nw; ++i) t = fmax(t, red[i]);
-    return t;
-}
-
 // one workgroup per sample: sum_i x_si^2 and sum_i eps_si^2 over every layer
 // (mean-field: x = mu + softplus(rho) eps, as the network kernel samples it)
 __global__ __launch_bounds__(256) void outer_stats_kernel(OuterArgs a) {
@@ -141,8 +112,8 @@ __global__ __launch_bounds__(1024) void outer_combine_kernel(OuterArgs a) {
             const double t = (double)a.w[m] * row[m];
             if (m < a.n_pseudo) ps += t; else ds += t;
         }
-        ps = wave_sum_d(ps);
-        ds = wave_sum_d(ds);
+        ps = wave_sum(ps);
+        ds = wave_sum(ds);
         if (lane == 0) {
             const double nkl = -a.stats[2 * s] * inv2 - nlog + 0.5 * a.stats[2 * s + 1] + sl;
             lw[s] = a.ablated ? nkl : -ps + nkl;
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(1024) void eval_weights_kernel(OuterArgs a, int cor
         double ps = 0.0;
         const float* row = a.nll + (size_t)s * a.M;
         for (int m = lane; m < a.n_pseudo; m += 64) ps += (double)a.w[m] * row[m];
-        ps = wave_sum_d(ps);
+        ps = wave_sum(ps);
         if (lane == 0)
             lw[s] = ps + (-a.stats[2 * s] * inv2 - nlog + 0.5 * a.stats[2 * s + 1] + sl);
     }

@@ -29,8 +29,6 @@
 // workgroup in their order, the workgroups' partials by a last one-workgroup
 // kernel (thread t sums partials t, t + 256, ... in order, then the same
 // tree).  No atomics; two runs give the same bits.
-#include <atomic>
-
 #include "psvi_internal.hpp"
 
 namespace psvi {
@@ -198,16 +196,7 @@ __global__ __launch_bounds__(kPredThreads) void predict_scores_kernel(PredArgs a
             dn -= (double)lpz;
         }
         if (a.part) {
-            red[tid] = dc;
-            red[NT + tid] = dn;
-            __syncthreads();
-            for (int o = NT / 2; o > 0; o >>= 1) {
-                if (tid < o) {
-                    red[tid] += red[tid + o];
-                    red[NT + tid] += red[NT + tid + o];
-                }
-                __syncthreads();
-            }
+            tree_sum<NT>({dc, dn}, red);
             if (tid == 0) {
                 tot_c += red[0];
                 tot_n += red[NT];
@@ -224,26 +213,17 @@ __global__ __launch_bounds__(kPredThreads) void predict_scores_kernel(PredArgs a
 // order, then a fixed tree over the threads
 __global__ __launch_bounds__(kPredThreads) void predict_stats_kernel(const double* part, int nb,
                                                                      double* stats) {
-    __shared__ double red[2][kPredThreads];
+    __shared__ double red[2 * kPredThreads];
     const int tid = threadIdx.x;
     double c = 0.0, n = 0.0;
     for (int b = tid; b < nb; b += kPredThreads) {
         c += part[2 * b];
         n += part[2 * b + 1];
     }
-    red[0][tid] = c;
-    red[1][tid] = n;
-    __syncthreads();
-    for (int o = kPredThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            red[0][tid] += red[0][tid + o];
-            red[1][tid] += red[1][tid + o];
-        }
-        __syncthreads();
-    }
+    tree_sum<kPredThreads>({c, n}, red);
     if (tid == 0) {
-        stats[0] = red[0][0];
-        stats[1] = red[1][0];
+        stats[0] = red[0];
+        stats[1] = red[kPredThreads];
     }
 }
 
@@ -320,17 +300,9 @@ hipError_t launch_predict_scores(const psvi_plan& p, const PredictScores& r, hip
     a.el2n = r.el2n; a.correct = r.correct;
     a.last_acc = r.last_acc; a.forgetting = r.forgetting; a.never_learnt = r.never_learnt;
     a.part = r.stats_out ? (double*)p.pred_scratch.dev : nullptr;
-    // the LDS limit is a property of the kernel on one device: once per device
-    static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (dev > 63 || !(attr_set.load() & bit)) {
-        hipError_t e = hipFuncSetAttribute((const void*)predict_scores_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPredLds);
-        if (e != hipSuccess) return e;
-        if (dev <= 63) attr_set.fetch_or(bit);
-    }
+    if (hipError_t e = allow_dynamic_lds((const void*)predict_scores_kernel, kPredLds);
+        e != hipSuccess)
+        return e;
     const int grid = (int)std::min<int64_t>(a.n_items, kPredMaxGrid);
     hipLaunchKernelGGL(predict_sigma_kernel, dim3(std::min(64, (s.n_tot + 255) / 256)), dim3(256), 0,
                        st, a, sig);

@@ -1250,17 +1250,15 @@ static void rop_fill(const psvi_plan& p, RopArgs& a) {
     }
 }
 
+hipError_t rop_allow_lds() {
+    for (const void* f : {(const void*)net_rop_kernel, (const void*)net_rop_mfma_kernel<false>,
+                          (const void*)net_rop_mfma_kernel<true>})
+        if (hipError_t e = allow_dynamic_lds(f, kRopLds); e != hipSuccess) return e;
+    return hipSuccess;
+}
+
 hipError_t launch_net_rop(const psvi_plan& p, const NetRop& r, hipStream_t st) {
     if (r.dzd && p.lik != PSVI_LIK_GAUSSIAN) return hipErrorInvalidValue;
-    static bool once = [] {
-        (void)hipFuncSetAttribute((const void*)net_rop_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRopLds);
-        for (const void* f : {(const void*)net_rop_mfma_kernel<false>,
-                              (const void*)net_rop_mfma_kernel<true>})
-            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRopLds);
-        return true;
-    }();
-    (void)once;
     RopArgs a{};
     rop_fill(p, a);
     a.nsplit = rop_splits(p);

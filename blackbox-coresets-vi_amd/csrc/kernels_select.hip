@@ -23,7 +23,6 @@
 // every sum has one owner and a fixed order; the block-wide sums meet in a
 // fixed tree.  No atomics.
 #include "psvi_internal.hpp"
-#include "select_reduce.hpp"
 
 namespace psvi {
 
@@ -31,14 +30,14 @@ namespace psvi {
 __device__ __forceinline__ void sel_softmax(double* lw, int S, double* red) {
     double mx = -INFINITY;
     for (int s = threadIdx.x; s < S; s += kSelThreads) mx = fmax(mx, lw[s]);
-    mx = sel_max(mx, red);
+    mx = tree_max<kSelThreads>(mx, red);
     double se = 0.0;
     for (int s = threadIdx.x; s < S; s += kSelThreads) {
         const double e = exp(lw[s] - mx);
         lw[s] = e;
         se += e;
     }
-    se = sel_sum(se, red);
+    se = tree_sum<kSelThreads>(se, red);
     for (int s = threadIdx.x; s < S; s += kSelThreads) lw[s] /= se;
     __syncthreads();
 }
@@ -99,9 +98,9 @@ __global__ __launch_bounds__(kSelThreads) void select_scores_kernel(SelArgs a) {
             }
         }
     }
-    bestc = sel_max(bestc, red);
+    bestc = tree_max<kSelThreads>(bestc, red);
     // max corr and its first argument: (value, index) pairs in a fixed tree
-    sel_argmax_first(best, besti, red, redi);
+    tree_argmax_first<kSelThreads>(best, besti, red, redi);
     if (tid == 0) {
         a.result[0] = red[0];
         a.result[1] = (double)(redi[0] == 0x7fffffff ? 0 : redi[0]);
@@ -125,11 +124,11 @@ __global__ __launch_bounds__(kSelThreads) void select_weight_grad_kernel(SelArgs
         rs[s] = sd * data - as;
         lwsum += lw;
     }
-    lwsum = sel_sum(lwsum, red);
+    lwsum = tree_sum<kSelThreads>(lwsum, red);
     sel_softmax(Wl, S, red);
     double rb = 0.0;
     for (int s = tid; s < S; s += kSelThreads) rb += Wl[s] * rs[s];
-    rb = sel_sum(rb, red);
+    rb = tree_sum<kSelThreads>(rb, red);
     if (tid == 0) a.loss[0] = rb - lwsum / S;
     // d loss / d a_s, in place of r_s
     for (int s = tid; s < S; s += kSelThreads) rs[s] = 1.0 / S - Wl[s] * (1.0 + rs[s] - rb);

@@ -8,13 +8,13 @@
 #include <string>
 #include <vector>
 
+#include "block_reduce.hpp"
 #include "psvi_hip.h"
 
 namespace psvi {
 
 constexpr int kMaxL = PSVI_MAX_LAYERS;
 constexpr int kMaxWorld = 8;      // ranks per node (xGMI)
-constexpr int kWave = 64;
 
 // ---------------------------------------------------------------- numerics
 // a * b rounded on its own: never fused into an fma with the add that uses it
@@ -30,84 +30,6 @@ __device__ __forceinline__ float softplus_f(float x) {
     return x > 20.f ? x : log1pf(expf(x));
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-
-// The wave's index in its workgroup, in an SGPR: the compiler cannot prove
-// threadIdx.x >> 6 wave-uniform, and treats loops and branches on it as
-// divergent (exec-masked, with conservative s_waitcnt that drain every
-// outstanding load at the branch).
-__device__ __forceinline__ int wave_id() {
-    return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
-// sum over each 16-lane row (DPP row rotations; every lane of the row active)
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dppf<0x128>(v));
-    v = fmaxf(v, dppf<0x124>(v));
-    v = fmaxf(v, dppf<0x122>(v));
-    v = fmaxf(v, dppf<0x121>(v));
-    return v;
-}
-// max / sum over the first W lanes of each aligned group of W (W = 2, 4:
-// quad permutes; 16: the row reductions above); the result is valid on those
-// lanes
-template <int W>
-__device__ __forceinline__ float lanes_max(float v) {
-    static_assert(W == 2 || W == 4 || W == 16, "2, 4 or 16 lanes");
-    if constexpr (W == 16) {
-        v = fmaxf(v, dppf<0x128>(v));
-        v = fmaxf(v, dppf<0x124>(v));
-        v = fmaxf(v, dppf<0x122>(v));
-        return fmaxf(v, dppf<0x121>(v));
-    } else {
-        v = fmaxf(v, dppf<0xB1>(v));              // quad_perm [1, 0, 3, 2]: lane ^ 1
-        if constexpr (W == 4) v = fmaxf(v, dppf<0x4E>(v));  // quad_perm [2, 3, 0, 1]: lane ^ 2
-        return v;
-    }
-}
-template <int W>
-__device__ __forceinline__ float lanes_sum(float v) {
-    static_assert(W == 2 || W == 4 || W == 16, "2, 4 or 16 lanes");
-    if constexpr (W == 16) {
-        v += dppf<0x128>(v);
-        v += dppf<0x124>(v);
-        v += dppf<0x122>(v);
-        return v + dppf<0x121>(v);
-    } else {
-        v += dppf<0xB1>(v);
-        if constexpr (W == 4) v += dppf<0x4E>(v);
-        return v;
-    }
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dppf<0x128>(v);  // row_ror:8
-    v += dppf<0x124>(v);  // row_ror:4
-    v += dppf<0x122>(v);  // row_ror:2
-    v += dppf<0x121>(v);  // row_ror:1
-    return v;
-}
-
-// Block-wide sum; `red` is >= blockDim/64 floats of LDS.  All threads call.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = wave_id();
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-    return t;  // valid in thread 0
-}
 
 // ------------------------------------------------------- buffer loads (T8)
 // 128-bit SRD in SGPRs + 32-bit per-lane byte offset; the hardware range
@@ -667,7 +589,15 @@ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 int build_plan(psvi_plan& p, std::string& err);
 // the network kernel's chunking and LDS size (kernels_net.hip: its LDS layout)
 size_t net_plan_geometry(psvi_plan& p);
-void net_set_lds_limit();  // kernels_net.hip
+// A launch of `kernel` with up to `bytes` of dynamic LDS (above the 64 KiB a
+// launch gets unasked) on the current device: the opt-in is made once per
+// (kernel, device), whichever thread asks first (capi.cpp)
+hipError_t allow_dynamic_lds(const void* kernel, size_t bytes);
+// the same for every network kernel (kernels_net.hip) and every R-op kernel
+// (kernels_rop.hip): at plan creation, so launch_net and launch_net_rop make
+// no runtime call for it
+hipError_t net_allow_lds();
+hipError_t rop_allow_lds();
 // psvi_debug_set values read when a plan is built
 struct PlanDebug {
     int stream_wgs = 0;       // PSVI_DBG_STREAM_WGS: streaming-update workgroups (0 = 256)
@@ -841,6 +771,8 @@ hipError_t launch_select_weight_grad(int S, int Nu, int B, const float* ll, cons
 // Laplace coreset baselines (kernels_laplace.hip).  The fit: T torch-Adam steps
 // on theta [d] of the weighted logistic log-joint of x [Nu][d] / y / w in one
 // workgroup, then the diagonal precision and (eps given) S samples from it.
+constexpr int kSelThreads = 512;   // the one-workgroup selection, scores and GIGA kernels
+constexpr int kSelMaxS = 2048;     // their per-sample terms live in LDS
 constexpr int kLapMaxD = 256;      // one column owner per thread of the fit's workgroup
 constexpr int kLapMaxNu = 4096;    // the fit's per-row terms live in LDS
 constexpr int kLapMaxRows = 2048;  // the scores' per-row means live in LDS
