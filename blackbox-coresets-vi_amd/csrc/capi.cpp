@@ -1525,6 +1525,48 @@ int psvi_coreset_draw(const psvi_coreset_draw_req* q, void* stream) {
     return 0;
 }
 
+static int kmeans_range(int64_t N, int64_t D, int64_t K) {
+    if (N < 1 || D < 1 || K < 1 || K > N)
+        return fail(PSVI_EINVAL, "k-means takes N >= 1, D >= 1 and 1 <= K <= N");
+    if (K > kKmMaxK || D > kKmMaxD || N > kKmMaxN)
+        return fail(PSVI_EUNSUP, "k-means supports K <= 128, D <= 4096, N <= 2^24");
+    return 0;
+}
+
+int psvi_kmeans_query(int32_t N, int32_t D, int32_t K, int64_t* out) {
+    if (!out) return fail(PSVI_EINVAL, "null pointer");
+    if (int rc = kmeans_range(N, D, K)) return rc;
+    const KmeansShape s = kmeans_shape(N, D, K);
+    out[0] = (int64_t)s.full_bytes;
+    out[1] = (int64_t)s.min_bytes;
+    out[2] = s.DT;
+    out[3] = s.G;
+    return 0;
+}
+
+int psvi_kmeans(const psvi_kmeans_req* q, void* stream) {
+    if (!q) return fail(PSVI_EINVAL, "null request");
+    if (!q->x || !q->centres_out || !q->labels_out || !q->counts_out || !q->inertia_out ||
+        !q->n_iter_out || !q->status_out)
+        return fail(PSVI_EINVAL, "null pointer");
+    if (int rc = kmeans_range(q->N, q->D, q->K)) return rc;
+    if (q->offset % 4) return fail(PSVI_EINVAL, "k-means offset must be a multiple of 4");
+    if (q->max_iter < 0) return fail(PSVI_EINVAL, "max_iter must be >= 0");
+    if (!(q->tol >= 0.0) || !std::isfinite(q->tol))
+        return fail(PSVI_EINVAL, "tol must be finite and >= 0");
+    if (!q->ws || q->ws_bytes < kmeans_shape(q->N, q->D, q->K).min_bytes)
+        return fail(PSVI_ENOSPC, "workspace too small");
+    Kmeans r;
+    r.x = q->x; r.N = q->N; r.D = q->D; r.K = q->K;
+    r.centres_in = q->centres_in; r.seed = q->seed; r.offset = q->offset;
+    r.max_iter = q->max_iter; r.tol = q->tol;
+    r.centres = q->centres_out; r.labels = q->labels_out; r.counts = q->counts_out;
+    r.seeds = q->seeds_out; r.inertia = q->inertia_out; r.n_iter = q->n_iter_out;
+    r.status = q->status_out; r.ws = q->ws; r.ws_bytes = q->ws_bytes;
+    HIP_TRY(launch_kmeans(r, as_stream(stream)));
+    return 0;
+}
+
 int psvi_hvp_partial(const psvi_plan* p, const float* u, const int32_t* z, const float* w,
                      const float* eps, const float* params, const float* vec,
                      int32_t include_kl, float* hv_out, float* du_out, float* dw_out, void* ws,

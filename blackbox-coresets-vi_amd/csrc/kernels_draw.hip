@@ -17,22 +17,6 @@ constexpr int kDrawThreads = 256;
 constexpr int kSortThreads = 1024;
 constexpr int kGatherThreads = 256;
 
-// the Philox output words 4q .. 4q+3 of the stream (seed, offset)
-__device__ __forceinline__ void draw_words(uint64_t seed, uint64_t offset, int64_t q,
-                                           uint32_t (&c)[4]) {
-    const uint64_t ctr = offset / 4 + (uint64_t)q;
-    c[0] = (uint32_t)ctr;
-    c[1] = (uint32_t)(ctr >> 32);
-    c[2] = 0u;
-    c[3] = 0u;
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-// exact in fp64, strictly inside (0, 1)
-__device__ __forceinline__ double draw_uniform(uint32_t word) {
-    return ((double)word + 0.5) * 0x1p-32;
-}
-
 // a weight the draw refuses: negative, NaN or infinite
 __device__ __forceinline__ bool bad_weight(float w) { return !(w >= 0.f) || isinf(w); }
 

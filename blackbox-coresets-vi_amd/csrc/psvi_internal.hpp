@@ -85,6 +85,22 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
     }
 }
 
+// the Philox output words 4q .. 4q+3 of the stream (seed, offset), and the
+// uniform of a word: exact in fp64, strictly inside (0, 1) -- the stream of
+// psvi_coreset_draw and of psvi_kmeans' seeding
+__device__ __forceinline__ void draw_words(uint64_t seed, uint64_t offset, int64_t q,
+                                           uint32_t (&c)[4]) {
+    const uint64_t ctr = offset / 4 + (uint64_t)q;
+    c[0] = (uint32_t)ctr;
+    c[1] = (uint32_t)(ctr >> 32);
+    c[2] = 0u;
+    c[3] = 0u;
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+__device__ __forceinline__ double draw_uniform(uint32_t word) {
+    return ((double)word + 0.5) * 0x1p-32;
+}
+
 // normals 4q .. 4q+3 of the stream (Philox counter offset / 4 + q, Box-Muller)
 __device__ __forceinline__ void randn_quad_vals(uint64_t seed, uint64_t offset, int64_t q,
                                                 float (&r)[4]) {
@@ -855,6 +871,68 @@ struct CoresetDraw {
     int32_t* status_out = nullptr;  // [1]
 };
 hipError_t launch_coreset_draw(const CoresetDraw& r, hipStream_t st);
+// k-means clustering of rows (kernels_kmeans.hip): k-means++ seeding on the
+// Philox stream and Lloyd iterations, every deciding number in fp64
+constexpr int kKmMaxK = 128, kKmMaxD = 4096;
+constexpr int64_t kKmMaxN = 1 << 24;
+constexpr int kKmThreads = 256;
+constexpr int kKmRows = 64;        // rows of a tile, and of a run of the seeding's prefix sum
+constexpr int kKmMaxGrid = 512;    // assignment workgroups: the partials of the one-pass sums
+constexpr int kKmMaxParts = 256;   // row chunks of the second-pass sums
+constexpr int kKmChunk = 16;       // iterations enqueued between two host reads of `done`
+constexpr size_t kKmLds = 76 * 1024;  // dynamic LDS of an assignment workgroup: two per CU
+// what a shape needs (host only): the column tile, the grids and the bytes
+struct KmeansShape {
+    int DT = 0;       // columns of a tile: the centres' fp64 tile and the rows' fp32 tile share kKmLds
+    int XS = 0;       // stride of the row tile (odd: no bank conflicts down a column)
+    int tiles = 0, tpb = 0, G = 0;  // row tiles, tiles per assignment workgroup, workgroups
+    int nruns = 0;    // runs of kKmRows rows
+    int cy = 0;       // combine grid: (K, cy), kKmThreads columns each
+    size_t part = 0;  // bytes of one [K][D] fp64 partial
+    size_t fixed = 0; // bytes before the partials
+    size_t min_bytes = 0, full_bytes = 0;  // one partial / G partials
+};
+inline KmeansShape kmeans_shape(int64_t N, int D, int K) {
+    KmeansShape s;
+    s.DT = (int)std::min<size_t>((size_t)D, (kKmLds - 256) / ((size_t)K * 8 + 4 * kKmRows));
+    s.XS = s.DT | 1;
+    s.tiles = (int)((N + kKmRows - 1) / kKmRows);
+    s.tpb = (s.tiles + kKmMaxGrid - 1) / kKmMaxGrid;
+    s.G = (s.tiles + s.tpb - 1) / s.tpb;
+    s.nruns = s.tiles;
+    s.cy = (D + kKmThreads - 1) / kKmThreads;
+    s.part = align256(sizeof(double) * (size_t)K * D);
+    s.fixed = 256                                              // the state words
+              + align256(sizeof(double) * (size_t)N)           // m: the seeding's distances
+              + 2 * align256(sizeof(double) * (size_t)s.nruns) // run totals, run prefix
+              + 2 * align256(sizeof(int) * (size_t)s.nruns)    // last positive row, non-finite flag
+              + 2 * align256(sizeof(int) * (size_t)s.G)        // changed, non-finite
+              + align256(sizeof(double) * (size_t)s.G)         // inertia
+              + align256(sizeof(int) * (size_t)s.G * K)        // counts
+              + 2 * align256(sizeof(double) * (size_t)K * s.cy);  // shift, of even / odd updates
+    s.min_bytes = s.fixed + s.part;
+    s.full_bytes = s.fixed + (size_t)s.G * s.part;
+    return s;
+}
+struct Kmeans {
+    const float* x = nullptr;  // [N][D]
+    int N = 0, D = 0, K = 0;
+    const double* centres_in = nullptr;  // [K][D], nullable
+    uint64_t seed = 0, offset = 0;
+    int max_iter = 0;
+    double tol = 0.0;
+    double* centres = nullptr;     // [K][D]: the working centres and the result
+    int32_t* labels = nullptr;     // [N]
+    int32_t* counts = nullptr;     // [K]
+    int32_t* seeds = nullptr;      // [K], nullable
+    double* inertia = nullptr;     // [1]
+    int32_t* n_iter = nullptr;     // [1]
+    int32_t* status = nullptr;     // [1]
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+};
+// synchronises the stream once per kKmChunk iterations (the `done` word)
+hipError_t launch_kmeans(const Kmeans& r, hipStream_t st);
 // MFVI regressor fit (kernels_mfvi_fit.hip): T chained steps of a mean-field
 // Gaussian-likelihood MLP on a fixed batch for G members, one workgroup each.
 constexpr int kMfFitThreads = 512;

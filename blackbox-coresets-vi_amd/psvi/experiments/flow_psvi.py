@@ -49,8 +49,10 @@ inf_dict = {
 
 
 # psvi_experiments.py:430-460, the extended driver's additions to that table
-# that run on the HIP path (its "el2n" and "kmeans" do not: ten-seed score files
-# nothing writes, sklearn).  A table of its own: inf_dict is flow_psvi.py's, and
+# that run on the HIP path (its "el2n" does not: ten-seed score files nothing
+# writes).  "mfvi_selection" with a k-means method -- "kmeans" is the default --
+# runs when method_args["clustering"] == "hip" (psvi_kmeans on the device in
+# place of sklearn) and is refused without it.  A table of its own: inf_dict is flow_psvi.py's, and
 # tests/test_giga_cpu.py and tests/test_mfvi_regr_cpu.py pin its keys.
 # experiment_driver looks a method up in both.
 extended_inf_dict = {
@@ -91,7 +93,8 @@ def experiment_driver(datasets, methods, method_args, write=True, world=None, ra
                     pretrain_epochs=method_args.get("pretrain_epochs", 5),
                     data_folder=method_args.get("data_folder"),
                     load_from_saved=method_args.get("load_from_saved", False),
-                    loaded_from_psvi=method_args.get("loaded_from_psvi", True))
+                    loaded_from_psvi=method_args.get("loaded_from_psvi", True),
+                    clustering=method_args.get("clustering"))
             if nm_alg.startswith("psvi"):
                 # flow_psvi.py's continual-learning arguments; absent: off, as before
                 extra.update({k: method_args.get(k, False)

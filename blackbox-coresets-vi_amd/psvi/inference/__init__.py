@@ -7,5 +7,7 @@ from .baselines import (run_mfvi, run_mfvi_subset, run_random, run_sparsevi,  # 
                         run_mfvi_regressor, run_mfvi_subset_regressor, MfviSelect,
                         run_selection_with_mfvi)
 from .utils import (MeanFieldVI, WeightedSubset, Selection, RandomSelection,  # noqa: F401,E402
-                    ScoreSelection, RandomScoreSelection, ScoreCalculator, CoresetSelect)
+                    ScoreSelection, RandomScoreSelection, ScoreCalculator, CoresetSelect,
+                    KmeansCluster, KmeansSelection, KmeansScoreSelection,
+                    WeightedKmeansSelection)
 from .sparsebbvi import run_sparsevi_with_bb_elbo  # noqa: F401,E402

@@ -142,8 +142,10 @@ psvi_predict_scores launch per batch.  Reference behaviours kept:
 * The net is built in the constructor, after a reseed, before the selection.
 Divergences: ``loaded_from_psvi=True`` (a new keyword, passed through to
 CoresetSelect, the reference's default there) falls back to computing the
-scores; "incremental", the k-means / submodular methods, architecture="lenet"
-and log_pseudodata raise NotImplementedError.
+scores; "incremental", kmeans_gradient / submodular, architecture="lenet" and
+log_pseudodata raise NotImplementedError; kmeans, scored_kmeans_* and
+weighted_kmeans run with ``clustering="hip"`` (psvi_kmeans on the device in
+place of sklearn) and are refused without it.
 
 ``mcmc=True`` (stan) and, on the public sparsevi / opsvi, ``diagonal=False``
 raise NotImplementedError.
@@ -987,7 +989,7 @@ class MfviSelect:
                  distr_fn=categorical_fn, seed=0, mul_fact=2, log_pseudodata=False,
                  score_method="kmeans", pretrain_epochs=5, data_folder=None,
                  load_from_saved=False, train_weights=True, distance_fn="euclidean",
-                 last_layer_only=False, loaded_from_psvi=True, eps_source=None):
+                 last_layer_only=False, loaded_from_psvi=True, eps_source=None, clustering=None):
         if log_pseudodata:
             raise NotImplementedError("log_pseudodata (grid predictions) is not on the HIP path")
         if architecture == "lenet":
@@ -1004,7 +1006,7 @@ class MfviSelect:
         self.data_folder, self.load_from_saved = data_folder, load_from_saved
         self.train_weights, self.distance_fn = train_weights, distance_fn
         self.last_layer_only, self.loaded_from_psvi = last_layer_only, loaded_from_psvi
-        self.eps_source = eps_source
+        self.eps_source, self.clustering = eps_source, clustering
         self.wt_vec = len(self.train_dataset) / self.num_pseudo * torch.ones(self.num_pseudo)
         self._setup()
 
@@ -1020,7 +1022,7 @@ class MfviSelect:
             lr0net=self.lr0net, log_every=10, data_folder=self.data_folder,
             load_from_saved=self.load_from_saved, dnm=self.dnm, distance_fn=self.distance_fn,
             last_layer_only=self.last_layer_only, loaded_from_psvi=self.loaded_from_psvi,
-            eps_source=self.eps_source)
+            eps_source=self.eps_source, clustering=self.clustering)
         select_method.select_data()
         self.chosen_dataset = select_method.chosen_dataset
         self.wt_index = select_method.wt_index
@@ -1078,10 +1080,11 @@ def run_selection_with_mfvi(x=None, y=None, xt=None, yt=None, mc_samples=4, data
                             dnm=None, init_sd=None, mfvi_selection_method="kmeans",
                             pretrain_epochs=5, data_folder=None, load_from_saved=False,
                             distance_fn="euclidean", last_layer_only=False,
-                            loaded_from_psvi=True, eps_source=None, **kwargs):
+                            loaded_from_psvi=True, eps_source=None, clustering=None, **kwargs):
     """Pretrain by MFVI, score every training row, keep the top rows per class,
     train MFVI on that weighted subset (baselines.py:1855-1952).  Returns
-    {accs, nlls, times, elbos, csizes, wt_index}."""
+    {accs, nlls, times, elbos, csizes, wt_index}.  clustering="hip" opens the
+    k-means methods on psvi_kmeans (CoresetSelect); None refuses them."""
     if mfvi_selection_method == "incremental":
         raise NotImplementedError('mfvi_selection_method "incremental" starts from a k-means '
                                   "selection (sklearn), which is not on the HIP path")
@@ -1094,6 +1097,6 @@ def run_selection_with_mfvi(x=None, y=None, xt=None, yt=None, mc_samples=4, data
         pretrain_epochs=pretrain_epochs, data_folder=data_folder,
         load_from_saved=load_from_saved, distance_fn=distance_fn,
         last_layer_only=last_layer_only, loaded_from_psvi=loaded_from_psvi,
-        eps_source=eps_source)
+        eps_source=eps_source, clustering=clustering)
     mfvi_select.select_data()
     return mfvi_select.evaluate_coreset()

@@ -1,5 +1,5 @@
-"""Data selection by predictive scores (the reference's psvi/inference/utils.py:
-221-452, 616-787, 941-1113, 1419-1607) on the HIP library:
+"""Data selection by predictive scores and by k-means clusters (the reference's
+psvi/inference/utils.py: 221-552, 616-1265, 1381-1607) on the HIP library:
 
   MeanFieldVI      utils.py:221-452    MFVI pretraining on the training set, with forgetting events
   WeightedSubset   utils.py:616-626    a Subset whose items carry (idx, data, target, weight)
@@ -8,6 +8,10 @@
   ScoreSelection   utils.py:941-1084   the top rows per class by a predictive score
   ScoreCalculator  utils.py:1088-1113  the three scores of a probability matrix (torch)
   CoresetSelect    utils.py:1419-1607  picks the selection method and runs it
+  KmeansCluster    utils.py:455-552    k-means per class (or over all rows), points per cluster
+  KmeansSelection  utils.py:789-938    rows picked at random inside k-means clusters
+  KmeansScoreSelection      utils.py:1116-1265  rows picked inside clusters by their scores
+  WeightedKmeansSelection   utils.py:1381-1416  k-means rows weighted by their entropy score
 
 The training half is ``_MFVIStepper`` (psvi_elbo_grad + torch-Adam); every
 predictive pass is ONE psvi_predict_scores launch (psvi.runtime.predict_scores):
@@ -40,10 +44,28 @@ Divergences (DESIGN §4 "MFVI selection", §9): ``loaded=True`` reads
 and computes the scores otherwise; ``"el2n"`` is ``_el2n_score`` of the one
 pretrained net (the reference averages ten per-seed files nothing writes); a
 ``data_folder`` / ``data_path`` of None skips the score and checkpoint files;
-kmeans, kmeans_gradient, submodular, scored_kmeans_*, weighted_kmeans (sklearn
-/ faiss / the submodular package), architecture="lenet" and log_pseudodata
-raise NotImplementedError.  ``scored_random_*`` falls out of ScoreSelection
-(RandomScoreSelection) and is ported.
+kmeans_gradient, submodular (faiss / the submodular package),
+architecture="lenet" and log_pseudodata raise NotImplementedError.
+``scored_random_*`` falls out of ScoreSelection (RandomScoreSelection) and is
+ported.
+K-means (DESIGN §4 "K-means selection"): the reference clusters with sklearn on
+the CPU; here every clustering is one ``psvi.runtime.kmeans`` call
+(psvi_kmeans: Philox k-means++ with one candidate per centre, fp64 Lloyd,
+empty clusters kept), so the clusters are a k-means solution, not sklearn's.
+That is why ``CoresetSelect(clustering=None)`` still refuses kmeans,
+scored_kmeans_* and weighted_kmeans as before, and ``clustering="hip"`` opens
+them.  Raw rows only (``embedding_flag=False``): the LeNet embeddings stay
+refused with the architecture.  ``loaded=True`` reads
+``embedding_{dnm}_{seed}.csv`` with numpy when the file exists and uses the
+dataset's rows otherwise.  ``_set_num_clusters`` raises ValueError where the
+reference returns None (``multiple_pts`` with a num_pseudo outside {30, 50,
+80, 100}).  The reference's WeightedKmeansSelection cannot run (it calls
+``get_arbitrary_pts()`` without its argument and builds the subset from
+``self.p``): ported with ``total_pts=self.num_pseudo`` and
+``indices=self.core_idc``; its weights are normalised to sum to n_train like
+every other selection's (the reference's factor makes them sum to n_train /
+n_coreset).  The picks inside clusters stay on numpy's global
+generator, as in the reference.
 Optional hook: ``eps_source(n)`` supplies every draw of n floats (a training
 step's or one predictive minibatch's noise, in the reference's order).
 """
@@ -61,11 +83,15 @@ from torch.utils.data import DataLoader, Subset
 from ..models import categorical_fn
 
 __all__ = ["MeanFieldVI", "WeightedSubset", "Selection", "RandomSelection", "ScoreSelection",
-           "RandomScoreSelection", "ScoreCalculator", "CoresetSelect"]
+           "RandomScoreSelection", "ScoreCalculator", "CoresetSelect", "KmeansCluster",
+           "KmeansSelection", "KmeansScoreSelection", "WeightedKmeansSelection",
+           "sample_multinomial"]
 
 _NO_KMEANS = ("kmeans", "kmeans_gradient", "submodular", "weighted_kmeans",
               "scored_kmeans_el2n", "scored_kmeans_forgetting", "scored_kmeans_entropy",
               "scored_kmeans_least_confidence")
+# what clustering="hip" opens: the methods whose only missing piece was k-means
+_HIP_KMEANS = tuple(m for m in _NO_KMEANS if m not in ("kmeans_gradient", "submodular"))
 
 
 def _B():
@@ -399,6 +425,211 @@ class RandomScoreSelection(ScoreSelection):
         return self._top_per_class(self._get_uncertainty_score(), num_scored_pts)
 
 
+class KmeansCluster:
+    """K-means of the rows, per class (balanced) or over all of them
+    (utils.py:455-552), each clustering one psvi.runtime.kmeans call: max_iter
+    300 and tol = 1e-4 mean_f var_i(x_if) (sklearn's defaults and its tol
+    rule), the Philox stream (seed, 0) advanced by the words each call used."""
+
+    def __init__(self, x, y, num_classes=2, balance=True, seed=None, dist="euclidean"):
+        valid_dist = ["cosine", "euclidean"]
+        if dist not in valid_dist:
+            raise ValueError(f"{dist} is not one ov valid dist: {valid_dist}")
+        self.x, self.y = x, y
+        self.balance, self.num_classes, self.dist = balance, num_classes, dist
+        self.kmeans_dict = []
+        self.cluster_centers = []
+        self.seed = int(time.time()) if seed is None else seed
+
+    def set_num_clusters(self, num_clusters):
+        self.num_clusters = num_clusters
+        self.pts_per_class = max(int(np.floor(num_clusters / self.num_classes)), 2)
+
+    def run_kmeans(self):
+        if self.balance:
+            self.run_kmeans_balanced()
+        else:
+            self.run_kmeans_unbalanced()
+
+    def _rows(self):
+        """The rows as (n, D) float32 (3-d data flattened), unit L2 rows under
+        the cosine distance (a zero row stays zero), on the HIP device."""
+        x = torch.as_tensor(self.x)
+        x = x.reshape(x.shape[0], -1).to(torch.float32)
+        if torch.cuda.is_available():
+            x = x.to("cuda")
+        if self.dist == "cosine":
+            norm = torch.linalg.vector_norm(x, dim=1, keepdim=True)
+            x = x / torch.where(norm > 0, norm, torch.ones_like(norm))
+        return x.contiguous()
+
+    def _cluster(self, rows, indices, K):
+        from .. import runtime
+
+        tol = 1e-4 * float(rows.double().var(dim=0, unbiased=False).mean())
+        out = runtime.kmeans(rows, K, seed=self.seed, offset=self._offset, max_iter=300, tol=tol)
+        self._offset += out["consumed"]
+        this_kmeans_dict = {}
+        for counter, label in enumerate(torch.as_tensor(out["labels"]).cpu().tolist()):
+            this_kmeans_dict.setdefault(label, []).append(int(indices[counter]))
+        self.kmeans_dict.append(this_kmeans_dict)
+        self.cluster_centers.append(torch.as_tensor(out["centres"]).cpu().numpy())
+
+    def run_kmeans_balanced(self):
+        self.kmeans_dict, self.cluster_centers, self._offset = [], [], 0
+        x, y = self._rows(), np.asarray(torch.as_tensor(self.y).int())
+        for class_index in range(self.num_classes):
+            indices = np.where(y == class_index)[0]
+            sel = torch.as_tensor(indices, device=x.device)
+            self._cluster(x[sel].contiguous(), indices, self.pts_per_class)
+
+    def run_kmeans_unbalanced(self):
+        self.kmeans_dict, self.cluster_centers, self._offset = [], [], 0
+        x = self._rows()
+        self._cluster(x, np.arange(x.shape[0]), self.num_clusters)
+
+    def get_arbitrary_pts(self, total_pts):
+        """total_pts // num_clusters rows from every non-empty cluster, the
+        remainder on the last, by np.random.choice."""
+        pts_per_cluster = [total_pts // self.num_clusters] * self.num_clusters
+        pts_per_cluster[-1] = total_pts - sum(pts_per_cluster[:-1])
+        core_idcs, counter = [], 0
+        for this_kmeans_dict in self.kmeans_dict:
+            for k in this_kmeans_dict.keys():
+                if len(this_kmeans_dict[k]) > 0:
+                    num_pts = pts_per_cluster[counter]
+                    counter += 1
+                    core_idcs = core_idcs + list(
+                        np.random.choice(this_kmeans_dict[k], num_pts, replace=False))
+        return [int(i) for i in core_idcs]
+
+
+def sample_multinomial(pval, k):
+    """The k entries drawn most often among 2 N multinomial draws (utils.py:732-744)."""
+    pval = np.array(pval) if isinstance(pval, list) else pval
+    N = pval.shape[0]
+    try:
+        samples = np.random.multinomial(2 * N, pval, size=1)[0]
+        return np.argsort(samples)[-k:]
+    except Exception:
+        return np.random.choice(a=N, size=k, replace=False)
+
+
+def _kmeans_num_clusters(sel):
+    if not sel.multiple_pts:
+        return sel.num_pseudo
+    table = {30: 30, 50: 50, 80: 20, 100: 20}
+    if sel.num_pseudo not in table:
+        raise ValueError(f"multiple_pts=True has cluster counts for num_pseudo in {sorted(table)} "
+                         f"only (got {sel.num_pseudo}): the reference returns None there")
+    return table[sel.num_pseudo]
+
+
+def _kmeans_rows(sel):
+    """The rows to cluster: embedding_{dnm}_{seed}.csv when ``loaded`` and the
+    file exists, else the dataset's own rows."""
+    if sel.embedding_flag:
+        raise NotImplementedError("embedding_flag=True (the LeNet embeddings) is not on the HIP path")
+    if sel.loaded and sel.data_folder is not None:
+        fname = os.path.join(sel.data_folder, f"embedding_{sel.dnm}_{sel.seed}.csv")
+        if os.path.exists(fname):
+            return torch.from_numpy(np.atleast_2d(np.loadtxt(fname, delimiter=",")))
+    return _rows(sel.train_dataset)[0]
+
+
+def _run_kmeans(sel):
+    cluster = KmeansCluster(x=_kmeans_rows(sel), y=torch.as_tensor(sel.train_dataset.targets),
+                            num_classes=sel.nc, seed=sel.seed, dist=sel.dist)
+    cluster.set_num_clusters(sel._set_num_clusters())
+    cluster.run_kmeans()
+    return cluster
+
+
+class KmeansSelection(Selection):
+    """num_pseudo rows picked at random inside the k-means clusters of every
+    class (utils.py:789-938).  No pretraining: the raw rows are clustered."""
+
+    def __init__(self, train_dataset, num_pseudo, nc, seed, forgetting_flag=False,
+                 embedding_flag=False, dist="euclidean", data_folder=None, dnm="MNIST",
+                 multiple_pts=True, loaded=True):
+        super().__init__(train_dataset, num_pseudo, nc, seed, forgetting_flag)
+        self.embedding_flag, self.dist = embedding_flag, dist
+        self.data_folder, self.dnm = data_folder, dnm
+        self.multiple_pts, self.loaded = multiple_pts, loaded
+
+    def select(self):
+        self.kmeans_cluster = _run_kmeans(self)
+        return self.kmeans_cluster.get_arbitrary_pts(self.num_pseudo)
+
+    def _set_num_clusters(self):
+        return _kmeans_num_clusters(self)
+
+    def pretrain(self, *args, **kwargs):
+        pass
+
+
+class KmeansScoreSelection(ScoreSelection):
+    """int(num_pseudo / clusters) rows per k-means cluster, drawn by their
+    predictive scores (utils.py:1116-1265): in proportion to score + alpha
+    (choose_difficult) or to 1 / (score + alpha + 1e-20)."""
+
+    def __init__(self, train_dataset, num_pseudo, nc, seed, forgetting_flag=False,
+                 score_type="least_confidence", embedding_flag=False, dist="euclidean",
+                 data_folder=None, dnm="MNIST", multiple_pts=True, alpha=0, loaded=False,
+                 choose_difficult=True):
+        super().__init__(train_dataset, num_pseudo, nc, seed, forgetting_flag, score_type,
+                         data_folder, dnm, loaded)
+        self.embedding_flag, self.dist, self.alpha = embedding_flag, dist, alpha
+        self.multiple_pts, self.choose_difficult = multiple_pts, choose_difficult
+
+    def select(self):
+        self.score_arr = self._scores()
+        self.kmeans_cluster = _run_kmeans(self)
+        return self._combine_kmeans_score()
+
+    def _set_num_clusters(self):
+        return _kmeans_num_clusters(self)
+
+    def _combine_kmeans_score(self):
+        pts_per_cluster = int(self.num_pseudo / self._set_num_clusters())
+        score = np.asarray(self.score_arr, dtype=np.float64)
+        core_idcs = []
+        for this_kmeans_dict in self.kmeans_cluster.kmeans_dict:
+            for k in this_kmeans_dict.keys():
+                indices = this_kmeans_dict[k]
+                if len(indices) > 0:
+                    sub = score[indices] + self.alpha
+                    if not self.choose_difficult:
+                        sub = 1.0 / (sub + 1e-20)
+                    chosen = sample_multinomial(pval=sub / sub.sum(), k=pts_per_cluster)
+                    core_idcs = core_idcs + [indices[int(j)] for j in chosen]
+        return core_idcs
+
+
+class WeightedKmeansSelection(KmeansScoreSelection):
+    """KmeansSelection's rows, weighted in proportion to their scores
+    (utils.py:1381-1416, with the repairs of the module docstring)."""
+
+    def __init__(self, train_dataset, num_pseudo, nc, seed, forgetting_flag=False,
+                 score_type="entropy", embedding_flag=False, dist="euclidean"):
+        super().__init__(train_dataset, num_pseudo, nc, seed, forgetting_flag, score_type,
+                         embedding_flag, dist)
+
+    def select(self):
+        self.kmeans_cluster = _run_kmeans(self)
+        return self.kmeans_cluster.get_arbitrary_pts(total_pts=self.num_pseudo)
+
+    def get_weighted_subset(self, wt_vec=None):
+        if len(self.core_idc) == 0:
+            self.core_idc = self.select()
+        n_coreset, n_train = len(self.core_idc), len(self.train_dataset)
+        wt_vec_init = torch.as_tensor(self._get_uncertainty_score())[self.core_idc]
+        self.wt_vec = (n_train / wt_vec_init.sum()) * wt_vec_init
+        self.chosen_dataset = WeightedSubset(dataset=self.train_dataset, indices=self.core_idc,
+                                             weights=self.wt_vec)
+        return self.chosen_dataset
+
+
 class ScoreCalculator:
     def __init__(self, outputs_prob, target, nc=10):
         self.outputs_prob = outputs_prob
@@ -423,7 +654,10 @@ class CoresetSelect:
                  score_method="kmeans", pretrain_epochs=5, data_folder=None,
                  load_from_saved=False, dnm=None, distance_fn="euclidean", last_layer_only=False,
                  multiple_pts_per_cluster=True, loaded_from_psvi=True, alpha_dirichlet=0,
-                 choose_difficult=True, eps_source=None):
+                 choose_difficult=True, eps_source=None, clustering=None):
+        if clustering not in (None, "hip"):
+            raise ValueError(f'clustering is None or "hip" (got {clustering!r})')
+        self.clustering = clustering
         self.architecture, self.score_method = architecture, score_method
         self.train_dataset, self.test_dataset = train_dataset, test_dataset
         self.num_pseudo, self.seed, self.nc, self.D, self.n_hidden = num_pseudo, seed, nc, D, n_hidden
@@ -440,11 +674,25 @@ class CoresetSelect:
         _refuse_net(self.architecture)
         common = dict(train_dataset=self.train_dataset, num_pseudo=self.num_pseudo, nc=self.nc,
                       seed=self.seed)
-        if self.score_method in _NO_KMEANS:
+        if self.score_method in _NO_KMEANS and not (self.clustering == "hip"
+                                                    and self.score_method in _HIP_KMEANS):
             raise NotImplementedError(
                 f"score_method {self.score_method!r} needs k-means clustering (sklearn / faiss) "
                 "or the submodular package, which are not on the HIP path")
-        if self.score_method == "random":
+        kmeans_args = dict(embedding_flag=False, dist=self.distance_fn)
+        if self.score_method == "kmeans":
+            select_method = KmeansSelection(**common, **kmeans_args, data_folder=self.data_folder,
+                                            dnm=self.dnm, multiple_pts=self.multiple_pts_per_cluster,
+                                            loaded=self.loaded_from_psvi)
+        elif self.score_method.startswith("scored_kmeans_"):
+            select_method = KmeansScoreSelection(
+                **common, **kmeans_args, score_type=self.score_method[14:],
+                data_folder=self.data_folder, dnm=self.dnm,
+                multiple_pts=self.multiple_pts_per_cluster, loaded=self.loaded_from_psvi,
+                alpha=self.alpha_dirichlet, choose_difficult=self.choose_difficult)
+        elif self.score_method == "weighted_kmeans":
+            select_method = WeightedKmeansSelection(**common, **kmeans_args, score_type="entropy")
+        elif self.score_method == "random":
             select_method = RandomSelection(**common)
         elif self.score_method in ["el2n", "least_confidence", "entropy", "forgetting"]:
             select_method = ScoreSelection(**common, score_type=self.score_method,

@@ -155,6 +155,27 @@ class CoresetDrawReq(ctypes.Structure):
     ]
 
 
+KMEANS_MAX_K = 128
+KMEANS_MAX_D = 4096
+KMEANS_MAX_N = 1 << 24
+
+
+class KmeansReq(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("centres_in", ctypes.c_void_p),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+        ("max_iter", ctypes.c_int32),
+        ("tol", ctypes.c_double),
+        ("centres_out", ctypes.c_void_p), ("labels_out", ctypes.c_void_p),
+        ("counts_out", ctypes.c_void_p), ("seeds_out", ctypes.c_void_p),
+        ("inertia_out", ctypes.c_void_p), ("n_iter_out", ctypes.c_void_p),
+        ("status_out", ctypes.c_void_p),
+        ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
 class PredictScoresReq(ctypes.Structure):
     _fields_ = [
         ("plan", ctypes.c_void_p),
@@ -231,6 +252,8 @@ SIGNATURES = {
     "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),
     "psvi_coreset_draw": (_I32, [ctypes.POINTER(CoresetDrawReq), _P]),
     "psvi_predict_scores": (_I32, [ctypes.POINTER(PredictScoresReq), _P]),
+    "psvi_kmeans": (_I32, [ctypes.POINTER(KmeansReq), _P]),
+    "psvi_kmeans_query": (_I32, [_I32, _I32, _I32, ctypes.POINTER(_I64)]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_partial": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "psvi_hvp_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _SZ, _P]),

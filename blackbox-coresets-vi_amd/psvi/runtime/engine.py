@@ -1038,6 +1038,64 @@ def coreset_draw(w, n, replacement, seed, offset, rows=None, targets=None):
     return idx, rows_out, targets_out, 4 * (((n if replacement else M) + 3) // 4)
 
 
+KMEANS_STATUS = {1: "a row or a given centre is not finite",
+                 2: "fewer than K distinct rows: every remaining distance to the chosen centres "
+                    "is zero"}
+KMEANS_WS_CAP = 256 << 20    # the wrapper's workspace: the one-pass sums up to this many bytes
+
+
+def kmeans_query(N, D, K):
+    """(one-pass ws bytes, least ws bytes, columns of an LDS tile, assignment
+    workgroups) of psvi_kmeans at a shape; needs no device."""
+    out = (ctypes.c_int64 * 4)()
+    check(_lib.load().psvi_kmeans_query(int(N), int(D), int(K), out), "psvi_kmeans_query")
+    return tuple(int(v) for v in out)
+
+
+def kmeans(x, K, seed=0, offset=0, centres=None, max_iter=300, tol=0.0, ws_bytes=None):
+    """K-means of the rows x (N, D float32 on the device) in fp64 (psvi_kmeans):
+    k-means++ seeding with one candidate per centre on the Philox stream
+    (seed, offset) -- or the given initial ``centres`` (K, D float64) -- then
+    Lloyd iterations until no label changes, the summed squared centre shift
+    is <= tol, or max_iter updates.  An empty cluster keeps its centre.
+    ``ws_bytes`` picks the workspace (default: the one-pass sums when they
+    take at most KMEANS_WS_CAP bytes, else that many bytes of partials).
+    Returns a dict of device tensors ``centres`` (K, D float64), ``labels``
+    (N int32), ``counts`` (K int32), ``seeds`` (K int32: the rows the seeding
+    chose, -1 with given centres), and host numbers ``inertia``, ``n_iter``,
+    ``consumed`` (the words of the stream used: 4 K, 0 with given centres --
+    add it to offset for the next call).  Reads the status once on the host;
+    raises ValueError naming the condition when the rows admit no clustering."""
+    if x is None or x.dim() != 2:
+        raise ValueError("x must be (N, D)")
+    N, D, K = int(x.shape[0]), int(x.shape[1]), int(K)
+    _need(x, "x", N * D)
+    full, least, _, _ = kmeans_query(N, D, K)
+    if ws_bytes is None:
+        ws_bytes = min(full, max(least, KMEANS_WS_CAP))
+    dev = x.device
+    if centres is not None:
+        _need(centres, "centres", K * D, torch.float64)
+    out = dict(centres=torch.empty(K, D, dtype=torch.float64, device=dev),
+               labels=torch.empty(N, dtype=torch.int32, device=dev),
+               counts=torch.empty(K, dtype=torch.int32, device=dev),
+               seeds=torch.empty(K, dtype=torch.int32, device=dev))
+    inertia = torch.empty(1, dtype=torch.float64, device=dev)
+    small = torch.empty(2, dtype=torch.int32, device=dev)     # n_iter, status
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+    req = _lib.KmeansReq(
+        _ptr(x), N, D, K, _ptr(centres), int(seed) & (2**64 - 1), int(offset), int(max_iter),
+        float(tol), _ptr(out["centres"]), _ptr(out["labels"]), _ptr(out["counts"]),
+        _ptr(out["seeds"]), _ptr(inertia), _ptr(small), _ptr(small[1:]), _ptr(ws), int(ws_bytes))
+    check(_lib.load().psvi_kmeans(ctypes.byref(req), _stream()), "psvi_kmeans")
+    n_iter, st = small.tolist()
+    if st:
+        raise ValueError(f"kmeans: {KMEANS_STATUS.get(st, f'status {st}')}")
+    out.update(inertia=float(inertia.item()), n_iter=int(n_iter),
+               consumed=0 if centres is not None else 4 * K)
+    return out
+
+
 def randn_(out, seed, offset=0):
     """Fill a float32 device tensor with N(0,1) (Philox4x32-10 + Box-Muller)."""
     _need(out, "out", None)

@@ -746,6 +746,93 @@ typedef struct psvi_coreset_draw_req {
 } psvi_coreset_draw_req;
 int psvi_coreset_draw(const psvi_coreset_draw_req* req, void* stream);
 
+/* ---- k-means clustering (the k-means data-selection baselines) -------------
+ * The clustering behind KmeansCluster (reference psvi/inference/utils.py:
+ * 455-552, which calls sklearn's KMeans on the CPU): K clusters of the N rows
+ * x ([N][D] device fp32), seeded from the library's Philox stream so that a
+ * selection stays a function of its seed, then Lloyd iterations.
+ * Arithmetic: every number that decides a label or a seed is fp64.  x is
+ * widened exactly, the centres live in fp64, d(i,k) = sum_f (x_if - c_kf)^2
+ * (the differences squared and added, not the expanded form).  A result
+ * differs from a float64 restatement of these rules by the rounding of the
+ * order of fp64 sums only; with a relative margin between the best and the
+ * second-best centre of every row far above D 2^-53 the labels are equal.
+ * Initial centres: centres_in ([K][D] device fp64) when given; seeds_out is
+ * then all -1 and no word of the stream is used.  Otherwise k-means++ with
+ * one candidate per centre.  Word j of the stream (seed, offset) and its
+ * uniform U_j = (word_j + 0.5) 2^-32 are those of psvi_coreset_draw; centre j
+ * takes word 4 j (one quad per centre: the call consumes 4 K words).
+ *   centre 0 = row floor(U_0 N), clamped to N - 1;
+ *   centre j >= 1: m_i = min over the chosen centres of d(i, .), C = the
+ *   inclusive fp64 prefix sum of m in index order, t = U_{4j} C_{N-1}, the
+ *   smallest i with C_i > t, clamped to the last i with m_i > 0.  A chosen
+ *   row has m_i = 0 and repeats its predecessor's prefix value, so it is
+ *   never chosen again.  The prefix is summed in runs of 64 consecutive rows
+ *   whose totals are added in run order (C_i = the runs before + within the
+ *   run): the fixed association of PSVI_DRAW_REPLACE, equal to the sequential
+ *   sum when the sums are exact.
+ * Lloyd: iteration t = 0, 1, ... assigns label_i = argmin_k d(i,k) against
+ * the centres C_t, the lowest k among equal distances.
+ *   If t == max_iter, or t > 0 and the summed squared shift
+ *   sum_kf (C_t - C_{t-1})^2 <= tol, this was the final assignment: stop,
+ *   n_iter = t.
+ *   Else if t > 0 and no label changed: stop, n_iter = t + 1 (the update
+ *   would reproduce C_t bit for bit and is not made; the count is
+ *   sklearn's n_iter_).
+ *   Else C_{t+1,k} = (the sum of cluster k's rows) / its count; a cluster
+ *   without rows keeps its centre (sklearn's relocation is not ported).
+ * max_iter == 0 is the assignment against the initial centres alone.
+ * Outputs (device): centres_out [K][D] fp64 (also the working centres),
+ * labels_out [N], counts_out [K] (of labels_out), seeds_out [K] (nullable),
+ * inertia_out [1] = sum_i d(i, label_i) against centres_out, n_iter_out [1],
+ * status_out [1]: 0 ok; 1 a non-finite input (a row or a given centre);
+ * 2 fewer than K distinct rows reachable by the seeding (all remaining
+ * distances zero).  On a non-zero status every label is -1, counts_out,
+ * inertia_out and n_iter_out are 0, centres_out is unspecified and seeds_out
+ * holds the rows chosen before the failure, then -1.  The call returns 0 then:
+ * the status is the caller's to read.
+ * Determinism: no atomic on anything that decides a label, a centre, the
+ * inertia or a seed.  Cluster sums are per-workgroup partials of consecutive
+ * rows, added in row order and combined in workgroup order; the inertia meets
+ * in a fixed tree.  Two calls with the same arguments (ws_bytes included) are
+ * bitwise equal.
+ * Launches: ordinary ones only -- no workgroup waits for another.  The
+ * iterations are enqueued 16 at a time; a device word `done` makes the
+ * launches behind the stopping one return at once, and the call reads it once
+ * per 16 iterations (the call synchronises the stream then, and returns with
+ * the last launch enqueued).  Centres and rows are staged in LDS in tiles of
+ * out[2] columns; D above that is tiled.
+ * psvi_kmeans_query(N, D, K, out), no device needed: out[0] = the ws bytes
+ * from which the cluster sums are formed in the assignment launch (one
+ * partial per workgroup, x read from memory once per iteration), out[1] = the
+ * least ws bytes a call takes (one partial), out[2] = the columns of a tile,
+ * out[3] = the assignment workgroups.  Between out[1] and out[0] the sums run
+ * as a second launch over as many row chunks as the workspace holds partials;
+ * the two forms differ by the rounding of the order of sums only.
+ * PSVI_EINVAL: a NULL request, x or non-nullable output; N < 1, D < 1, K < 1,
+ * K > N; offset % 4 != 0; max_iter < 0; tol negative or not finite.
+ * PSVI_EUNSUP: K > 128, D > 4096, N > 2^24.  PSVI_ENOSPC: ws NULL or
+ * ws_bytes < out[1]. */
+typedef struct psvi_kmeans_req {
+    const float* x;            /* [N][D] rows, device fp32 */
+    int32_t N, D, K;
+    const double* centres_in;  /* [K][D] nullable: given initial centres */
+    uint64_t seed, offset;     /* Philox stream of the seeding when centres_in == NULL; offset % 4 == 0 */
+    int32_t max_iter;          /* >= 0 centre updates */
+    double tol;                /* >= 0: stop when the summed squared centre shift <= tol */
+    double* centres_out;       /* [K][D] */
+    int32_t* labels_out;       /* [N] */
+    int32_t* counts_out;       /* [K] */
+    int32_t* seeds_out;        /* [K] row indices the seeding chose (nullable; -1s with centres_in) */
+    double* inertia_out;       /* [1] */
+    int32_t* n_iter_out;       /* [1] */
+    int32_t* status_out;       /* [1] */
+    void* ws;
+    size_t ws_bytes;
+} psvi_kmeans_req;
+int psvi_kmeans(const psvi_kmeans_req* req, void* stream);
+int psvi_kmeans_query(int32_t N, int32_t D, int32_t K, int64_t* out);
+
 /* ---- MFVI regression baselines (fit, run_mfvi_regressor) -------------------
  * The whole fit of a mean-field Gaussian-likelihood MLP on a FIXED batch (fit,
  * psvi/inference/baselines.py:1283-1346: every step takes next(iter(loader)) of
