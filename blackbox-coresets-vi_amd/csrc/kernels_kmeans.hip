@@ -42,30 +42,27 @@ struct KmWs {
     double* inertia;
     int* cnt;       // [G][K]
     double* shift[2];  // [cy][K]: update t writes shift[t & 1], test t + 1 reads it
-    double* part;   // [P][K][D]
+    double* part;   // [P][K][D]: the rest of the workspace
 };
 
-KmWs km_carve(void* base, const KmeansShape& s, int64_t N, int K) {
-    char* p = static_cast<char*>(base);
-    auto take = [&](size_t bytes) {
-        char* q = p;
-        p += align256(bytes);
-        return q;
-    };
+// s: the grids of kmeans_shape; fixed: the bytes before the partials (base
+// nullptr: sizes only)
+KmWs km_carve(void* base, const KmeansShape& s, int64_t N, int K, size_t* fixed = nullptr) {
+    WsCarve c(base);
     KmWs w;
-    w.state = (KmState*)take(256);
-    w.m = (double*)take(sizeof(double) * (size_t)N);
-    w.runT = (double*)take(sizeof(double) * (size_t)s.nruns);
-    w.runB = (double*)take(sizeof(double) * (size_t)s.nruns);
-    w.runLast = (int*)take(sizeof(int) * (size_t)s.nruns);
-    w.runBad = (int*)take(sizeof(int) * (size_t)s.nruns);
-    w.changed = (int*)take(sizeof(int) * (size_t)s.G);
-    w.bad = (int*)take(sizeof(int) * (size_t)s.G);
-    w.inertia = (double*)take(sizeof(double) * (size_t)s.G);
-    w.cnt = (int*)take(sizeof(int) * (size_t)s.G * K);
-    w.shift[0] = (double*)take(sizeof(double) * (size_t)K * s.cy);
-    w.shift[1] = (double*)take(sizeof(double) * (size_t)K * s.cy);
-    w.part = (double*)p;
+    w.state = c.take<KmState>(1);                  // the state words
+    w.m = c.take<double>((size_t)N);               // the seeding's distances
+    w.runT = c.take<double>((size_t)s.nruns);      // run totals
+    w.runB = c.take<double>((size_t)s.nruns);      // run prefix
+    w.runLast = c.take<int>((size_t)s.nruns);      // last positive row
+    w.runBad = c.take<int>((size_t)s.nruns);       // non-finite flag
+    w.changed = c.take<int>((size_t)s.G);
+    w.bad = c.take<int>((size_t)s.G);
+    w.inertia = c.take<double>((size_t)s.G);
+    w.cnt = c.take<int>((size_t)s.G * K);
+    for (double*& sh : w.shift) sh = c.take<double>((size_t)K * s.cy);  // of even / odd updates
+    w.part = c.take<double>(0);
+    if (fixed) *fixed = c.bytes();
     return w;
 }
 
@@ -474,6 +471,22 @@ km_assign_fn km_assign_for(int K) {
 }
 
 }  // namespace
+
+KmeansShape kmeans_shape(int64_t N, int D, int K) {
+    KmeansShape s;
+    s.DT = (int)std::min<size_t>((size_t)D, (kKmLds - 256) / ((size_t)K * 8 + 4 * kKmRows));
+    s.XS = s.DT | 1;
+    s.tiles = (int)((N + kKmRows - 1) / kKmRows);
+    s.tpb = (s.tiles + kKmMaxGrid - 1) / kKmMaxGrid;
+    s.G = (s.tiles + s.tpb - 1) / s.tpb;
+    s.nruns = s.tiles;
+    s.cy = (D + kKmThreads - 1) / kKmThreads;
+    s.part = align256(sizeof(double) * (size_t)K * D);
+    km_carve(nullptr, s, N, K, &s.fixed);
+    s.min_bytes = s.fixed + s.part;
+    s.full_bytes = s.fixed + (size_t)s.G * s.part;
+    return s;
+}
 
 hipError_t launch_kmeans(const Kmeans& r, hipStream_t st) {
     const KmeansShape s = kmeans_shape(r.N, r.D, r.K);

@@ -1493,32 +1493,26 @@ LenetWs lenet_ws(const psvi_plan& p, void* base) {
     const int64_t S = p.s_cnt[p.rank], M = p.d.M;
     LenetWs w{};
     w.nchunk = lenet_nchunk(p);
-    size_t off = 0;
-    char* b = (char*)base;
-    auto take = [&](size_t bytes) -> void* {
-        void* r = b ? (void*)(b + off) : nullptr;
-        off += (bytes + 255) & ~size_t(255);
-        return r;
-    };
-    w.wsamp = (float*)take(sizeof(float) * S * p.n_tot);
-    w.dws = (float*)take(sizeof(float) * S * p.n_tot);
-    w.p1 = (float*)take(sizeof(float) * S * M * kP1);
-    w.r1 = (int8_t*)take(S * M * kP1);
-    w.x2 = (float*)take(sizeof(float) * S * M * kX2);
-    w.r2 = (int8_t*)take(S * M * kX2);
-    w.h1 = (float*)take(sizeof(float) * S * M * 120);
-    w.h2 = (float*)take(sizeof(float) * S * M * 84);
-    w.d = (float*)take(sizeof(float) * S * M * 10);
-    w.dh2 = (float*)take(sizeof(float) * S * M * 84);
-    w.dh1 = (float*)take(sizeof(float) * S * M * 120);
-    w.dx2 = (float*)take(sizeof(float) * S * M * kX2);
-    w.part = (float*)take(sizeof(float) * S * w.nchunk * kNConv);
+    WsCarve c(base);
+    w.wsamp = c.take<float>(S * p.n_tot);
+    w.dws = c.take<float>(S * p.n_tot);
+    w.p1 = c.take<float>(S * M * kP1);
+    w.r1 = c.take<int8_t>(S * M * kP1);
+    w.x2 = c.take<float>(S * M * kX2);
+    w.r2 = c.take<int8_t>(S * M * kX2);
+    w.h1 = c.take<float>(S * M * 120);
+    w.h2 = c.take<float>(S * M * 84);
+    w.d = c.take<float>(S * M * 10);
+    w.dh2 = c.take<float>(S * M * 84);
+    w.dh1 = c.take<float>(S * M * 120);
+    w.dx2 = c.take<float>(S * M * kX2);
+    w.part = c.take<float>(S * w.nchunk * kNConv);
     // MFMA backward: the routed d P1 and conv1's weight-gradient partials
     // (8 samples per workgroup, >= ~1024 workgroups)
-    w.g1 = (float*)take(sizeof(float) * S * M * kP1);
+    w.g1 = c.take<float>(S * M * kP1);
     w.nch1 = (int)std::max<int64_t>(1, std::min<int64_t>(M, 1024 / ((S + kW1S - 1) / kW1S)));
-    w.part1 = (float*)take(sizeof(float) * S * w.nch1 * 156);
-    w.bytes = off;
+    w.part1 = c.take<float>(S * w.nch1 * 156);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -1683,30 +1677,24 @@ hipError_t launch_lenet(const psvi_plan& p, const float* u, const int32_t* z, co
 LenetTanWs lenet_tan_ws(const psvi_plan& p, void* base) {
     const int64_t S = p.s_cnt[p.rank], M = p.d.M;
     LenetTanWs w{};
-    size_t off = 0;
-    char* b = (char*)base;
-    auto take = [&](size_t bytes) -> void* {
-        void* r = b ? (void*)(b + off) : nullptr;
-        off += (bytes + 255) & ~size_t(255);
-        return r;
-    };
-    w.nll = (double*)take(sizeof(double));
-    w.acc = (float*)take(sizeof(float) * 2 * p.n_tot);
-    w.wdot = (float*)take(sizeof(float) * S * p.n_tot);
-    w.gd = (float*)take(sizeof(float) * S * p.n_tot);
-    w.p1d = (float*)take(sizeof(float) * S * M * kP1);
-    w.x2d = (float*)take(sizeof(float) * S * M * kX2);
-    w.h1d = (float*)take(sizeof(float) * S * M * 120);
-    w.h2d = (float*)take(sizeof(float) * S * M * 84);
-    w.ld = (float*)take(sizeof(float) * S * M * 10);
-    w.prob = (float*)take(sizeof(float) * S * M * 10);
-    w.dh2d = (float*)take(sizeof(float) * S * M * 84);
-    w.dh1d = (float*)take(sizeof(float) * S * M * 120);
-    w.dx2d = (float*)take(sizeof(float) * S * M * kX2);
-    w.part = (float*)take(sizeof(float) * S * lenet_nchunk(p) * kNConv);
-    w.du = (float*)take(sizeof(float) * S * M * 784);
-    w.nlld = (float*)take(sizeof(float) * S * M);
-    w.bytes = off;
+    WsCarve c(base);
+    w.nll = c.take<double>(1);
+    w.acc = c.take<float>(2 * (size_t)p.n_tot);
+    w.wdot = c.take<float>(S * p.n_tot);
+    w.gd = c.take<float>(S * p.n_tot);
+    w.p1d = c.take<float>(S * M * kP1);
+    w.x2d = c.take<float>(S * M * kX2);
+    w.h1d = c.take<float>(S * M * 120);
+    w.h2d = c.take<float>(S * M * 84);
+    w.ld = c.take<float>(S * M * 10);
+    w.prob = c.take<float>(S * M * 10);
+    w.dh2d = c.take<float>(S * M * 84);
+    w.dh1d = c.take<float>(S * M * 120);
+    w.dx2d = c.take<float>(S * M * kX2);
+    w.part = c.take<float>(S * lenet_nchunk(p) * kNConv);
+    w.du = c.take<float>(S * M * 784);
+    w.nlld = c.take<float>(S * M);
+    w.bytes = c.bytes();
     return w;
 }
 

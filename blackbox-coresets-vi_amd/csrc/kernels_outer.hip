@@ -1,5 +1,5 @@
 // kernels_outer.hip -- the outer objective PSVI.psvi_elbo around the network
-// kernel's two outer passes (psvi_outer_elbo_grad, capi.cpp).
+// kernel's two outer passes (psvi_outer_elbo_grad, capi_outer.cpp).
 //
 // Reference (/root/reference):
 //   PSVI.psvi_elbo            psvi/inference/psvi_classes.py:445-486

@@ -1230,9 +1230,6 @@ int rop_rows(const psvi_plan& p) {
     return 0;
 }
 
-// two workgroups per sample while the samples alone leave CUs idle
-int rop_splits(const psvi_plan& p) { return (p.d.S < 256 && p.d.M > 1) ? 2 : 1; }
-
 static void rop_fill(const psvi_plan& p, RopArgs& a) {
     a.L = p.L;
     a.M = p.d.M;

@@ -2,12 +2,13 @@
 // layout, the sample and row shards, and the work lists of the full-cov
 // kernels (forward items, update chunks, the streaming run table, the K-split
 // and segmented-sample tables).  Launches nothing and calls no HIP API:
-// capi.cpp uploads the lists, tests/cpp/plan_tables_check.cpp checks them.
+// capi_plan.cpp uploads the lists, tests/cpp/plan_tables_check.cpp checks them.
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "psvi_internal.hpp"
+#include "workspace.hpp"
 
 namespace psvi {
 
@@ -473,7 +474,7 @@ int build_lenet_plan(psvi_plan& p, std::string& err) {
     shard_samples(p);
     for (int q = 0; q < p.world; ++q) p.rows_tot[q] = 0;
     p.acc_count = 2 * (int64_t)p.n_tot;
-    p.ws_bytes = align256(sizeof(float) * (size_t)p.acc_count);
+    p.ws_bytes = step_ws(p, nullptr).bytes;
     if (p.Peps > kMaxOff || (int64_t)p.s_cnt[p.rank] * p.d.M * kLenetRowFloats > kMaxOff * 4)
         return fail(err, PSVI_EUNSUP, "LeNet scratch beyond the supported size");
     return 0;
@@ -532,10 +533,8 @@ int build_plan(psvi_plan& p, std::string& err) {
     if (p.net_lds > 160 * 1024)
         return fail(err, PSVI_EUNSUP, "layer too wide for the per-sample LDS network kernel");
     if (!sizes_ok(p)) return fail(err, PSVI_EUNSUP, "buffers beyond 2^31 floats are not supported");
-    if (p.family != PSVI_FAMILY_FULLCOV) {
-        p.ws_bytes = align256(sizeof(float) * (size_t)p.acc_count);
-        return 0;
-    }
+    p.ws_bytes = step_ws(p, nullptr).bytes;
+    if (p.family != PSVI_FAMILY_FULLCOV) return 0;
     const int S = p.d.S;
     build_fwd_upd(p);
     // fusion needs band-aligned row blocks (rank row ranges start at 0) and
@@ -548,8 +547,6 @@ int build_plan(psvi_plan& p, std::string& err) {
     // the segmented sample at every S (x_0 of a loop, the HVP's tangent
     // sample, the sharded step): equal runs over 512 workgroups
     build_fseg(p);
-    const size_t xs = sizeof(float) * (size_t)S * p.rows_tot[p.rank];
-    p.ws_bytes = align256(xs) * 2 + 256;
     if (p.world == 1) layout_eps_planes(p);
     return 0;
 }

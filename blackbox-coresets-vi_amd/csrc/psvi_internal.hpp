@@ -10,6 +10,7 @@
 
 #include "block_reduce.hpp"
 #include "psvi_hip.h"
+#include "ws_carve.hpp"
 
 namespace psvi {
 
@@ -598,7 +599,6 @@ inline int plan_in_dim(const psvi_plan& p) {
 inline unsigned plan_nkl_mask(const psvi_plan& p) {
     return p.family == PSVI_FAMILY_LENET ? 0x1Cu : 0xFFu;
 }
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 // Plan building (plan_tables.cpp: host only, no HIP call): the layout, the
 // shards, the network geometry and every work list of a plan whose family, d,
 // world and rank are set.  Returns 0, or a PSVI_E* code with its message in err.
@@ -607,7 +607,7 @@ int build_plan(psvi_plan& p, std::string& err);
 size_t net_plan_geometry(psvi_plan& p);
 // A launch of `kernel` with up to `bytes` of dynamic LDS (above the 64 KiB a
 // launch gets unasked) on the current device: the opt-in is made once per
-// (kernel, device), whichever thread asks first (capi.cpp)
+// (kernel, device), whichever thread asks first (capi_plan.cpp)
 hipError_t allow_dynamic_lds(const void* kernel, size_t bytes);
 // the same for every network kernel (kernels_net.hip) and every R-op kernel
 // (kernels_rop.hip): at plan creation, so launch_net and launch_net_rop make
@@ -625,7 +625,7 @@ struct PlanDebug {
 extern PlanDebug g_plan_dbg;
 // psvi_debug_set / psvi_debug_set_ptr values read when a kernel is launched (and
 // by net_plan_geometry): A/B switches, ablation masks and stamp buffers, all 0 /
-// nullptr in production unless a default says otherwise (psvi_diag.h; capi.cpp)
+// nullptr in production unless a default says otherwise (psvi_diag.h; capi_plan.cpp)
 struct Diag {
     using Stamps = unsigned long long*;  // 16 slots per workgroup
     int net_ablation = 0;         // PSVI_DBG_NET_ABLATION, mask
@@ -892,28 +892,8 @@ struct KmeansShape {
     size_t fixed = 0; // bytes before the partials
     size_t min_bytes = 0, full_bytes = 0;  // one partial / G partials
 };
-inline KmeansShape kmeans_shape(int64_t N, int D, int K) {
-    KmeansShape s;
-    s.DT = (int)std::min<size_t>((size_t)D, (kKmLds - 256) / ((size_t)K * 8 + 4 * kKmRows));
-    s.XS = s.DT | 1;
-    s.tiles = (int)((N + kKmRows - 1) / kKmRows);
-    s.tpb = (s.tiles + kKmMaxGrid - 1) / kKmMaxGrid;
-    s.G = (s.tiles + s.tpb - 1) / s.tpb;
-    s.nruns = s.tiles;
-    s.cy = (D + kKmThreads - 1) / kKmThreads;
-    s.part = align256(sizeof(double) * (size_t)K * D);
-    s.fixed = 256                                              // the state words
-              + align256(sizeof(double) * (size_t)N)           // m: the seeding's distances
-              + 2 * align256(sizeof(double) * (size_t)s.nruns) // run totals, run prefix
-              + 2 * align256(sizeof(int) * (size_t)s.nruns)    // last positive row, non-finite flag
-              + 2 * align256(sizeof(int) * (size_t)s.G)        // changed, non-finite
-              + align256(sizeof(double) * (size_t)s.G)         // inertia
-              + align256(sizeof(int) * (size_t)s.G * K)        // counts
-              + 2 * align256(sizeof(double) * (size_t)K * s.cy);  // shift, of even / odd updates
-    s.min_bytes = s.fixed + s.part;
-    s.full_bytes = s.fixed + (size_t)s.G * s.part;
-    return s;
-}
+// (fixed: what the workspace's carve takes before the partials, kernels_kmeans.hip)
+KmeansShape kmeans_shape(int64_t N, int D, int K);
 struct Kmeans {
     const float* x = nullptr;  // [N][D]
     int N = 0, D = 0, K = 0;
@@ -1072,7 +1052,9 @@ hipError_t launch_cg_update(int64_t n, double* x, double* p, float* p32, const d
                             const double* state, hipStream_t st);
 // Hessian-vector products (kernels_rop.hip)
 int rop_rows(const psvi_plan& p);
-int rop_splits(const psvi_plan& p);  // row blocks per sample: G / G_dot slots
+// row blocks per sample (G / G_dot slots): two workgroups per sample while the
+// samples alone leave CUs idle
+inline int rop_splits(const psvi_plan& p) { return (p.d.S < 256 && p.d.M > 1) ? 2 : 1; }
 struct NetRop {
     const float* u = nullptr;
     Targets targets;

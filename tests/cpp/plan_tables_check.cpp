@@ -1,8 +1,11 @@
 // plan_tables_check.cpp -- stand-alone check of the work lists plan_tables.cpp
 // builds (no GPU use): every plan of a list of shapes is built on the host and
-// its tables are checked against what the kernels assume of them.  Built with
+// its tables are checked against what the kernels assume of them; every
+// workspace layout (workspace.hpp) is carved on a buffer of exactly the size it
+// reports and its regions are checked to lie inside, apart and aligned.  Built with
 // the host sanitizers by `make check-tables`; exit status 0 when all hold.
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <set>
@@ -11,6 +14,7 @@
 #include <vector>
 
 #include "psvi_internal.hpp"
+#include "workspace.hpp"
 
 using namespace psvi;
 
@@ -376,6 +380,124 @@ void check_upd(const psvi_plan& p) {
     CHECK(tiles == p.upd_tiles);
 }
 
+// ------------------------------------------------------- workspace layouts
+struct Buf {
+    char* p;
+    size_t n;
+    explicit Buf(size_t bytes) : p(static_cast<char*>(std::malloc(bytes))), n(bytes) {}
+    Buf(const Buf&) = delete;
+    ~Buf() { std::free(p); }
+};
+
+// One region of a layout carved on a buffer of exactly the reported size.
+struct Region {
+    const char* name;
+    const void* ptr;  // nullptr: the plan has no such region
+    size_t bytes;     // what the entry point may touch from ptr on
+};
+
+// Every region 256-aligned, in increasing order, none overlapping the one
+// before, all inside [base, base + bytes); the sizes-only pass reports the
+// same bytes.
+void check_regions(const char* layout, const char* base, size_t bytes, size_t bytes_null,
+                   const std::vector<Region>& regions) {
+    CHECK(bytes == bytes_null);
+    const char* end = base;
+    for (const Region& r : regions) {
+        if (!r.ptr) continue;
+        const char* q = static_cast<const char*>(r.ptr);
+        if (q < end || (q - base) % 256 != 0 || q + r.bytes > base + bytes) {
+            if (++g_failed <= 50)
+                std::fprintf(stderr, "[%s] %s.%s: offset %td size %zu, previous end %td, total %zu\n",
+                             g_what.c_str(), layout, r.name, q - base, r.bytes, end - base, bytes);
+            return;
+        }
+        end = q + r.bytes;
+    }
+}
+
+std::vector<Region> step_regions(const psvi_plan& p, const StepWs& w) {
+    const size_t n = sizeof(float) * (size_t)p.d.S * p.rows_tot[p.rank];
+    return {{"x", w.x, n}, {"g", w.g, n + 256}, {"acc", w.acc, sizeof(float) * (size_t)p.acc_count}};
+}
+void append(std::vector<Region>& v, const std::vector<Region>& more) {
+    v.insert(v.end(), more.begin(), more.end());
+}
+std::vector<Region> outer_regions(const psvi_plan& p, const OuterWs& w) {
+    const size_t S = p.d.S, M = p.d.M, D = plan_in_dim(p), f = sizeof(float);
+    std::vector<Region> v = step_regions(p, w.step);
+    append(v, {{"nll", w.nll, f * S * M}, {"rowcoef", w.rowcoef, f * 2 * S}, {"ck", w.ck, f * S},
+               {"sck", w.sck, f}, {"stats", w.stats, sizeof(double) * 2 * S},
+               {"du", w.du, f * S * M * D}, {"dz", w.dz, f * S * M}});
+    return v;
+}
+
+// the five layouts of a non-LeNet plan, each carved on a malloc'd buffer of
+// exactly its size (the sanitizer's redzones right behind it)
+void check_workspaces(const psvi_plan& p) {
+    const size_t S = p.d.S, M = p.d.M, f = sizeof(float);
+    CHECK(p.ws_bytes == step_ws(p, nullptr).bytes);
+    {
+        const Buf buf(step_ws(p, nullptr).bytes);
+        const StepWs w = step_ws(p, buf.p);
+        check_regions("step", buf.p, buf.n, w.bytes, step_regions(p, w));
+        CHECK((p.family == PSVI_FAMILY_FULLCOV) == (w.x != nullptr && w.g != nullptr));
+        CHECK((p.family == PSVI_FAMILY_FULLCOV) == (w.acc == nullptr));
+        if (w.g) CHECK(w.g_pad == w.g + S * p.rows_tot[p.rank]);
+    }
+    {
+        const Buf buf(loop_ws(p, nullptr).bytes);
+        const LoopWs w = loop_ws(p, buf.p);
+        const size_t eb = f * ((size_t)eps_stride(p) + 64);
+        std::vector<Region> v = step_regions(p, w.step);
+        append(v, {{"ebuf0", w.ebuf[0], eb}, {"ebuf1", w.ebuf[1], eb},
+                   {"tstate", w.tstate, f * tiled_floats(p)},
+                   {"pbuf0", w.pbuf[0], w.pbuf_bytes}, {"pbuf1", w.pbuf[1], w.pbuf_bytes}});
+        check_regions("loop", buf.p, buf.n, w.bytes, v);
+        CHECK((w.tstate != nullptr) == tiled_ok(p));
+        CHECK((w.pbuf[0] != nullptr) == p.bf_stream && (w.pbuf[1] != nullptr) == p.bf_stream);
+        if (p.bf_stream) CHECK(w.pbuf_bytes >= 3 * sizeof(uint16_t) * (size_t)p.eps_planes.pl);
+        // each pad: 64 floats, inside its owner's region, behind the owner's data
+        const float* owner[3] = {w.ebuf[0], w.ebuf[1], w.step.g};
+        const size_t data[3] = {(size_t)p.Peps, (size_t)p.Peps, S * p.rows_tot[p.rank]};
+        const size_t room[3] = {eb, eb, f * data[2] + 256};
+        for (int k = 0; k < 3; ++k) {
+            CHECK((w.pads[k] != nullptr) == (owner[k] != nullptr));
+            if (!owner[k]) continue;
+            CHECK(w.pads[k] == owner[k] + data[k]);
+            CHECK((const char*)(w.pads[k] + 64) <= (const char*)owner[k] + room[k]);
+        }
+    }
+    {
+        const Buf buf(outer_ws(p, nullptr).bytes);
+        const OuterWs w = outer_ws(p, buf.p);
+        check_regions("outer", buf.p, buf.n, w.bytes, outer_regions(p, w));
+        CHECK((w.dz != nullptr) == (p.lik == PSVI_LIK_GAUSSIAN));
+    }
+    {
+        const Buf buf(eval_ws(p, nullptr).bytes);
+        const EvalWs w = eval_ws(p, buf.p);
+        std::vector<Region> v = outer_regions(p, w.outer);
+        append(v, {{"out", w.out, f * S * M * p.lay[p.L - 1].dout}, {"W", w.W, f * S}});
+        check_regions("eval", buf.p, buf.n, w.bytes, v);
+    }
+    {
+        const Buf buf(hvp_ws(p, nullptr).bytes);
+        const HvpWs w = hvp_ws(p, buf.p);
+        const size_t nt = p.n_tot, ns = rop_splits(p);
+        const size_t part2 = f * kFwdRows *
+                             std::max({(size_t)p.fwd.n() * S, (size_t)p.n_fp_slots * kKsPass,
+                                       (size_t)p.n_fs_slots * kKsPass});
+        std::vector<Region> v = step_regions(p, w.step);
+        append(v, {{"xd", w.xd, f * S * nt}, {"G", w.G, f * ns * S * nt}, {"Gd", w.Gd, f * ns * S * nt},
+                   {"du", w.du, f * S * M * p.lay[0].din}, {"nlld", w.nlld, f * S * M},
+                   {"dzd", w.dzd, f * S * M}, {"part2", w.part2, part2}});
+        check_regions("hvp", buf.p, buf.n, w.bytes, v);
+        CHECK((w.dzd != nullptr) == (p.lik == PSVI_LIK_GAUSSIAN));
+        CHECK((w.part2 != nullptr) == (p.family == PSVI_FAMILY_FULLCOV));
+    }
+}
+
 // ------------------------------------------------------------------- plans
 std::unique_ptr<psvi_plan> make_plan(int family, const std::vector<int>& dims, int S, int M, int world,
                                      int rank) {
@@ -414,6 +536,7 @@ void check_fullcov(const std::vector<int>& dims, int S, int world, int rank) {
     check_fseg(*p, 256, p->fp_segs, p->fp_off, p->fp_rb, p->n_fp_slots);
     check_fwd(*p);
     check_upd(*p);
+    check_workspaces(*p);
 }
 
 void check_empty(int family, const char* name) {
@@ -422,6 +545,11 @@ void check_empty(int family, const char* name) {
     if (!p) return;
     ++g_plans;
     CHECK(all_fullcov_tables_empty(*p));
+    if (family == PSVI_FAMILY_LENET) return;  // its HVP scratch is kernels_lenet.hip's
+    check_workspaces(*p);
+    g_what += " (gaussian)";  // as psvi_plan_create_lik leaves a Gaussian plan
+    p->lik = PSVI_LIK_GAUSSIAN;
+    check_workspaces(*p);
 }
 
 }  // namespace

@@ -2,7 +2,7 @@
 RCCL (CPU): the all_to_all split/dtype/contiguity check every exchange passes
 through (psvi.runtime.sharded.check_exchange), and the plan's bound on the
 tiled corr / m / v state that the write-through buffer stores address with
-one 32-bit descriptor (capi.cpp tiled_ok)."""
+one 32-bit descriptor (workspace.cpp tiled_ok)."""
 import pytest
 import torch
 

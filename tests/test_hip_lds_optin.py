@@ -1,6 +1,6 @@
 """Every kernel family that launches with more than 64 KiB of dynamic LDS,
 run on device 0 and then on device 1 of one process: each launch needs the
-kernel's opt-in (allow_dynamic_lds, csrc/capi.cpp) on the device it runs on,
+kernel's opt-in (allow_dynamic_lds, csrc/capi_plan.cpp) on the device it runs on,
 so the second device only works if the opt-in is made per device (or is a
 property of the kernel on all devices at once).  Every call must succeed on
 both devices and device 1's outputs must equal device 0's bit for bit: the
