@@ -22,7 +22,7 @@
 // an atomic: every sum has one owner and a fixed order.
 #include <limits.h>
 
-#include "psvi_internal.hpp"
+#include "lds_layout.hpp"
 
 namespace psvi {
 
@@ -259,14 +259,15 @@ __device__ __forceinline__ void km_accumulate(const KmArgs& a, int row_lo, int r
 // they are still in cache).
 template <int KPT>
 __global__ __launch_bounds__(kKmThreads) void km_assign_kernel(KmArgs a, int t) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char km_lds[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char km_sm[];
     __shared__ double sBd[kKg][kKmRows];
     __shared__ int sBk[kKg][kKmRows];
     __shared__ int sLab[kKmRows];
     __shared__ int sCnt[kKmMaxK];
     if (a.w.state->done[t & 1]) return;
-    double* sC = reinterpret_cast<double*>(km_lds);
-    float* sX = reinterpret_cast<float*>(km_lds + sizeof(double) * (size_t)a.K * a.DT);
+    const KmLds sh = km_lds(km_sm, a.K, a.DT, a.XS, true);
+    double* sC = sh.sC;
+    float* sX = sh.sX;
     const int tid = threadIdx.x, lane = tid & 63, g = wave_id();
     const int K = a.K, D = a.D, DT = a.DT, XS = a.XS;
     const int nk = g < K ? (K - g + kKg - 1) / kKg : 0;
@@ -365,14 +366,14 @@ __global__ __launch_bounds__(kKmThreads) void km_assign_kernel(KmArgs a, int t) 
 // the second-pass sums: workgroup (p, ct) owns the rows of chunk p and the
 // columns of tile ct
 __global__ __launch_bounds__(kKmThreads) void km_sums_kernel(KmArgs a, int t) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char km_lds[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char km_sm[];
     __shared__ int sLab[kKmRows];
     if (a.w.state->done[t & 1]) return;
     const int p = blockIdx.x, f0 = blockIdx.y * a.DT;
     const int row_lo = (int)min((int64_t)p * a.rpc, (int64_t)a.N);
     const int row_hi = (int)min((int64_t)row_lo + a.rpc, (int64_t)a.N);
-    km_accumulate(a, row_lo, row_hi, f0, min(a.DT, a.D - f0), reinterpret_cast<double*>(km_lds), sLab,
-                  a.w.part + (int64_t)p * a.K * a.D);
+    km_accumulate(a, row_lo, row_hi, f0, min(a.DT, a.D - f0), km_lds(km_sm, a.K, a.DT, a.XS, false).sC,
+                  sLab, a.w.part + (int64_t)p * a.K * a.D);
 }
 
 // Workgroup (k, cb): columns [256 cb, 256 cb + 256) of centre k.  Every
@@ -474,7 +475,7 @@ km_assign_fn km_assign_for(int K) {
 
 KmeansShape kmeans_shape(int64_t N, int D, int K) {
     KmeansShape s;
-    s.DT = (int)std::min<size_t>((size_t)D, (kKmLds - 256) / ((size_t)K * 8 + 4 * kKmRows));
+    s.DT = km_tile_cols(D, K);
     s.XS = s.DT | 1;
     s.tiles = (int)((N + kKmRows - 1) / kKmRows);
     s.tpb = (s.tiles + kKmMaxGrid - 1) / kKmMaxGrid;
@@ -513,8 +514,8 @@ hipError_t launch_kmeans(const Kmeans& r, hipStream_t st) {
         a.P = (s.tiles + tiles_per - 1) / tiles_per;
     }
     const km_assign_fn assign = km_assign_for(r.K);
-    const size_t lds_assign = sizeof(double) * (size_t)r.K * s.DT + sizeof(float) * kKmRows * (size_t)s.XS;
-    const size_t lds_sums = sizeof(double) * (size_t)r.K * s.DT;
+    const size_t lds_assign = km_lds(nullptr, r.K, s.DT, s.XS, true).bytes;
+    const size_t lds_sums = km_lds(nullptr, r.K, s.DT, s.XS, false).bytes;
     if (hipError_t e = allow_dynamic_lds((const void*)assign, kKmLds); e != hipSuccess) return e;
     if (hipError_t e = allow_dynamic_lds((const void*)km_sums_kernel, kKmLds); e != hipSuccess)
         return e;

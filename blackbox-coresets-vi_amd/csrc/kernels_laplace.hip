@@ -35,12 +35,9 @@
 // geodesic direction of every minibatch point on the unit sphere of centred
 // log-likelihood vectors, the greedy pick and the line-search step, one
 // workgroup over the same float-rounded ll (giga_step_kernel below).
-#include "psvi_internal.hpp"
+#include "lds_layout.hpp"
 
 namespace psvi {
-
-constexpr int kLapThreads = 256;
-constexpr size_t kLapLds = 160 * 1024;
 
 // overflow-safe Bernoulli terms of a logit f: e = exp(-|f|),
 // sigmoid(f) = 1 / (1 + e) or e / (1 + e), softplus(f) = max(f, 0) + log1p(e)
@@ -70,10 +67,9 @@ template <bool XLDS>
 __global__ __launch_bounds__(kLapThreads) void laplace_fit_kernel(LapFitArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lap_sm[];
     const int Nu = a.Nu, d = a.d, tid = threadIdx.x;
-    double* th = lap_sm;                 // [2][kLapMaxD]
-    double* part = th + 2 * kLapMaxD;    // [kLapThreads]
-    double* r = part + kLapThreads;      // [Nu]
-    float* xs = (float*)(r + Nu);        // [Nu][ds], XLDS only
+    const LapFitLds l = lap_fit_lds(lap_sm, Nu, a.ds, XLDS);
+    double *th = l.th, *part = l.part, *r = l.r;
+    float* xs = l.xs;
     const int ld = XLDS ? a.ds : d;
     if (XLDS) {
         for (int i = tid; i < Nu * d; i += kLapThreads) xs[(i / d) * ld + i % d] = a.x[i];
@@ -151,11 +147,6 @@ __global__ __launch_bounds__(kLapThreads) void laplace_fit_kernel(LapFitArgs a) 
     }
 }
 
-static size_t lap_fit_lds(int Nu, int ds, bool xlds) {
-    return sizeof(double) * (2 * kLapMaxD + kLapThreads + (size_t)Nu) +
-           (xlds ? sizeof(float) * (size_t)Nu * ds : 0);
-}
-
 hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st) {
     if (r.d < 1 || r.d > kLapMaxD || r.Nu < 0 || r.Nu > kLapMaxNu || r.S < 0 || r.T < 0 ||
         r.T > kLapMaxT)
@@ -169,8 +160,8 @@ hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st) {
     a.log_norm0 = -std::log(r.sd0) - 0.5 * std::log(2.0 * 3.14159265358979323846);
     a.lr = r.lr; a.b1 = r.beta1; a.b2 = r.beta2; a.adam_eps = r.adam_eps;
     a.theta = r.theta; a.loss = r.loss_out; a.prec = r.prec_out; a.samples = r.samples_out;
-    const bool xlds = lap_fit_lds(r.Nu, a.ds, true) <= kLapLds;
-    const size_t lds = lap_fit_lds(r.Nu, a.ds, xlds);
+    const bool xlds = lap_fit_xlds(r.Nu, a.ds);
+    const size_t lds = lap_fit_lds(nullptr, r.Nu, a.ds, xlds).bytes;
     auto kernel = xlds ? laplace_fit_kernel<true> : laplace_fit_kernel<false>;
     if (hipError_t e = allow_dynamic_lds((const void*)kernel, kLapLds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(1), dim3(kLapThreads), lds, st, a);
@@ -185,8 +176,8 @@ hipError_t launch_laplace_fit(const LaplaceFit& r, hipStream_t st) {
 // the last row and column upwards), L = A^-1: a sample is theta + y, A y = eps,
 // one forward substitution, and L is never formed.  Every eigenvalue of P is
 // >= 1 (w >= 0): no pivoting, no jitter.
-// One workgroup; th [d], the lower triangle of P / A packed by rows
-// (tri(i) + j, j <= i) and a work area are fp64 in LDS:
+// One workgroup; th, the lower triangle of P / A packed by rows (tri(i) + j,
+// j <= i) and a work area are fp64 in LDS (lap_full_lds):
 //   phase 1  rows:    thread t owns rows t, t + 256, ...: r_m = w_m p_m (1 - p_m) -> work
 //            entries: thread t owns the packed entries t, t + 256, ...: the sum
 //                     over the rows in order, x from global memory, then + I
@@ -216,9 +207,8 @@ __device__ __forceinline__ int lap_tri_row(int e) {
 __global__ __launch_bounds__(kLapThreads) void laplace_sample_full_kernel(LapFullArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lapf_sm[];
     const int Nu = a.Nu, d = a.d, tid = threadIdx.x, ntri = lap_tri(d);
-    double* th = lapf_sm;    // [d]
-    double* P = th + d;      // [tri(d)]
-    double* work = P + ntri; // [max(Nu, nb * d)]: r, then y
+    const LapFullLds l = lap_full_lds(lapf_sm, Nu, d, a.nb);
+    double *th = l.th, *P = l.P, *work = l.work;
     for (int j = tid; j < d; j += kLapThreads) th[j] = (double)a.theta[j];
     __syncthreads();
     for (int m = tid; m < Nu; m += kLapThreads) {
@@ -285,11 +275,6 @@ __global__ __launch_bounds__(kLapThreads) void laplace_sample_full_kernel(LapFul
     }
 }
 
-static size_t lap_full_lds(int Nu, int d, int nb) {
-    return sizeof(double) * ((size_t)d + (size_t)d * (d + 1) / 2 +
-                             (size_t)std::max(Nu, nb * d));
-}
-
 hipError_t launch_laplace_sample_full(const LaplaceSampleFull& r, hipStream_t st) {
     if (r.d < 2 || r.d > kLapFullMaxD || r.Nu < 0 || r.Nu > kLapMaxNu || r.S < 0 ||
         r.S > kSelMaxS || (r.S > 0 && (!r.eps || !r.samples_out)))
@@ -299,10 +284,8 @@ hipError_t launch_laplace_sample_full(const LaplaceSampleFull& r, hipStream_t st
     a.x = r.x; a.w = r.w; a.theta = r.theta; a.eps = r.eps;
     a.prec = r.prec_out; a.factor = r.factor_out; a.samples = r.samples_out;
     a.logdet = r.logdet_out;
-    // the sample columns that fit beside theta and the factor, one thread each
-    const int room = (int)((kLapLds - lap_full_lds(0, r.d, 0)) / (sizeof(double) * r.d));
-    a.nb = std::min(std::min(kLapThreads, room), r.S);
-    const size_t lds = lap_full_lds(r.Nu, r.d, a.nb);
+    a.nb = lap_full_cols(r.d, r.S);
+    const size_t lds = lap_full_lds(nullptr, r.Nu, r.d, a.nb).bytes;
     if (lds > kLapLds) return hipErrorInvalidValue;
     if (hipError_t e = allow_dynamic_lds((const void*)laplace_sample_full_kernel, kLapLds);
         e != hipSuccess)
@@ -443,11 +426,8 @@ __global__ __launch_bounds__(kSelThreads) void giga_step_kernel(GigaArgs a) {
     __shared__ double red[kSelThreads];
     __shared__ int redi[kSelThreads];
     const int S = a.S, d = a.d, N = a.N, tid = threadIdx.x;
-    double* mean = giga_sm;  // [N]
-    double* inv = mean + N;  // [N]
-    double* b = inv + N;     // [N]
-    double* ell = b + N;     // [S]
-    double* dd = ell + S;    // [S]: d, then ell*
+    const GigaLds l = giga_lds(giga_sm, N, S);
+    double *mean = l.mean, *inv = l.inv, *b = l.b, *ell = l.ell, *dd = l.dd;
     auto LL = [&](int s, int n) { return lap_ll(a.samples, a.rows, a.labels, d, s, n); };
     for (int n = tid; n < N; n += kSelThreads) {
         double sum = 0.0;
@@ -556,10 +536,10 @@ hipError_t launch_giga_step(const GigaStep& r, hipStream_t st) {
     a.samples = r.samples; a.rows = r.rows; a.labels = r.labels; a.lw = r.lw_in;
     a.score = r.score; a.lw_out = r.lw_out; a.ll = r.ll_out; a.result = r.result;
     // above the 64 KiB a launch gets unasked at the range's far corner
-    constexpr size_t max_lds = sizeof(double) * (3 * (size_t)kLapMaxRows + 2 * (size_t)kSelMaxS);
+    const size_t max_lds = giga_lds(nullptr, kLapMaxRows, kSelMaxS).bytes;
     if (hipError_t e = allow_dynamic_lds((const void*)giga_step_kernel, max_lds); e != hipSuccess)
         return e;
-    const size_t lds = sizeof(double) * (3 * (size_t)r.n_data + 2 * (size_t)r.S);
+    const size_t lds = giga_lds(nullptr, r.n_data, r.S).bytes;
     hipLaunchKernelGGL(giga_step_kernel, dim3(1), dim3(kSelThreads), lds, st, a);
     return hipGetLastError();
 }

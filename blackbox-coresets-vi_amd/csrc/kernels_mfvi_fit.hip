@@ -29,7 +29,7 @@
 // Accumulation: fp32 for the network, the gradient and Adam (the arithmetic of
 // the step-by-step path: net_kernel, mf_update_kernel, adam_apply); fp64 for
 // the per-row NLL terms, the KL terms' sum and the bias corrections.
-#include "psvi_internal.hpp"
+#include "lds_layout.hpp"
 
 namespace psvi {
 
@@ -72,25 +72,15 @@ __global__ __launch_bounds__(kMfFitThreads) void mfvi_fit_kernel(MfFitArgs a) {
     const int tid = threadIdx.x, g = blockIdx.x, NT = kMfFitThreads;
     const int L = a.L, B = a.B, S = a.S, n_tot = a.n_tot, hs = a.hs, RB = a.RB;
     const int P = 2 * n_tot;
-    double* red = mffit_sm;                // [NT]
-    float* Wb = (float*)(red + NT);        // [n_tot]: W_s
-    float* eb = Wb + n_tot;                // [n_tot]: eps_s
-    float* nx = eb + n_tot;
-    float *gmu, *grho, *sp_, *sm_, *sv_;
-    const float* xb;
-    int xs;
+    const MfFitLds sh = mffit_lds(mffit_sm, LDS, L, B, n_tot, hs, a.xs, RB);
+    double* red = sh.red;
+    float *Wb = sh.Wb, *eb = sh.eb, *h = sh.h, *dA = sh.dA, *dB = sh.dB;
+    float *gmu = sh.gmu, *grho = sh.grho, *sp_ = sh.sp, *sm_ = sh.sm, *sv_ = sh.sv;
+    const float* xb = sh.xl;
+    int xs = a.xs;
     if (LDS) {
-        gmu = nx;
-        grho = gmu + n_tot;
-        sp_ = grho + n_tot;
-        sm_ = sp_ + P;
-        sv_ = sm_ + P;
-        float* xl = sv_ + P;
-        nx = xl + (size_t)B * a.xs;
-        xb = xl;
-        xs = a.xs;
         const int D = a.din[0];
-        for (int i = tid; i < B * D; i += NT) xl[(i / D) * xs + i % D] = a.x[i];
+        for (int i = tid; i < B * D; i += NT) sh.xl[(i / D) * xs + i % D] = a.x[i];
     } else {
         gmu = a.ws + (size_t)g * P;
         grho = gmu + n_tot;
@@ -100,9 +90,6 @@ __global__ __launch_bounds__(kMfFitThreads) void mfvi_fit_kernel(MfFitArgs a) {
         xb = a.x;
         xs = a.din[0];
     }
-    float* h = nx;                             // [L - 1][RB][hs]
-    float* dA = h + (size_t)(L - 1) * RB * hs;  // [RB][hs]
-    float* dB = dA + (size_t)RB * hs;           // [RB][hs]
     if (LDS) {
         // owner-mapped as every later access of the state
         for (int l = 0; l < L; ++l)
@@ -263,46 +250,10 @@ __global__ __launch_bounds__(kMfFitThreads) void mfvi_fit_kernel(MfFitArgs a) {
     }
 }
 
-// bytes of LDS at RB rows per chunk
-static size_t mffit_lds(const MfviFitShape& s, bool lds, int RB) {
-    size_t f = 2 * (size_t)s.n_tot;                                          // W_s, eps_s
-    if (lds) f += 8 * (size_t)s.n_tot + (size_t)s.B * s.xs;                  // accumulators, state, batch
-    f += (size_t)(s.L + 1) * RB * s.hs;                                      // activations, two deltas
-    return sizeof(double) * kMfFitThreads + sizeof(float) * f;
-}
-
-int mfvi_fit_shape(const psvi_net_desc& d, MfviFitShape& s) {
-    s = MfviFitShape{};
-    s.L = d.n_layers;
-    s.B = d.M;
-    s.S = d.S;
-    int hmax = 1;
-    for (int l = 0; l < s.L; ++l) {
-        s.n_tot += d.dims[l] * d.dims[l + 1] + d.dims[l + 1];
-        if (l > 0) hmax = std::max(hmax, d.dims[l]);
-    }
-    s.hs = hmax | 1;
-    s.xs = d.dims[0] | 1;
-    s.eps_count = (int64_t)s.S * s.n_tot;
-    // the state and the batch stay in LDS when a chunk of min(B, 16) rows still fits beside them
-    const int want = std::min(s.B, 16);
-    for (int lds = 1; lds >= 0; --lds) {
-        const size_t fixed = mffit_lds(s, lds != 0, 0);
-        if (fixed >= kMfFitLds) continue;
-        const size_t rows = (kMfFitLds - fixed) / (sizeof(float) * (size_t)(s.L + 1) * s.hs);
-        if (rows < (size_t)(lds ? want : 1)) continue;
-        s.lds = lds != 0;
-        s.RB = (int)std::min<size_t>(rows, (size_t)s.B);
-        s.ws_bytes = s.lds ? 0 : sizeof(float) * 2 * (size_t)s.n_tot;  // per member
-        return 0;
-    }
-    return PSVI_EUNSUP;
-}
-
 hipError_t launch_mfvi_fit(const MfviFit& r, hipStream_t st) {
     const MfviFitShape& s = r.shape;
     if (s.L < 2 || s.L > kMfFitMaxL || r.G < 1 || r.G > kMfFitMaxG || s.RB < 1 || r.T < 0 ||
-        mffit_lds(s, s.lds, s.RB) > kMfFitLds || (!s.lds && !r.ws))
+        mffit_lds_bytes(s, s.lds, s.RB) > kMfFitLds || (!s.lds && !r.ws))
         return hipErrorInvalidValue;
     if (r.T == 0) return hipSuccess;
     MfFitArgs a{};
@@ -337,7 +288,7 @@ hipError_t launch_mfvi_fit(const MfviFit& r, hipStream_t st) {
     a.ws = (float*)r.ws;
     auto kernel = s.lds ? mfvi_fit_kernel<true> : mfvi_fit_kernel<false>;
     if (hipError_t e = allow_dynamic_lds((const void*)kernel, kMfFitLds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(r.G), dim3(kMfFitThreads), mffit_lds(s, s.lds, s.RB), st, a);
+    hipLaunchKernelGGL(kernel, dim3(r.G), dim3(kMfFitThreads), mffit_lds_bytes(s, s.lds, s.RB), st, a);
     return hipGetLastError();
 }
 

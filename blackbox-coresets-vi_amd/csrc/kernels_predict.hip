@@ -29,7 +29,7 @@
 // workgroup in their order, the workgroups' partials by a last one-workgroup
 // kernel (thread t sums partials t, t + 256, ... in order, then the same
 // tree).  No atomics; two runs give the same bits.
-#include "psvi_internal.hpp"
+#include "lds_layout.hpp"
 
 namespace psvi {
 
@@ -58,12 +58,9 @@ __global__ __launch_bounds__(kPredThreads) void predict_scores_kernel(PredArgs a
     extern __shared__ __attribute__((aligned(16))) double pred_sm[];
     const int tid = threadIdx.x, NT = kPredThreads;
     const int L = a.L, S = a.S, C = a.C, D = a.D, RG = a.RG, hs = a.hs, xs = a.xs;
-    double* red = pred_sm;                    // [2][NT]
-    float* Wt = (float*)(red + 2 * NT);       // [wcap]: a tile's W_s rows, then its biases
-    float* xin = Wt + a.wcap;                 // [RG][xs]
-    float* hA = xin + (size_t)RG * xs;        // [RG][hs]
-    float* hB = hA + (size_t)RG * hs;         // [RG][hs]
-    float* lg = hB + (size_t)RG * hs;         // [RG][C]: sum over s of the logits
+    const PredLds sh = pred_lds(pred_sm, RG, a.wcap, xs, hs, C);
+    double* red = sh.red;
+    float *Wt = sh.Wt, *xin = sh.xin, *hA = sh.hA, *hB = sh.hB, *lg = sh.lg;
     const float Sf = (float)S;
     double tot_c = 0.0, tot_n = 0.0;  // thread 0: this workgroup's statistics
     for (int64_t item = blockIdx.x; item < a.n_items; item += gridDim.x) {
@@ -227,59 +224,10 @@ __global__ __launch_bounds__(kPredThreads) void predict_stats_kernel(const doubl
     }
 }
 
-// bytes of LDS at RG rows per group and a W tile of wcap floats
-static size_t pred_lds(const PredictShape& s, int RG, int wcap) {
-    return sizeof(double) * 2 * kPredThreads +
-           sizeof(float) * ((size_t)wcap + (size_t)RG * (s.xs + 2 * s.hs + s.C));
-}
-
-int predict_shape(const psvi_plan& p, int64_t rpd, PredictShape& s) {
-    s = PredictShape{};
-    s.L = p.L;
-    s.S = p.d.S;
-    s.D = p.lay[0].din;
-    s.C = p.lay[p.L - 1].dout;
-    s.n_tot = p.n_tot;
-    s.eps_count = p.Peps;
-    int hmax = 1;
-    for (int l = 0; l + 1 < p.L; ++l) hmax = std::max(hmax, p.lay[l].dout);
-    s.hs = hmax | 1;
-    s.xs = s.D | 1;
-    // row groups of one eps block: even shares of at most kPredMaxRows rows,
-    // halved until a tile of `want` units of every layer fits beside them
-    const int64_t groups = (rpd + kPredMaxRows - 1) / kPredMaxRows;
-    const int rg0 = (int)((rpd + groups - 1) / groups);
-    for (int want : {16, 1})
-        for (int rg = rg0;; rg = (rg + 1) / 2) {
-            const size_t fixed = pred_lds(s, rg, 0);
-            if (fixed < kPredLds) {
-                const size_t cap = (kPredLds - fixed) / sizeof(float);
-                bool ok = true;
-                size_t need = 0;
-                for (int l = 0; l < p.L && ok; ++l) {
-                    const size_t row = (size_t)p.lay[l].din + 1;
-                    size_t ut = std::min<size_t>(cap / row, (size_t)p.lay[l].dout);
-                    ok = ut >= (size_t)std::min(want, p.lay[l].dout);
-                    // whole groups of four units, unless the tile is the whole layer
-                    if (ut >= 4 && ut < (size_t)p.lay[l].dout) ut &= ~size_t(3);
-                    s.ut[l] = (int)ut;
-                    need = std::max(need, ut * row);
-                }
-                if (ok) {
-                    s.RG = rg;
-                    s.wcap = (int)need;
-                    return 0;
-                }
-            }
-            if (rg == 1) break;
-        }
-    return PSVI_EUNSUP;
-}
-
 hipError_t launch_predict_scores(const psvi_plan& p, const PredictScores& r, hipStream_t st) {
     const PredictShape& s = r.shape;
     if (s.RG < 1 || s.wcap < 1 || r.n_rows < 1 || r.rpd < 1 || !p.pred_scratch.dev ||
-        pred_lds(s, s.RG, s.wcap) > kPredLds)
+        pred_lds_bytes(s, s.RG, s.wcap) > kPredLds)
         return hipErrorInvalidValue;
     PredArgs a{};
     a.L = s.L; a.S = s.S; a.C = s.C; a.D = s.D; a.RG = s.RG; a.wcap = s.wcap; a.hs = s.hs; a.xs = s.xs;
@@ -307,7 +255,7 @@ hipError_t launch_predict_scores(const psvi_plan& p, const PredictScores& r, hip
     hipLaunchKernelGGL(predict_sigma_kernel, dim3(std::min(64, (s.n_tot + 255) / 256)), dim3(256), 0,
                        st, a, sig);
     hipLaunchKernelGGL(predict_scores_kernel, dim3(grid), dim3(kPredThreads),
-                       pred_lds(s, s.RG, s.wcap), st, a);
+                       pred_lds_bytes(s, s.RG, s.wcap), st, a);
     if (r.stats_out)
         hipLaunchKernelGGL(predict_stats_kernel, dim3(1), dim3(kPredThreads), 0, st,
                            (const double*)p.pred_scratch.dev, grid, r.stats_out);

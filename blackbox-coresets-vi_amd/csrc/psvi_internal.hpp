@@ -788,6 +788,8 @@ hipError_t launch_select_weight_grad(int S, int Nu, int B, const float* ll, cons
 // on theta [d] of the weighted logistic log-joint of x [Nu][d] / y / w in one
 // workgroup, then the diagonal precision and (eps given) S samples from it.
 constexpr int kSelThreads = 512;   // the one-workgroup selection, scores and GIGA kernels
+constexpr int kLapThreads = 256;   // the fit's and the full-precision samples' workgroup
+constexpr size_t kLapLds = 160 * 1024;  // their dynamic-LDS cap
 constexpr int kSelMaxS = 2048;     // their per-sample terms live in LDS
 constexpr int kLapMaxD = 256;      // one column owner per thread of the fit's workgroup
 constexpr int kLapMaxNu = 4096;    // the fit's per-row terms live in LDS

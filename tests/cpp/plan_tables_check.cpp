@@ -2,10 +2,13 @@
 // builds (no GPU use): every plan of a list of shapes is built on the host and
 // its tables are checked against what the kernels assume of them; every
 // workspace layout (workspace.hpp) is carved on a buffer of exactly the size it
-// reports and its regions are checked to lie inside, apart and aligned.  Built with
+// reports and its regions are checked to lie inside, apart and aligned; every
+// kernel's dynamic-LDS layout (lds_layout.hpp) is held to the byte count it had
+// before that header and walked on a buffer of exactly that size.  Built with
 // the host sanitizers by `make check-tables`; exit status 0 when all hold.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <set>
@@ -13,7 +16,7 @@
 #include <utility>
 #include <vector>
 
-#include "psvi_internal.hpp"
+#include "lds_layout.hpp"
 #include "workspace.hpp"
 
 using namespace psvi;
@@ -498,6 +501,213 @@ void check_workspaces(const psvi_plan& p) {
     }
 }
 
+// ------------------------------------------------------------- LDS layouts
+// One region of a kernel's dynamic LDS (lds_layout.hpp) at its documented extent.
+struct LdsRegion {
+    const char* name;
+    void* ptr;
+    size_t elem, count;
+    bool absent = false;  // the shape has no such region: null
+};
+#define LDS_R(l, m, count) LdsRegion{#m, (l).m, sizeof(*(l).m), (size_t)(count)}
+
+int g_lds_cases = 0;
+
+// `layout(base)` is a kernel's layout function at one shape, `regions(l)` its
+// regions in order.  The null-base bytes are what the closed-form expression
+// of the commit before lds_layout.hpp gave (`was`: the layouts are unchanged)
+// and, for a shape the launcher accepts, within the kernel's opt-in cap.  On
+// a buffer of exactly that many bytes every region is non-null, aligned to its
+// type and starts where the one before ends; its first and last element are
+// written, the sanitizer's redzone right behind the last region.
+template <class Layout, class Regions>
+void check_lds(const char* kernel, size_t was, bool accepted, size_t cap, Layout layout, Regions regions) {
+    ++g_lds_cases;
+    g_what = kernel;
+    const auto l0 = layout(nullptr);
+    CHECK(l0.bytes == was);
+    if (accepted) CHECK(l0.bytes <= cap);
+    for (const LdsRegion& r : regions(l0)) CHECK(r.ptr == nullptr);
+    const Buf buf(l0.bytes);
+    const auto l = layout(buf.p);
+    CHECK(l.bytes == l0.bytes);
+    char* end = buf.p;
+    for (const LdsRegion& r : regions(l)) {
+        if (r.absent) {
+            CHECK(r.ptr == nullptr && r.count == 0);
+            continue;
+        }
+        char* q = static_cast<char*>(r.ptr);
+        if (q != end || (q - buf.p) % r.elem != 0 || q + r.elem * r.count > buf.p + buf.n) {
+            if (++g_failed <= 50)
+                std::fprintf(stderr, "[%s] %s: offset %td, %zu x %zu bytes, previous end %td, total %zu\n",
+                             g_what.c_str(), r.name, q - buf.p, r.count, r.elem, end - buf.p, buf.n);
+            return;
+        }
+        if (r.count) {
+            std::memset(q, 0xA5, r.elem);
+            std::memset(q + r.elem * (r.count - 1), 0x5A, r.elem);
+        }
+        end = q + r.elem * r.count;
+    }
+    CHECK(end == buf.p + buf.n);
+}
+
+void check_lds_laplace() {
+    const size_t f8 = sizeof(double), f4 = sizeof(float);
+    int staged[2] = {0, 0};
+    for (int Nu : {0, 1, kLapMaxNu})
+        for (int d : {1, 2, 255, kLapMaxD}) {
+            const int ds = d | 1;
+            const bool was_xlds = f8 * (2 * kLapMaxD + kLapThreads + (size_t)Nu) + f4 * (size_t)Nu * ds <= kLapLds;
+            g_what = "laplace_fit";
+            CHECK(lap_fit_xlds(Nu, ds) == was_xlds);
+            for (bool xlds : {false, true}) {
+                const size_t was = f8 * (2 * kLapMaxD + kLapThreads + (size_t)Nu) +
+                                   (xlds ? f4 * (size_t)Nu * ds : 0);
+                check_lds("laplace_fit", was, xlds == was_xlds, kLapLds,
+                          [&](void* b) { return lap_fit_lds(b, Nu, ds, xlds); },
+                          [&](const LapFitLds& l) {
+                              return std::vector<LdsRegion>{LDS_R(l, th, 2 * kLapMaxD), LDS_R(l, part, kLapThreads),
+                                                            LDS_R(l, r, Nu), LDS_R(l, xs, xlds ? Nu * ds : 0)};
+                          });
+            }
+            ++staged[was_xlds];
+        }
+    g_what = "laplace_fit";
+    CHECK(staged[0] > 0 && staged[1] > 0);
+    // the GPU suite's two sides (tests/test_hip_laplace.py: the edge shapes; Nu = 700, d = 65)
+    CHECK(lap_fit_xlds(65, 65 | 1) && !lap_fit_xlds(700, 65 | 1) && !lap_fit_xlds(4096, 11 | 1));
+    for (int d : {2, 127, kLapFullMaxD})
+        for (int Nu : {0, 1, kLapMaxNu})
+            for (int S : {0, 1, kSelMaxS}) {
+                const size_t head = f8 * ((size_t)d + (size_t)d * (d + 1) / 2);
+                const int room = (int)((kLapLds - head) / (f8 * d));
+                const int nb = std::min(std::min(kLapThreads, room), S);
+                g_what = "laplace_sample_full";
+                CHECK(lap_full_cols(d, S) == nb);
+                check_lds("laplace_sample_full", head + f8 * (size_t)std::max(Nu, nb * d), true, kLapLds,
+                          [&](void* b) { return lap_full_lds(b, Nu, d, nb); },
+                          [&](const LapFullLds& l) {
+                              return std::vector<LdsRegion>{LDS_R(l, th, d), LDS_R(l, P, d * (d + 1) / 2),
+                                                            LDS_R(l, work, std::max(Nu, nb * d))};
+                          });
+            }
+    const size_t giga_cap = giga_lds(nullptr, kLapMaxRows, kSelMaxS).bytes;
+    g_what = "giga_step";
+    CHECK(giga_cap == f8 * (3 * (size_t)kLapMaxRows + 2 * (size_t)kSelMaxS));
+    for (int N : {1, kLapMaxRows})
+        for (int S : {2, kSelMaxS})
+            check_lds("giga_step", f8 * (3 * (size_t)N + 2 * (size_t)S), true, giga_cap,
+                      [&](void* b) { return giga_lds(b, N, S); },
+                      [&](const GigaLds& l) {
+                          return std::vector<LdsRegion>{LDS_R(l, mean, N), LDS_R(l, inv, N), LDS_R(l, b, N),
+                                                        LDS_R(l, ell, S), LDS_R(l, dd, S)};
+                      });
+}
+
+void check_lds_mfvi_fit() {
+    const size_t f4 = sizeof(float);
+    int placed[2] = {0, 0};
+    for (int L : {2, kMfFitMaxL})
+        for (int D : {1, kMfFitMaxD})
+            for (int H : {1, kMfFitMaxH})
+                for (int B : {1, 16, kMfFitMaxB})
+                    for (int S : {1, kMfFitMaxS}) {
+                        psvi_net_desc d{};
+                        d.n_layers = L;
+                        d.dims[0] = D;
+                        for (int l = 1; l < L; ++l) d.dims[l] = H;
+                        d.dims[L] = 1;
+                        d.M = B;
+                        d.S = S;
+                        MfviFitShape s;
+                        const int rc = mfvi_fit_shape(d, s);
+                        g_what = "mfvi_fit";
+                        CHECK(rc == 0 && s.RB >= 1 && s.RB <= B);  // every shape of the ranges fits
+                        ++placed[s.lds];
+                        auto was = [&](bool lds, int RB) {
+                            size_t f = 2 * (size_t)s.n_tot;
+                            if (lds) f += 8 * (size_t)s.n_tot + (size_t)s.B * s.xs;
+                            f += (size_t)(s.L + 1) * RB * s.hs;
+                            return sizeof(double) * kMfFitThreads + f4 * f;
+                        };
+                        for (bool lds : {false, true}) {
+                            // what a further row costs, as the solver takes it from the walk
+                            CHECK(mffit_lds_bytes(s, lds, 1) - mffit_lds_bytes(s, lds, 0) ==
+                                  f4 * (size_t)(s.L + 1) * s.hs);
+                            for (int RB : {0, 1, s.RB}) {
+                                const size_t n = s.n_tot, rows = (size_t)RB * s.hs;
+                                check_lds("mfvi_fit", was(lds, RB), lds == s.lds && RB == s.RB, kMfFitLds,
+                                          [&](void* b) { return mffit_lds(b, lds, s.L, s.B, s.n_tot, s.hs, s.xs, RB); },
+                                          [&](const MfFitLds& l) {
+                                              std::vector<LdsRegion> v{
+                                                  LDS_R(l, red, kMfFitThreads), LDS_R(l, Wb, n), LDS_R(l, eb, n),
+                                                  LDS_R(l, gmu, lds ? n : 0), LDS_R(l, grho, lds ? n : 0),
+                                                  LDS_R(l, sp, lds ? 2 * n : 0), LDS_R(l, sm, lds ? 2 * n : 0),
+                                                  LDS_R(l, sv, lds ? 2 * n : 0),
+                                                  LDS_R(l, xl, lds ? (size_t)s.B * s.xs : 0),
+                                                  LDS_R(l, h, (s.L - 1) * rows), LDS_R(l, dA, rows), LDS_R(l, dB, rows)};
+                                              for (int i = 3; i < 9; ++i) v[i].absent = !lds;
+                                              return v;
+                                          });
+                            }
+                        }
+                    }
+    g_what = "mfvi_fit";
+    CHECK(placed[0] > 0 && placed[1] > 0);
+}
+
+// the predictive scores' layout at the shapes predict_shape solves for a plan
+void check_lds_predict(const psvi_plan& p) {
+    const std::string plan = g_what;
+    for (int64_t rpd : {1, 63, 64, 65, 1000}) {
+        PredictShape s;
+        g_what = plan + " predict_scores";
+        // every plan built here is small: one row and one unit always fit.  RG,
+        // wcap and ut[] have no query to pin them; they follow from the bytes
+        // held below and from the cost of a further float, the two things the
+        // solver reads off the walk (its body is otherwise as it was)
+        CHECK(predict_shape(p, rpd, s) == 0);
+        CHECK(s.RG >= 1 && s.RG <= kPredMaxRows && s.wcap >= 1);
+        for (int l = 0; l < p.L; ++l)  // a tile of every layer: its W rows and its biases
+            CHECK(s.ut[l] >= 1 && (size_t)s.ut[l] * (p.lay[l].din + 1) <= (size_t)s.wcap);
+        // what a further float of the W tile costs, as the solver takes it from the walk
+        CHECK(pred_lds_bytes(s, s.RG, 1) - pred_lds_bytes(s, s.RG, 0) == sizeof(float));
+        const size_t was = sizeof(double) * 2 * kPredThreads +
+                           sizeof(float) * ((size_t)s.wcap + (size_t)s.RG * (s.xs + 2 * s.hs + s.C));
+        check_lds(g_what.c_str(), was, true, kPredLds,
+                  [&](void* b) { return pred_lds(b, s.RG, s.wcap, s.xs, s.hs, s.C); },
+                  [&](const PredLds& l) {
+                      const size_t R = s.RG;
+                      return std::vector<LdsRegion>{LDS_R(l, red, 2 * kPredThreads), LDS_R(l, Wt, s.wcap),
+                                                    LDS_R(l, xin, R * s.xs), LDS_R(l, hA, R * s.hs),
+                                                    LDS_R(l, hB, R * s.hs), LDS_R(l, lg, R * s.C)};
+                  });
+    }
+    g_what = plan;
+}
+
+void check_lds_kmeans() {
+    for (int K : {1, kKmMaxK})
+        for (int D : {1, 784, kKmMaxD}) {
+            const int DT = (int)std::min<size_t>((size_t)D, (kKmLds - 256) / ((size_t)K * 8 + 4 * kKmRows));
+            const int XS = DT | 1;
+            g_what = "kmeans";
+            CHECK(km_tile_cols(D, K) == DT && DT >= 1);
+            for (bool rows : {true, false}) {
+                const size_t was = sizeof(double) * (size_t)K * DT +
+                                   (rows ? sizeof(float) * kKmRows * (size_t)XS : 0);
+                check_lds(rows ? "km_assign" : "km_sums", was, true, kKmLds,
+                          [&](void* b) { return km_lds(b, K, DT, XS, rows); },
+                          [&](const KmLds& l) {
+                              return std::vector<LdsRegion>{LDS_R(l, sC, (size_t)K * DT),
+                                                            LDS_R(l, sX, rows ? kKmRows * XS : 0)};
+                          });
+            }
+        }
+}
+
 // ------------------------------------------------------------------- plans
 std::unique_ptr<psvi_plan> make_plan(int family, const std::vector<int>& dims, int S, int M, int world,
                                      int rank) {
@@ -537,6 +747,7 @@ void check_fullcov(const std::vector<int>& dims, int S, int world, int rank) {
     check_fwd(*p);
     check_upd(*p);
     check_workspaces(*p);
+    check_lds_predict(*p);
 }
 
 void check_empty(int family, const char* name) {
@@ -547,6 +758,7 @@ void check_empty(int family, const char* name) {
     CHECK(all_fullcov_tables_empty(*p));
     if (family == PSVI_FAMILY_LENET) return;  // its HVP scratch is kernels_lenet.hip's
     check_workspaces(*p);
+    check_lds_predict(*p);
     g_what += " (gaussian)";  // as psvi_plan_create_lik leaves a Gaussian plan
     p->lik = PSVI_LIK_GAUSSIAN;
     check_workspaces(*p);
@@ -575,10 +787,13 @@ int main() {
     g_plan_dbg.ks_wgs = 100;
     check_fullcov(fn2, 128, 1, 0);
     g_plan_dbg.ks_wgs = 0;
+    check_lds_laplace();
+    check_lds_mfvi_fit();
+    check_lds_kmeans();
     if (g_failed) {
         std::fprintf(stderr, "plan_tables_check: %d failed checks\n", g_failed);
         return 1;
     }
-    std::printf("plan_tables_check: %d plans ok\n", g_plans);
+    std::printf("plan_tables_check: %d plans ok, %d LDS layouts ok\n", g_plans, g_lds_cases);
     return 0;
 }
