@@ -279,7 +279,7 @@ int psvi_hvp_ex(const psvi_plan* p, const float* u, const int32_t* z, const floa
                                  as_stream(stream), include_kl != 0));
         return 0;
     }
-    if (rop_rows(*p) == 0)
+    if (p->rop.valu.rc == 0)
         return fail(PSVI_EUNSUP, "model too wide for the per-sample R-op kernel's LDS");
     const HvpWs o = hvp_ws(*p, ws);
     if (!ws || ws_bytes < o.bytes) return fail(PSVI_ENOSPC, "workspace too small");

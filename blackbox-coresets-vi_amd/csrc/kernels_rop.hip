@@ -1,7 +1,7 @@
 // kernels_rop.hip -- Hessian-vector products of the inner ELBO (psvi_hvp) for
 // hypergrad's CG_normaleq (the `hyper` trainer's implicit hypergradient).
 //
-// Reference (/root/reference):
+// Reference:
 //   PSVI.hyper_step            psvi/inference/psvi_classes.py:602-687
 //   CG_normaleq / jvp / grd    psvi/hypergrad/hypergradients.py:199-244, 300-311
 //   GradientDescent fp_map     psvi/hypergrad/diff_optimizers.py:51-60, 157-159
@@ -21,32 +21,31 @@
 // the KL Hessian (hvp_param_kernel).  The mixed products the hypergradient
 // needs come out of the same pass: d/du (vec . grad) = sum_s delta_dot_0 W +
 // delta_0 W_dot, d/dw_m (vec . grad) = sum_s NLL_dot_sm.
+//
+// Which form a plan takes (net_rop_mfma_kernel: matrix cores, a row block in
+// one pass; net_rop_kernel: VALU, rows in chunks), the rows per chunk and both
+// LDS layouts are fixed with the plan (psvi_plan::rop: rop_geometry in
+// lds_shapes.cpp, the layouts in lds_layout.hpp); launch_net_rop reads them.
+// Both forms share the loss head (rop_head) and the weight fetch (rop_fetch_w).
 #include <algorithm>
 
+#include "lds_layout.hpp"
 #include "mfma_tiles.hpp"
 #include "psvi_internal.hpp"
 
 namespace psvi {
 
-struct RopArgs {
-    int L, M, S, n_tot, family, rc, maxd;
+// What every R-op kernel reads (dimensions, offsets into the parameters and
+// eps, pointers, the likelihood): net_rop_kernel takes it with the plan's
+// RopValuLds, net_rop_mfma_kernel with its RopMfmaLds, hvp_assemble_kernel alone.
+struct RopCommon {
+    int L, M, S, n_tot, family;
     int nsplit;  // workgroups per sample (row blocks), each storing its G / G_dot partial
                  // into its own slot [split][S][n_tot]; slot_sum_kernel adds them in order
-    int single;  // 1: the workgroup's rows are one chunk -- weight gradients go straight
-                 // to its slot (no LDS accumulators)
+    int single;  // VALU form, 1: the workgroup's rows are one chunk -- weight gradients go
+                 // straight to its slot (no LDS accumulators)
     int din[kMaxL], dout[kMaxL], woff[kMaxL];
     int64_t poff[kMaxL], eoff[kMaxL];
-    int lx, lxd, lg, lgd, lh[kMaxL + 1], lhd[kMaxL + 1], ld0, ld1, ldd0, ldd1;  // LDS carve
-    // W_l / W_dot_l in LDS: rows of an odd stride ldw[l] (a lane per output row
-    // then hits its own bank), layer l at xo[l] of the X / XD regions, b after W
-    int ldw[kMaxL], xo[kMaxL];
-    // MFMA form (net_rop_mfma_kernel): X_l (l = 0..L) at mxo[l], rows of
-    // ldxm[l] floats = [h | h_dot] halves of kx[l] = rup16(width) (X_0: the u
-    // rows alone; X_L: logits and their tangents); W2_l at mwo[l], rup16(dout)
-    // rows of ldwm[l] = [W | W_dot] halves of kx[l]; b_l | b_dot_l at mbo[l]
-    // (halves of kx[l + 1])
-    int mxo[kMaxL + 1], ldxm[kMaxL + 1], kx[kMaxL + 1], mwo[kMaxL], ldwm[kMaxL], mbo[kMaxL], lstamp;
-    int jw[kMaxL], jbl[kMaxL], jb, ju;  // load jobs: layer l's W2 rows from jw[l], bias rows from jb + jbl[l], u rows from ju
     const float* u;
     const int32_t* z;
     const float* w;
@@ -68,18 +67,68 @@ struct RopArgs {
     float* dzd;
 };
 
+// Element i of layer l's sampled mean-field weights (W row-major, then b) for
+// sample s, and its tangent: mu + softplus(rho) eps, v_mu + sigmoid(rho) v_rho eps
+// (eps holds the layer's weights and biases in separate [S][.] blocks)
+__device__ __forceinline__ void rop_fetch_w(const RopCommon& a, int s, int l, int i, float& xv, float& xdv) {
+    const int dout = a.dout[l], nw = a.din[l] * dout, n = nw + dout;
+    const float e = i < nw ? a.eps[a.eoff[l] + (int64_t)s * nw + i]
+                           : a.eps[a.eoff[l] + (int64_t)a.S * nw + (int64_t)s * dout + i - nw];
+    const int64_t pm = a.poff[l] + i, pr = pm + n;
+    const float rho = a.params[pr];
+    xv = a.params[pm] + softplus_f(rho) * e;
+    xdv = a.vec[pm] + sigmoid_f(rho) * a.vec[pr] * e;
+}
+
+// The loss head of row `row` (of M) of sample s, from its C logits lg and
+// their tangents ld: delta = w (p - onehot) to dl, delta_dot = w p (a_dot -
+// p.a_dot) to ddl, NLL_dot = (p - onehot).a_dot to nlld; Gaussian plans: delta
+// = w tau (f - z), delta_dot = w tau f_dot, -delta_dot to dzd.  dl / ddl may be
+// lg / ld themselves (the matrix-core form works in place): each ld[c] is read
+// before dl[c] / ddl[c] are written.
+__device__ __forceinline__ void rop_head(const RopCommon& a, int s, int row, int C, const float* lg,
+                                         const float* ld, float* dl, float* ddl) {
+    const float wm = a.w[row];
+    if (a.lik == PSVI_LIK_GAUSSIAN) {
+        const float fd = ld[0];
+        const float d = a.tau * (lg[0] - __int_as_float(a.z[row]));
+        const float dd = wm * (a.tau * fd);
+        dl[0] = wm * d;
+        ddl[0] = dd;
+        if (a.nlld) a.nlld[(int64_t)s * a.M + row] = d * fd;
+        if (a.dzd) a.dzd[(int64_t)s * a.M + row] = -dd;
+        return;
+    }
+    const int zm = a.z[row];
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(lg[c] - mx);
+    const float lse = mx + logf(se);
+    float pad = 0.f, nd = 0.f;
+    for (int c = 0; c < C; ++c) pad += expf(lg[c] - lse) * ld[c];
+    for (int c = 0; c < C; ++c) {
+        const float p = expf(lg[c] - lse), ldc = ld[c];
+        const float pmo = p - (c == zm ? 1.f : 0.f);
+        nd = fmaf(pmo, ldc, nd);
+        dl[c] = wm * pmo;
+        ddl[c] = wm * p * (ldc - pad);
+    }
+    if (a.nlld) a.nlld[(int64_t)s * a.M + row] = nd;
+}
+
 // layers at most this wide (the loss head) run the 16-lane K-split forms:
 // the 2 x 2 register blocks leave all but a few threads idle there
 constexpr int kRopNarrow = 8;
 
-__global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
+__global__ __launch_bounds__(512) void net_rop_kernel(RopCommon a, RopValuLds lds) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const int L = a.L, D = a.din[0], C = a.dout[L - 1];
-    float* X = sm + a.lx;
-    float* XD = sm + a.lxd;
-    float* GA = sm + a.lg;
-    float* GDA = sm + a.lgd;
+    float* X = sm + lds.lx;
+    float* XD = sm + lds.lxd;
+    float* GA = sm + lds.lg;
+    float* GDA = sm + lds.lgd;
     // diagnostics (thread 0): shader clocks summed per phase -- 0 weights,
     // 1 inputs, 2-4 forward layers, 5 head, 6-8 backward layers (top first),
     // 9 the slot stores; slot 15 = chunks
@@ -118,8 +167,8 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
                 if (i >= n) break;
                 // exact for i < 2^21: (i + 0.5) / din is >= 0.5 / din from an integer
                 const int j = (int)(((float)i + 0.5f) * rdin);
-                const int dst = a.xo[l] + (i < nw ? j * a.ldw[l] + (i - j * din)
-                                                  : dout * a.ldw[l] + (i - nw));
+                const int dst = lds.xo[l] + (i < nw ? j * lds.ldw[l] + (i - j * din)
+                                                  : dout * lds.ldw[l] + (i - nw));
                 X[dst] = xv[k];
                 XD[dst] = xdv[k];
                 if (!a.single) {
@@ -134,16 +183,9 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
         for (int i = tid; i < n; i += nt) {
             const int o = a.woff[l] + i;
             float xv, xdv;
-            {
-                const float e = i < nw ? a.eps[a.eoff[l] + (int64_t)s * nw + i]
-                                       : a.eps[a.eoff[l] + (int64_t)a.S * nw + (int64_t)s * dout + i - nw];
-                const int64_t pm = a.poff[l] + i, pr = pm + n;
-                const float rho = a.params[pr];
-                xv = a.params[pm] + softplus_f(rho) * e;
-                xdv = a.vec[pm] + sigmoid_f(rho) * a.vec[pr] * e;
-            }
-            const int dst = a.xo[l] + (i < nw ? (i / din) * a.ldw[l] + i % din
-                                              : dout * a.ldw[l] + (i - nw));
+            rop_fetch_w(a, s, l, i, xv, xdv);
+            const int dst = lds.xo[l] + (i < nw ? (i / din) * lds.ldw[l] + i % din
+                                              : dout * lds.ldw[l] + (i - nw));
             X[dst] = xv;
             XD[dst] = xdv;
             if (!a.single) {
@@ -156,8 +198,8 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
     ph(0);
     const int rows_per = (a.M + a.nsplit - 1) / a.nsplit;
     const int m_lo = blockIdx.y * rows_per, m_hi = min(a.M, m_lo + rows_per);
-    for (int m0 = m_lo; m0 < m_hi; m0 += a.rc) {
-        const int rc = min(a.rc, m_hi - m0);
+    for (int m0 = m_lo; m0 < m_hi; m0 += lds.rc) {
+        const int rc = min(lds.rc, m_hi - m0);
         // inputs: h_0 = u rows, h_dot_0 = 0 (the loads of a pass all in flight)
         {
             constexpr int kB = 8;
@@ -171,8 +213,8 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
                 for (int k = 0; k < kB; ++k) {
                     const int i = base + k * nt;
                     if (i >= nu) break;
-                    sm[a.lh[0] + i] = uv[k];
-                    sm[a.lhd[0] + i] = 0.f;
+                    sm[lds.lh[0] + i] = uv[k];
+                    sm[lds.lhd[0] + i] = 0.f;
                 }
             }
         }
@@ -182,15 +224,15 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
         // forward + tangent forward: 2 rows x 2 outputs per thread (8 LDS
         // reads per 12 FMAs; clamped duplicates at odd edges, stored once)
         for (int l = 0; l < L; ++l) {
-            const int din = a.din[l], dout = a.dout[l], ldw = a.ldw[l];
-            const float* W = X + a.xo[l];
-            const float* Wd = XD + a.xo[l];
+            const int din = a.din[l], dout = a.dout[l], ldw = lds.ldw[l];
+            const float* W = X + lds.xo[l];
+            const float* Wd = XD + lds.xo[l];
             const float* b = W + dout * ldw;
             const float* bd = Wd + dout * ldw;
-            const float* H = sm + a.lh[l];
-            const float* HD = sm + a.lhd[l];
-            float* Hn = sm + a.lh[l + 1];
-            float* HDn = sm + a.lhd[l + 1];
+            const float* H = sm + lds.lh[l];
+            const float* HD = sm + lds.lhd[l];
+            float* Hn = sm + lds.lh[l + 1];
+            float* HDn = sm + lds.lhd[l + 1];
             if (dout <= kRopNarrow) {
                 // narrow layer (the head): a 16-lane row per (row m, output o),
                 // lane j summing inputs i = j, j + 16, ..; DPP row sums
@@ -294,50 +336,23 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
             ph(2 + min(l, 2));
         }
         // head: delta = w (p - onehot), delta_dot = w p (a_dot - p.a_dot)
-        float* Dl = sm + a.ld0;
-        float* DDl = sm + a.ldd0;
-        float* Dn = sm + a.ld1;
-        float* DDn = sm + a.ldd1;
-        for (int m = tid; m < rc; m += nt) {
-            const float* lg = sm + a.lh[L] + m * C;
-            const float* ld = sm + a.lhd[L] + m * C;
-            const float wm = a.w[m0 + m];
-            if (a.lik == PSVI_LIK_GAUSSIAN) {
-                const float d = a.tau * (lg[0] - __int_as_float(a.z[m0 + m]));
-                const float dd = wm * (a.tau * ld[0]);
-                Dl[m * a.maxd] = wm * d;
-                DDl[m * a.maxd] = dd;
-                if (a.nlld) a.nlld[(int64_t)s * a.M + m0 + m] = d * ld[0];
-                if (a.dzd) a.dzd[(int64_t)s * a.M + m0 + m] = -dd;
-                continue;
-            }
-            const int zm = a.z[m0 + m];
-            float mx = -INFINITY;
-            for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
-            float se = 0.f;
-            for (int c = 0; c < C; ++c) se += expf(lg[c] - mx);
-            const float lse = mx + logf(se);
-            float pad = 0.f, nd = 0.f;
-            for (int c = 0; c < C; ++c) pad += expf(lg[c] - lse) * ld[c];
-            for (int c = 0; c < C; ++c) {
-                const float p = expf(lg[c] - lse);
-                const float pmo = p - (c == zm ? 1.f : 0.f);
-                nd = fmaf(pmo, ld[c], nd);
-                Dl[m * a.maxd + c] = wm * pmo;
-                DDl[m * a.maxd + c] = wm * p * (ld[c] - pad);
-            }
-            if (a.nlld) a.nlld[(int64_t)s * a.M + m0 + m] = nd;
-        }
+        float* Dl = sm + lds.ld0;
+        float* DDl = sm + lds.ldd0;
+        float* Dn = sm + lds.ld1;
+        float* DDn = sm + lds.ldd1;
+        for (int m = tid; m < rc; m += nt)
+            rop_head(a, s, m0 + m, C, sm + lds.lh[L] + m * C, sm + lds.lhd[L] + m * C, Dl + m * lds.maxd,
+                     DDl + m * lds.maxd);
         __syncthreads();
         ph(5);
         // R-backward: weight gradients 2 outputs x 2 inputs per thread, the
         // propagation 2 rows x 2 inputs (as the forward)
         for (int l = L - 1; l >= 0; --l) {
-            const int din = a.din[l], dout = a.dout[l], nw = din * dout, ldw = a.ldw[l];
-            const float* W = X + a.xo[l];
-            const float* Wd = XD + a.xo[l];
-            const float* H = sm + a.lh[l];
-            const float* HD = sm + a.lhd[l];
+            const int din = a.din[l], dout = a.dout[l], nw = din * dout, ldw = lds.ldw[l];
+            const float* W = X + lds.xo[l];
+            const float* Wd = XD + lds.xo[l];
+            const float* H = sm + lds.lh[l];
+            const float* HD = sm + lds.lhd[l];
             // one chunk: straight into this row block's slot; else the LDS
             // accumulators (added over chunks, stored at the end)
             const int64_t gslot = ((int64_t)blockIdx.y * a.S + s) * a.n_tot + a.woff[l];
@@ -347,7 +362,7 @@ __global__ __launch_bounds__(512) void net_rop_kernel(RopArgs a) {
                 if (a.single) P[i] = v;
                 else P[i] += v;
             };
-            const int md = a.maxd;
+            const int md = lds.maxd;
             const int nbi = (din + 1) >> 1, nbw = ((dout + 1) >> 1) * nbi;
             if (dout <= kRopNarrow) {
                 // narrow layer: a 16-lane row per weight (then per bias), lane j
@@ -641,7 +656,7 @@ __device__ __forceinline__ void rop_gemm(int P, int Q, int K16, int first, const
 }
 
 // The R-op on the matrix cores: one workgroup per (sample, row block), its
-// rows in one pass (launch_net_rop takes this form when the carve fits the LDS).
+// rows in one pass (launch_net_rop takes this form when the plan's layout of it fits the LDS).
 // Per layer l, forward: [a | a_dot] = X_l [W | W_dot]^T pairs (X = h W^T,
 // Y = h W_dot^T + h_dot W^T) + [b | b_dot], the ReLU and its mask in the
 // epilogue into X_{l+1}; the head in place on X_L (delta | delta_dot); per
@@ -659,7 +674,7 @@ __device__ __forceinline__ void lds_dma4(rsrc_t r, float* lds, uint32_t voff) {
 }
 
 template <bool FC>
-__global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
+__global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopCommon a, RopMfmaLds lds) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const int L = a.L, D = a.din[0], C = a.dout[L - 1];
@@ -667,7 +682,7 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
     const int m0 = blockIdx.y * rows_per, rc = max(0, min(a.M, m0 + rows_per) - m0);
     // diagnostics (thread 0): phase clocks summed into LDS past the carve
     // (a register array indexed at run time would live in scratch)
-    unsigned long long* tph = reinterpret_cast<unsigned long long*>(sm + a.lstamp);
+    unsigned long long* tph = reinterpret_cast<unsigned long long*>(sm + lds.lstamp);
     unsigned long long tlast = 0;
     auto ph = [&](int q) __attribute__((always_inline)) {
         if (a.stamps && tid == 0) {
@@ -689,25 +704,25 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
     // registers, a few jobs' loads in flight.
     {
         const int lane = tid & 63, wid = wave_id(), nwv = nt >> 6;
-        const int nch0 = (a.kx[0] + 63) >> 6;
-        const int njobs = a.ju + rc * nch0;
+        const int nch0 = (lds.kx[0] + 63) >> 6;
+        const int njobs = lds.ju + rc * nch0;
         // job j -> kind (0 W2 row, 1 bias row, 2 u row), layer, row, first column (uniform)
         auto decode = [&](int j, int& kind, int& l, int& row, int& c0) __attribute__((always_inline)) {
             l = 0;
-            if (j < a.jb) {
+            if (j < lds.jb) {
                 kind = 0;
-                while (l + 1 < L && j >= a.jw[l + 1]) ++l;
-                const int r = j - a.jw[l], nch = (a.kx[l] + 63) >> 6;
+                while (l + 1 < L && j >= lds.jw[l + 1]) ++l;
+                const int r = j - lds.jw[l], nch = (lds.kx[l] + 63) >> 6;
                 row = nch == 1 ? r : r / nch;
                 c0 = (r - row * nch) << 6;
-            } else if (j < a.ju) {
+            } else if (j < lds.ju) {
                 kind = 1;
-                while (l + 1 < L && j >= a.jb + a.jbl[l + 1]) ++l;
+                while (l + 1 < L && j >= lds.jb + lds.jbl[l + 1]) ++l;
                 row = 0;
-                c0 = (j - a.jb - a.jbl[l]) << 6;
+                c0 = (j - lds.jb - lds.jbl[l]) << 6;
             } else {
                 kind = 2;
-                const int r = j - a.ju;
+                const int r = j - lds.ju;
                 row = nch0 == 1 ? r : r / nch0;
                 c0 = (r - row * nch0) << 6;
             }
@@ -720,9 +735,9 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
             const rsrc_t rxd = make_rsrc(a.xd + (int64_t)s * a.n_tot, 4 * (int64_t)a.n_tot);
             const rsrc_t ru = make_rsrc(a.u + (int64_t)m0 * D, 4 * (int64_t)rc * D);
             for (int l = 0; l < L; ++l) {  // uniform
-                const int din = a.din[l], dout = a.dout[l], kxl = a.kx[l], kq = a.kx[l + 1];
-                const int ldw = a.ldwm[l], nch = (kxl + 63) >> 6, woff = a.woff[l];
-                float* const W2 = sm + a.mwo[l];
+                const int din = a.din[l], dout = a.dout[l], kxl = lds.kx[l], kq = lds.kx[l + 1];
+                const int ldw = lds.ldwm[l], nch = (kxl + 63) >> 6, woff = a.woff[l];
+                float* const W2 = sm + lds.mwo[l];
                 for (int r = wid; r < kq * nch; r += nwv) {  // wave-uniform
                     const int row = nch == 1 ? r : r / nch, c0 = (r - row * nch) << 6, c = c0 + lane;
                     float* d = W2 + row * ldw + c0;
@@ -732,7 +747,7 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
                         lds_dma4(rxd, d + kxl, vo);
                     }
                 }
-                float* const bb = sm + a.mbo[l];
+                float* const bb = sm + lds.mbo[l];
                 for (int c0 = 64 * ((wid + l) % nwv); c0 < kq; c0 += 64 * nwv) {  // wave-uniform
                     const int c = c0 + lane;
                     if (c < kq) {
@@ -743,10 +758,10 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
                 }
             }
             {
-                const int kx0 = a.kx[0], ld0 = a.ldxm[0];
+                const int kx0 = lds.kx[0], ld0 = lds.ldxm[0];
                 for (int r = wid; r < rc * nch0; r += nwv) {  // wave-uniform
                     const int row = nch0 == 1 ? r : r / nch0, c0 = (r - row * nch0) << 6, c = c0 + lane;
-                    float* d = sm + a.mxo[0] + row * ld0 + c0;
+                    float* d = sm + lds.mxo[0] + row * ld0 + c0;
                     if (c < kx0) {
                         lds_dma4(ru, d, c < D ? 4u * (uint32_t)(row * D + c) : kOOB);
                     }
@@ -757,66 +772,54 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
             {
                 const int nz = ((rc + 15) & ~15) - rc;
                 for (int l = 0; l <= L; ++l) {
-                    float4* z4 = reinterpret_cast<float4*>(sm + a.mxo[l] + rc * a.ldxm[l]);
-                    for (int i = tid; i < (nz * a.ldxm[l]) >> 2; i += nt) z4[i] = float4{0.f, 0.f, 0.f, 0.f};
+                    float4* z4 = reinterpret_cast<float4*>(sm + lds.mxo[l] + rc * lds.ldxm[l]);
+                    for (int i = tid; i < (nz * lds.ldxm[l]) >> 2; i += nt) z4[i] = float4{0.f, 0.f, 0.f, 0.f};
                 }
-                const int kx0 = a.kx[0], q4 = kx0 >> 2;
+                const int kx0 = lds.kx[0], q4 = kx0 >> 2;
                 for (int i = tid; i < rc * q4; i += nt) {
                     const int row = i / q4;
-                    reinterpret_cast<float4*>(sm + a.mxo[0] + row * a.ldxm[0] + kx0)[i - row * q4] =
+                    reinterpret_cast<float4*>(sm + lds.mxo[0] + row * lds.ldxm[0] + kx0)[i - row * q4] =
                         float4{0.f, 0.f, 0.f, 0.f};
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (D < a.kx[0]) {
+            if (D < lds.kx[0]) {
                 // layer 0's ones column, over this wave's own DMA'd rows
-                const int ld0 = a.ldxm[0];
+                const int ld0 = lds.ldxm[0];
                 for (int r = wid; r < rc * nch0; r += nwv) {  // wave-uniform
                     const int row = nch0 == 1 ? r : r / nch0, c0 = (r - row * nch0) << 6;
-                    if (c0 + lane == D) sm[a.mxo[0] + row * ld0 + D] = 1.f;
+                    if (c0 + lane == D) sm[lds.mxo[0] + row * ld0 + D] = 1.f;
                 }
             }
         } else {
-            auto fetch_w = [&](int l, int i, float& xv, float& xdv) __attribute__((always_inline)) {
-                // element i of layer l's sampled weights (W row-major, then b) and its tangent
-                const int dout = a.dout[l], nw = a.din[l] * dout, n = nw + dout;
-                const float e = i < nw ? a.eps[a.eoff[l] + (int64_t)s * nw + i]
-                                       : a.eps[a.eoff[l] + (int64_t)a.S * nw + (int64_t)s * dout + i - nw];
-                const int64_t pm = a.poff[l] + i, pr = pm + n;
-                const float rho = a.params[pr];
-                xv = a.params[pm] + softplus_f(rho) * e;
-                xdv = a.vec[pm] + sigmoid_f(rho) * a.vec[pr] * e;
-            };
-            {
-                const int nz = ((rc + 15) & ~15) - rc;
-                for (int l = 0; l <= L; ++l)
-                    for (int i = tid; i < nz * a.ldxm[l]; i += nt) sm[a.mxo[l] + rc * a.ldxm[l] + i] = 0.f;
-            }
+            const int nz = ((rc + 15) & ~15) - rc;
+            for (int l = 0; l <= L; ++l)
+                for (int i = tid; i < nz * lds.ldxm[l]; i += nt) sm[lds.mxo[l] + rc * lds.ldxm[l] + i] = 0.f;
             for (int j = wid; j < njobs; j += nwv) {  // wave-uniform
                 int kind, l, row, c0;
                 decode(j, kind, l, row, c0);
                 const int c = c0 + lane;
                 float v0 = 0.f, v1 = 0.f;
                 if (kind == 0) {
-                    if (row < a.dout[l] && c < a.din[l]) fetch_w(l, row * a.din[l] + c, v0, v1);
-                    if (c < a.kx[l]) {
-                        float* w2 = sm + a.mwo[l] + row * a.ldwm[l] + c;
+                    if (row < a.dout[l] && c < a.din[l]) rop_fetch_w(a, s, l, row * a.din[l] + c, v0, v1);
+                    if (c < lds.kx[l]) {
+                        float* w2 = sm + lds.mwo[l] + row * lds.ldwm[l] + c;
                         w2[0] = v0;
-                        w2[a.kx[l]] = v1;
+                        w2[lds.kx[l]] = v1;
                     }
                 } else if (kind == 1) {
-                    if (c < a.dout[l]) fetch_w(l, a.din[l] * a.dout[l] + c, v0, v1);
-                    if (c < a.kx[l + 1]) {
-                        sm[a.mbo[l] + c] = v0;
-                        sm[a.mbo[l] + a.kx[l + 1] + c] = v1;
+                    if (c < a.dout[l]) rop_fetch_w(a, s, l, a.din[l] * a.dout[l] + c, v0, v1);
+                    if (c < lds.kx[l + 1]) {
+                        sm[lds.mbo[l] + c] = v0;
+                        sm[lds.mbo[l] + lds.kx[l + 1] + c] = v1;
                     }
                 } else {
                     v0 = c == D ? 1.f : 0.f;  // the ones column
                     if (c < D) v0 = a.u[(int64_t)(m0 + row) * D + c];
-                    if (c < a.kx[0]) {
-                        float* x0 = sm + a.mxo[0] + row * a.ldxm[0] + c;
+                    if (c < lds.kx[0]) {
+                        float* x0 = sm + lds.mxo[0] + row * lds.ldxm[0] + c;
                         x0[0] = v0;
-                        x0[a.kx[0]] = 0.f;
+                        x0[lds.kx[0]] = 0.f;
                     }
                 }
             }
@@ -831,9 +834,9 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
     // its 16-row tiles through every layer with no barrier -- leaves half the
     // waves idle at C3's 50-row blocks and measured slower.)
     for (int l = 0; l < L; ++l) {
-        const int dout = a.dout[l], kxl = a.kx[l], kq = a.kx[l + 1], ldn = a.ldxm[l + 1];
-        const float* bl = sm + a.mbo[l];
-        float* Xn = sm + a.mxo[l + 1];
+        const int dout = a.dout[l], kxl = lds.kx[l], kq = lds.kx[l + 1], ldn = lds.ldxm[l + 1];
+        const float* bl = sm + lds.mbo[l];
+        float* Xn = sm + lds.mxo[l + 1];
         const bool last = l == L - 1;
         auto epi = [&](int pr, int q, floatx4 vx, floatx4 vy, int rot) __attribute__((always_inline)) {
             const float b = bl[q], bd = bl[kq + q];  // zero past dout, as the W2 rows
@@ -849,52 +852,25 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
                 }
             }
         };
-        rop_gemm<true, true, true, true, true>(rc, dout, kxl, 0, sm + a.mxo[l], a.ldxm[l], kxl,
-                                                     sm + a.mwo[l], a.ldwm[l], kxl, epi);
+        rop_gemm<true, true, true, true, true>(rc, dout, kxl, 0, sm + lds.mxo[l], lds.ldxm[l], kxl,
+                                                     sm + lds.mwo[l], lds.ldwm[l], kxl, epi);
         __syncthreads();
         ph(2 + min(l, 2));
     }
     // ---- head, in place on X_L: delta = w (p - onehot), delta_dot = w p (a_dot - p.a_dot)
     for (int m = tid; m < rc; m += nt) {
-        float* lg = sm + a.mxo[L] + m * a.ldxm[L];
-        float* ld = lg + a.kx[L];
-        const float wm = a.w[m0 + m];
-        if (a.lik == PSVI_LIK_GAUSSIAN) {
-            const float fd = ld[0];
-            const float d = a.tau * (lg[0] - __int_as_float(a.z[m0 + m]));
-            const float dd = wm * (a.tau * fd);
-            lg[0] = wm * d;
-            ld[0] = dd;
-            if (a.nlld) a.nlld[(int64_t)s * a.M + m0 + m] = d * fd;
-            if (a.dzd) a.dzd[(int64_t)s * a.M + m0 + m] = -dd;
-            continue;
-        }
-        const int zm = a.z[m0 + m];
-        float mx = -INFINITY;
-        for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(lg[c] - mx);
-        const float lse = mx + logf(se);
-        float pad = 0.f, nd = 0.f;
-        for (int c = 0; c < C; ++c) pad += expf(lg[c] - lse) * ld[c];
-        for (int c = 0; c < C; ++c) {
-            const float p = expf(lg[c] - lse), ldc = ld[c];
-            const float pmo = p - (c == zm ? 1.f : 0.f);
-            nd = fmaf(pmo, ldc, nd);
-            lg[c] = wm * pmo;
-            ld[c] = wm * p * (ldc - pad);
-        }
-        if (a.nlld) a.nlld[(int64_t)s * a.M + m0 + m] = nd;
+        float* lg = sm + lds.mxo[L] + m * lds.ldxm[L];
+        rop_head(a, s, m0 + m, C, lg, lg + lds.kx[L], lg, lg + lds.kx[L]);
     }
     __syncthreads();
     ph(5);
     // ---- R-backward
     for (int l = L - 1; l >= 0; --l) {
-        const int din = a.din[l], dout = a.dout[l], nw = din * dout, kxl = a.kx[l], kq = a.kx[l + 1];
-        const float* Dl = sm + a.mxo[l + 1];  // [delta | delta_dot] rows
-        const int ldd = a.ldxm[l + 1], ldx = a.ldxm[l];
-        float* Xl = sm + a.mxo[l];
-        const float* W2 = sm + a.mwo[l];
+        const int din = a.din[l], dout = a.dout[l], nw = din * dout, kxl = lds.kx[l], kq = lds.kx[l + 1];
+        const float* Dl = sm + lds.mxo[l + 1];  // [delta | delta_dot] rows
+        const int ldd = lds.ldxm[l + 1], ldx = lds.ldxm[l];
+        float* Xl = sm + lds.mxo[l];
+        const float* W2 = sm + lds.mwo[l];
         const int64_t gslot = ((int64_t)blockIdx.y * a.S + s) * a.n_tot + a.woff[l];
         float* GW = a.G + gslot;
         float* GDW = a.Gd + gslot;
@@ -951,7 +927,7 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
                     }
                 }
             };
-            rop_gemm<true, false, true, true, true>(rc, din, kq, 0, Dl, ldd, kq, W2, a.ldwm[l], kxl, pepi);
+            rop_gemm<true, false, true, true, true>(rc, din, kq, 0, Dl, ldd, kq, W2, lds.ldwm[l], kxl, pepi);
             __syncthreads();
         } else if (a.du) {
             // d/du of (vec . grad): the input rows' delta_dot (no mask at the input)
@@ -963,7 +939,7 @@ __global__ __launch_bounds__(512) void net_rop_mfma_kernel(RopArgs a) {
                     if (m < rc) a.du[((int64_t)s * a.M + m0 + m) * D + q] = vy[r];
                 }
             };
-            rop_gemm<true, false, true, true, true>(rc, din, kq, 0, Dl, ldd, kq, W2, a.ldwm[0], kxl, uepi);
+            rop_gemm<true, false, true, true, true>(rc, din, kq, 0, Dl, ldd, kq, W2, lds.ldwm[0], kxl, uepi);
         }
         ph(6 + min(L - 1 - l, 2));
     }
@@ -1005,7 +981,7 @@ __device__ __forceinline__ void sample_quarter(int S, int wv, int& s0, int& s1) 
 }
 
 template <bool SLOTS, bool FC>
-__device__ __forceinline__ void hvp_param_body(const RopArgs& a, float* hv, float inv_s0sq, float klw,
+__device__ __forceinline__ void hvp_param_body(const RopCommon& a, float* hv, float inv_s0sq, float klw,
                                                int64_t slot2, int bx) {
     // SLOTS: G / G_dot still in the R-op's two row-block slots (slot 1 at
     // + slot2), added here as slot_sum_kernel would: slot 0 + slot 1.  FC:
@@ -1120,7 +1096,7 @@ __device__ __forceinline__ void sample_sum_body(const float* __restrict__ src, i
 // [0, nbp) the parameter elements, then nbu of d_u, then the d_w ones (a
 // workgroup-uniform branch; three launches before)
 template <bool SLOTS, bool FC>
-__global__ __launch_bounds__(1024) void hvp_assemble_kernel(RopArgs a, float* hv, float inv_s0sq, float klw,
+__global__ __launch_bounds__(1024) void hvp_assemble_kernel(RopCommon a, float* hv, float inv_s0sq, float klw,
                                                            int64_t slot2, int nbp, const float* du,
                                                            int64_t ndu, float* d_u, int nbu,
                                                            const float* nlld, float* d_w) {
@@ -1133,104 +1109,8 @@ __global__ __launch_bounds__(1024) void hvp_assemble_kernel(RopArgs a, float* hv
         sample_sum_body(nlld, a.M, a.S, a.M, d_w, b - nbp - nbu);
 }
 
-static int rup4(int x) { return (x + 3) & ~3; }
-
-// LDS carve for rows in chunks of rc; returns floats
-static size_t rop_carve(const psvi_plan& p, int rc, RopArgs* a, bool with_g = true) {
-    size_t off = 0;
-    auto take = [&](size_t nfl) {
-        const size_t o = off;
-        off += (nfl + 3) & ~size_t(3);
-        return (int)o;
-    };
-    int maxd = 0;
-    for (int l = 0; l < p.L; ++l) maxd = std::max(maxd, std::max(p.lay[l].din, p.lay[l].dout));
-    maxd = rup4(maxd) | 1;  // odd row stride of the delta buffers
-    int xo[kMaxL], ldw[kMaxL], xtot = 0;
-    for (int l = 0; l < p.L; ++l) {
-        ldw[l] = p.lay[l].din | 1;
-        xo[l] = xtot;
-        xtot += p.lay[l].dout * ldw[l] + p.lay[l].dout;
-    }
-    const int lx = take(xtot), lxd = take(xtot);
-    const int lg = with_g ? take(p.n_tot) : 0, lgd = with_g ? take(p.n_tot) : 0;
-    int lh[kMaxL + 1], lhd[kMaxL + 1];
-    for (int l = 0; l <= p.L; ++l) {
-        const int d = l < p.L ? p.lay[l].din : p.lay[p.L - 1].dout;
-        lh[l] = take((size_t)rc * d);
-        lhd[l] = take((size_t)rc * d);
-    }
-    const int ld0 = take((size_t)rc * maxd), ld1 = take((size_t)rc * maxd);
-    const int ldd0 = take((size_t)rc * maxd), ldd1 = take((size_t)rc * maxd);
-    if (a) {
-        a->lx = lx; a->lxd = lxd; a->lg = lg; a->lgd = lgd;
-        for (int l = 0; l < p.L; ++l) { a->xo[l] = xo[l]; a->ldw[l] = ldw[l]; }
-        for (int l = 0; l <= p.L; ++l) { a->lh[l] = lh[l]; a->lhd[l] = lhd[l]; }
-        a->ld0 = ld0; a->ld1 = ld1; a->ldd0 = ldd0; a->ldd1 = ldd1;
-        a->maxd = maxd;
-        a->rc = rc;
-    }
-    return off;
-}
-
-// LDS carve of the MFMA form for a row block of `rows`; returns floats.  The
-// activation regions come first, so a 16-row tile's over-read past a region's
-// rows stays inside the allocation (tail slack when the weights after the last
-// one are shorter than that).
-static size_t rop_mfma_carve(const psvi_plan& p, int rows, RopArgs* a) {
-    const int L = p.L;
-    int kx[kMaxL + 1], mxo[kMaxL + 1], ldxm[kMaxL + 1], mwo[kMaxL], ldwm[kMaxL], mbo[kMaxL];
-    for (int l = 0; l < L; ++l) kx[l] = (p.lay[l].din + 15) & ~15;
-    kx[L] = (p.lay[L - 1].dout + 15) & ~15;
-    size_t off = 0;
-    for (int l = 0; l <= L; ++l) {
-        ldxm[l] = 2 * kx[l] + 8;  // == 8 (mod 16); X_0's tangent half is zero
-        mxo[l] = (int)off;
-        off += (size_t)rows * ldxm[l];
-    }
-    const size_t x_end = off;
-    for (int l = 0; l < L; ++l) {
-        ldwm[l] = 2 * kx[l] + 8;
-        mwo[l] = (int)off;
-        off += (size_t)kx[l + 1] * ldwm[l];
-    }
-    for (int l = 0; l < L; ++l) {
-        mbo[l] = (int)off;
-        off += 2 * (size_t)kx[l + 1];
-    }
-    const size_t over = (size_t)(((rows + 15) & ~15) - rows) * ldxm[L];
-    if (off - x_end < over) off = x_end + over;
-    off = (off + 3) & ~size_t(3);
-    const int lstamp = (int)off;
-    off += 20;  // 10 uint64 phase clocks (diagnostics)
-    if (a) {
-        int j = 0;
-        for (int l = 0; l < L; ++l) {
-            a->jw[l] = j;
-            j += kx[l + 1] * ((kx[l] + 63) >> 6);
-        }
-        a->jb = j;
-        for (int l = 0; l < L; ++l) {
-            a->jbl[l] = j - a->jb;
-            j += (kx[l + 1] + 63) >> 6;
-        }
-        a->ju = j;
-        a->lstamp = lstamp;
-        for (int l = 0; l <= L; ++l) { a->kx[l] = kx[l]; a->mxo[l] = mxo[l]; a->ldxm[l] = ldxm[l]; }
-        for (int l = 0; l < L; ++l) { a->mwo[l] = mwo[l]; a->ldwm[l] = ldwm[l]; a->mbo[l] = mbo[l]; }
-    }
-    return off;
-}
-
-constexpr size_t kRopLds = 160 * 1024;
-// rows per chunk that fit the LDS (0: the model's weights alone do not fit)
-int rop_rows(const psvi_plan& p) {
-    for (int rc = 64; rc >= 1; rc >>= 1)
-        if (rop_carve(p, rc, nullptr) * 4 <= kRopLds) return rc;
-    return 0;
-}
-
-static void rop_fill(const psvi_plan& p, RopArgs& a) {
+static RopCommon rop_common(const psvi_plan& p) {
+    RopCommon a{};
     a.L = p.L;
     a.M = p.d.M;
     a.S = p.d.S;
@@ -1245,6 +1125,7 @@ static void rop_fill(const psvi_plan& p, RopArgs& a) {
         a.poff[l] = p.lay[l].poff;
         a.eoff[l] = p.lay[l].eoff;
     }
+    return a;
 }
 
 hipError_t rop_allow_lds() {
@@ -1254,80 +1135,52 @@ hipError_t rop_allow_lds() {
     return hipSuccess;
 }
 
+// The form, the rows per chunk and the LDS layouts are the plan's
+// (p.rop: rop_geometry, lds_shapes.cpp); nothing is sized here.
 hipError_t launch_net_rop(const psvi_plan& p, const NetRop& r, hipStream_t st) {
     if (r.dzd && p.lik != PSVI_LIK_GAUSSIAN) return hipErrorInvalidValue;
-    RopArgs a{};
-    rop_fill(p, a);
-    a.nsplit = rop_splits(p);
+    const RopGeometry& g = p.rop;
+    const bool mfma = g_diag.rop_valu != 1 && g.mfma_fits;
+    if (!mfma && g.valu.rc == 0) return hipErrorInvalidValue;
+    RopCommon a = rop_common(p);
+    a.nsplit = g.nsplit;
+    a.single = mfma ? 1 : g.single;
     // the targets' 4-byte slots: labels, or fp32 values the Gaussian head reads as such
     a.u = r.u; a.z = r.targets.slots(); a.w = r.w; a.x = r.x; a.xd = r.xd;
     a.params = r.params; a.vec = r.vec; a.eps = r.eps;
     a.G = r.G; a.Gd = r.Gd; a.du = r.du; a.nlld = r.nlld; a.dzd = r.dzd;
     a.stamps = g_diag.rop_stamps;
-    {
-        // the matrix-core form when a row block fits the LDS in one pass
-        // rows padded to a 16-multiple: the rows past a block's own are zero
-        // (the contraction over rows runs to the 16-multiple)
-        const int rows = (((p.d.M + a.nsplit - 1) / a.nsplit) + 15) & ~15;
-        const size_t lds = rop_mfma_carve(p, rows, &a) * 4;
-        if (g_diag.rop_valu != 1 && lds <= kRopLds) {
-            a.single = 1;
-            const dim3 grid(p.d.S, a.nsplit), block(512);
-            const bool fc = p.family == PSVI_FAMILY_FULLCOV;
-            if (fc)
-                hipLaunchKernelGGL((net_rop_mfma_kernel<true>), grid, block, lds, st, a);
-            else
-                hipLaunchKernelGGL((net_rop_mfma_kernel<false>), grid, block, lds, st, a);
-            if (a.nsplit > 1 && r.sum_slots) {
-                const int64_t n = (int64_t)p.d.S * p.n_tot;
-                hipLaunchKernelGGL(slot_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                                   r.G, r.Gd, n, a.nsplit);
-            }
-            return hipGetLastError();
-        }
-    }
-    // a workgroup's rows in one chunk when they fit without the LDS gradient
-    // accumulators (C3: 50 rows, 146 KB): every phase then runs once per
-    // workgroup instead of once per chunk
-    const int rows_per = (p.d.M + a.nsplit - 1) / a.nsplit;
-    const bool single = rop_carve(p, rows_per, nullptr, false) * 4 <= kRopLds;
-    const int rc = single ? rows_per : rop_rows(p);
-    if (rc == 0) return hipErrorInvalidValue;
-    const size_t lds = rop_carve(p, rc, &a, !single) * 4;
-    a.single = single ? 1 : 0;
-    hipLaunchKernelGGL(net_rop_kernel, dim3(p.d.S, a.nsplit), dim3(512), lds, st, a);
-    if (a.nsplit > 1 && r.sum_slots) {
+    const dim3 grid(p.d.S, g.nsplit), block(512);
+    if (!mfma)
+        hipLaunchKernelGGL(net_rop_kernel, grid, block, g.valu.bytes, st, a, g.valu);
+    else if (p.family == PSVI_FAMILY_FULLCOV)
+        hipLaunchKernelGGL((net_rop_mfma_kernel<true>), grid, block, g.mfma.bytes, st, a, g.mfma);
+    else
+        hipLaunchKernelGGL((net_rop_mfma_kernel<false>), grid, block, g.mfma.bytes, st, a, g.mfma);
+    if (g.nsplit > 1 && r.sum_slots) {
         const int64_t n = (int64_t)p.d.S * p.n_tot;
         hipLaunchKernelGGL(slot_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r.G,
-                           r.Gd, n, a.nsplit);
+                           r.Gd, n, g.nsplit);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_hvp_assemble(const psvi_plan& p, const HvpAssemble& r, hipStream_t st) {
-    RopArgs a{};
-    rop_fill(p, a);
+    RopCommon a = rop_common(p);
     a.params = r.params; a.vec = r.vec; a.eps = r.eps;
     a.G = const_cast<float*>(r.G);
     a.Gd = const_cast<float*>(r.Gd);
-    const float *du = r.du, *nlld = r.nlld;
-    float *hv = r.hv, *d_u = r.d_u, *d_w = r.d_w;
-    const int64_t slot2 = r.slot2;
     const float s0 = p.d.prior_sd;
     const int nbp = (int)((p.n_tot + 63) / 64), M = p.d.M, D = p.lay[0].din;
     const int64_t ndu = (int64_t)M * D;
-    const int nbu = d_u ? (int)((ndu + 63) / 64) : 0, nbw = d_w ? (M + 63) / 64 : 0;
+    const int nbu = r.d_u ? (int)((ndu + 63) / 64) : 0, nbw = r.d_w ? (M + 63) / 64 : 0;
     const dim3 pg((unsigned)(nbp + nbu + nbw)), pb(64 * kAsmWaves);
     const float is2 = 1.f / (s0 * s0), klw = r.include_kl ? 1.f : 0.f;
     const bool fc = p.family == PSVI_FAMILY_FULLCOV;
-    if (slot2 && fc)
-        hipLaunchKernelGGL((hvp_assemble_kernel<true, true>), pg, pb, 0, st, a, hv, is2, klw, slot2, nbp, du, ndu, d_u, nbu, nlld, d_w);
-    else if (slot2)
-        hipLaunchKernelGGL((hvp_assemble_kernel<true, false>), pg, pb, 0, st, a, hv, is2, klw, slot2, nbp, du, ndu, d_u, nbu, nlld, d_w);
-    else if (fc)
-        hipLaunchKernelGGL((hvp_assemble_kernel<false, true>), pg, pb, 0, st, a, hv, is2, klw, slot2, nbp, du, ndu, d_u, nbu, nlld, d_w);
-    else
-        hipLaunchKernelGGL((hvp_assemble_kernel<false, false>), pg, pb, 0, st, a, hv, is2, klw, slot2, nbp, du, ndu, d_u, nbu, nlld, d_w);
+    const auto kern = r.slot2 ? (fc ? hvp_assemble_kernel<true, true> : hvp_assemble_kernel<true, false>)
+                              : (fc ? hvp_assemble_kernel<false, true> : hvp_assemble_kernel<false, false>);
+    hipLaunchKernelGGL(kern, pg, pb, 0, st, a, r.hv, is2, klw, r.slot2, nbp, r.du, ndu, r.d_u, nbu, r.nlld,
+                       r.d_w);
     return hipGetLastError();
 }
 

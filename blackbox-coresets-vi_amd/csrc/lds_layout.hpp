@@ -3,10 +3,14 @@
 // regions, their order and their extents.  The kernel runs its layout function
 // on its LDS base and uses the pointers; the launcher and the shape solver run
 // it on a null base for the bytes, so the size a launch asks for and the
-// pointers the kernel forms come from the same walk.  (The network and R-op
-// kernels carry host-computed offsets in their argument structs instead:
-// net_carve, rop_carve, rop_mfma_carve.)
+// pointers the kernel forms come from the same walk.  The layouts: lap_fit_lds,
+// lap_full_lds, giga_lds, mffit_lds, pred_lds, km_lds, and the R-op's
+// rop_valu_lds / rop_mfma_lds, which yield float offsets that the plan holds
+// and the kernels take as an argument.  (The network kernel likewise carries
+// host-computed offsets: net_carve, kernels_net.hip.)
 #pragma once
+#include <utility>
+
 #include "psvi_internal.hpp"
 
 namespace psvi {
@@ -177,6 +181,88 @@ __host__ __device__ inline KmLds km_lds(void* base, int K, int DT, int XS, bool 
 inline int km_tile_cols(int D, int K) {
     const size_t x = km_lds(nullptr, K, 0, 1, true).bytes, cx = km_lds(nullptr, K, 1, 1, true).bytes;
     return (int)std::min<size_t>((size_t)D, (kKmLds - x) / cx);
+}
+
+// ---------------------------------------------------------- kernels_rop.hip
+// The R-op kernels take their layout as float offsets in a kernel argument
+// (RopValuLds, RopMfmaLds: psvi_internal.hpp), walked once per plan on the
+// host by rop_geometry; the walk of the offsets is the walk of the bytes.
+constexpr size_t kRopLds = 160 * 1024;
+struct LdsFloats {
+    size_t off = 0;
+    int take(size_t nfl) { return (int)std::exchange(off, off + nfl); }
+    int take4(size_t nfl) { return take((nfl + 3) & ~size_t(3)); }  // the next region 16-byte aligned
+};
+
+// net_rop_kernel at rc rows per chunk; with_g: the G / G_dot accumulators of
+// rows in several chunks
+inline RopValuLds rop_valu_lds(const psvi_plan& p, int rc, bool with_g) {
+    LdsFloats c;
+    RopValuLds v{};
+    v.rc = rc;
+    int maxd = 0, xtot = 0;
+    for (int l = 0; l < p.L; ++l) {
+        maxd = std::max(maxd, std::max(p.lay[l].din, p.lay[l].dout));
+        v.ldw[l] = p.lay[l].din | 1;
+        v.xo[l] = xtot;
+        xtot += p.lay[l].dout * v.ldw[l] + p.lay[l].dout;
+    }
+    v.maxd = ((maxd + 3) & ~3) | 1;
+    v.lx = c.take4(xtot);                                  // W_l rows, then b_l, layer by layer
+    v.lxd = c.take4(xtot);                                 // their tangents
+    v.lg = with_g ? c.take4(p.n_tot) : 0;                  // [n_tot]
+    v.lgd = with_g ? c.take4(p.n_tot) : 0;                 // [n_tot]
+    for (int l = 0; l <= p.L; ++l) {
+        const int d = l < p.L ? p.lay[l].din : p.lay[p.L - 1].dout;
+        v.lh[l] = c.take4((size_t)rc * d);                 // [rc][d]
+        v.lhd[l] = c.take4((size_t)rc * d);                // [rc][d]
+    }
+    v.ld0 = c.take4((size_t)rc * v.maxd);                  // [rc][maxd] each
+    v.ld1 = c.take4((size_t)rc * v.maxd);
+    v.ldd0 = c.take4((size_t)rc * v.maxd);
+    v.ldd1 = c.take4((size_t)rc * v.maxd);
+    v.bytes = sizeof(float) * c.off;
+    return v;
+}
+
+// net_rop_mfma_kernel for a row block of `rows`.  The activation regions come
+// first, so a 16-row tile's over-read past a region's rows stays inside the
+// allocation (tail slack when the weights after the last one are shorter than
+// that).
+inline RopMfmaLds rop_mfma_lds(const psvi_plan& p, int rows) {
+    const int L = p.L;
+    LdsFloats c;
+    RopMfmaLds m{};
+    for (int l = 0; l < L; ++l) m.kx[l] = (p.lay[l].din + 15) & ~15;
+    m.kx[L] = (p.lay[L - 1].dout + 15) & ~15;
+    for (int l = 0; l <= L; ++l) {
+        m.ldxm[l] = 2 * m.kx[l] + 8;  // == 8 (mod 16); X_0's tangent half is zero
+        m.mxo[l] = c.take((size_t)rows * m.ldxm[l]);       // [rows][ldxm]
+    }
+    const size_t x_end = c.off;
+    for (int l = 0; l < L; ++l) {
+        m.ldwm[l] = 2 * m.kx[l] + 8;
+        m.mwo[l] = c.take((size_t)m.kx[l + 1] * m.ldwm[l]);  // [kx_{l+1}][ldwm]
+    }
+    for (int l = 0; l < L; ++l) m.mbo[l] = c.take(2 * (size_t)m.kx[l + 1]);
+    const size_t over = (size_t)(((rows + 15) & ~15) - rows) * m.ldxm[L];
+    if (c.off - x_end < over) c.off = x_end + over;
+    c.off = (c.off + 3) & ~size_t(3);
+    m.lstamp = c.take(20);  // 10 uint64 phase clocks (diagnostics)
+    m.bytes = sizeof(float) * c.off;
+    // the load jobs: a job is one row of up to 64 columns
+    int j = 0;
+    for (int l = 0; l < L; ++l) {
+        m.jw[l] = j;
+        j += m.kx[l + 1] * ((m.kx[l] + 63) >> 6);
+    }
+    m.jb = j;
+    for (int l = 0; l < L; ++l) {
+        m.jbl[l] = j - m.jb;
+        j += (m.kx[l + 1] + 63) >> 6;
+    }
+    m.ju = j;
+    return m;
 }
 
 }  // namespace psvi

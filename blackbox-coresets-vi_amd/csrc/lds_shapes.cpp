@@ -33,6 +33,27 @@ int mfvi_fit_shape(const psvi_net_desc& d, MfviFitShape& s) {
     return PSVI_EUNSUP;
 }
 
+RopGeometry rop_geometry(const psvi_plan& p) {
+    RopGeometry g{};
+    g.nsplit = rop_splits(p);
+    const int rows_per = (p.d.M + g.nsplit - 1) / g.nsplit;
+    // the matrix-core form when a row block fits the LDS in one pass, its rows
+    // padded to a 16-multiple (the contraction over rows runs to it, over zeros)
+    g.mfma_rows = (rows_per + 15) & ~15;
+    g.mfma = rop_mfma_lds(p, g.mfma_rows);
+    g.mfma_fits = g.mfma.bytes <= kRopLds;
+    // VALU: the rows per chunk that fit beside the LDS gradient accumulators (a
+    // power of two up to 64; none: unsupported) -- or a workgroup's rows in one
+    // chunk when they fit without the accumulators (C3: 50 rows, 146 KB)
+    int rc = 0;
+    for (int r = 64; r >= 1 && !rc; r >>= 1)
+        if (rop_valu_lds(p, r, true).bytes <= kRopLds) rc = r;
+    if (!rc) return g;
+    g.single = rop_valu_lds(p, rows_per, false).bytes <= kRopLds;
+    g.valu = rop_valu_lds(p, g.single ? rows_per : rc, !g.single);
+    return g;
+}
+
 int predict_shape(const psvi_plan& p, int64_t rpd, PredictShape& s) {
     s = PredictShape{};
     s.L = p.L;

@@ -534,6 +534,7 @@ int build_plan(psvi_plan& p, std::string& err) {
         return fail(err, PSVI_EUNSUP, "layer too wide for the per-sample LDS network kernel");
     if (!sizes_ok(p)) return fail(err, PSVI_EUNSUP, "buffers beyond 2^31 floats are not supported");
     p.ws_bytes = step_ws(p, nullptr).bytes;
+    p.rop = rop_geometry(p);
     if (p.family != PSVI_FAMILY_FULLCOV) return 0;
     const int S = p.d.S;
     build_fwd_upd(p);

@@ -372,6 +372,43 @@ struct NetBand {
 
 struct NetArgs;  // kernels_net.hip
 
+// The R-op kernels' dynamic-LDS layouts (lds_layout.hpp: rop_valu_lds,
+// rop_mfma_lds) as float offsets from the LDS base, handed to the kernels by
+// value.  net_rop_kernel (VALU), rows in chunks of rc:
+struct RopValuLds {
+    int rc;    // rows per chunk
+    int maxd;  // odd row stride of the delta buffers
+    // W_l / W_dot_l: rows of an odd stride ldw[l] (a lane per output row then
+    // hits its own bank), layer l at xo[l] of the X (lx) / X_dot (lxd) regions,
+    // b after W
+    int lx, lxd, ldw[kMaxL], xo[kMaxL];
+    int lg, lgd;                         // G / G_dot accumulators [n_tot] (chunked rows only)
+    int lh[kMaxL + 1], lhd[kMaxL + 1];   // h_l / h_dot_l [rc][width_l]
+    int ld0, ld1, ldd0, ldd1;            // delta / delta_dot, double-buffered [rc][maxd]
+    size_t bytes;
+};
+// net_rop_mfma_kernel (matrix cores), a row block in one pass.  X_l (l = 0..L)
+// at mxo[l], rows of ldxm[l] floats = [h | h_dot] halves of kx[l] = rup16(width)
+// (X_0: the u rows alone; X_L: logits and their tangents); W2_l at mwo[l],
+// rup16(dout) rows of ldwm[l] = [W | W_dot] halves of kx[l]; b_l | b_dot_l at
+// mbo[l] (halves of kx[l + 1]); the diagnostics' phase clocks at lstamp.
+// Load jobs: layer l's W2 rows from jw[l], bias rows from jb + jbl[l], u rows from ju
+struct RopMfmaLds {
+    int mxo[kMaxL + 1], ldxm[kMaxL + 1], kx[kMaxL + 1], mwo[kMaxL], ldwm[kMaxL], mbo[kMaxL], lstamp;
+    int jw[kMaxL], jbl[kMaxL], jb, ju;
+    size_t bytes;
+};
+// What launch_net_rop launches for a plan (rop_geometry, lds_shapes.cpp): both
+// forms, since PSVI_DBG_ROP_VALU picks between them at launch time.
+struct RopGeometry {
+    int nsplit;       // workgroups per sample (row blocks), each with its own G / G_dot slot
+    bool mfma_fits;   // the matrix-core form's row block fits the LDS in one pass
+    int mfma_rows;    // its rows, padded to a 16-multiple
+    RopMfmaLds mfma;
+    int single;       // VALU: a workgroup's rows are one chunk (no LDS accumulators)
+    RopValuLds valu;  // valu.rc == 0: the model's weights alone do not fit (unsupported)
+};
+
 // Outer-objective passes of the network kernel (psvi_outer_elbo_grad).
 struct NetOuter {
     int mode;             // 1 forward (per-row NLL), 2 backward (row coefficients)
@@ -550,6 +587,7 @@ struct psvi_plan {
     int mchunks = 1, mc = 0, net_threads = 256, net_roles = 1;
     bool net_mloop = false;  // full-cov inner objective: the LDS-forced chunks looped in a workgroup
     size_t net_lds = 0;
+    psvi::RopGeometry rop{};  // psvi_hvp's R-op (mean-field and full-cov)
     size_t ws_bytes = 0;
     int64_t acc_count = 0;
     // LeNet: plan-owned activation / gradient scratch (kernels_lenet.hip)
@@ -1053,10 +1091,11 @@ hipError_t launch_cg_residual(int64_t n, const float* hv1, const float* hv2, dou
 hipError_t launch_cg_update(int64_t n, double* x, double* p, float* p32, const double* r,
                             const double* state, hipStream_t st);
 // Hessian-vector products (kernels_rop.hip)
-int rop_rows(const psvi_plan& p);
 // row blocks per sample (G / G_dot slots): two workgroups per sample while the
 // samples alone leave CUs idle
 inline int rop_splits(const psvi_plan& p) { return (p.d.S < 256 && p.d.M > 1) ? 2 : 1; }
+// the R-op's form choice, rows per chunk and LDS layouts (lds_shapes.cpp: host only)
+RopGeometry rop_geometry(const psvi_plan& p);
 struct NetRop {
     const float* u = nullptr;
     Targets targets;

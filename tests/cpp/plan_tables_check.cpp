@@ -4,7 +4,9 @@
 // workspace layout (workspace.hpp) is carved on a buffer of exactly the size it
 // reports and its regions are checked to lie inside, apart and aligned; every
 // kernel's dynamic-LDS layout (lds_layout.hpp) is held to the byte count it had
-// before that header and walked on a buffer of exactly that size.  Built with
+// before that header and walked on a buffer of exactly that size; the R-op's
+// geometry (psvi_plan::rop) is held to the recorded fixture given as the one
+// argument and its two layouts are walked likewise.  Built with
 // the host sanitizers by `make check-tables`; exit status 0 when all hold.
 #include <cstdio>
 #include <cstdlib>
@@ -708,6 +710,273 @@ void check_lds_kmeans() {
         }
 }
 
+// ------------------------------------------------------------ R-op geometry
+// tests/golden/w3_rop_geometry.json: per plan of a grid, what launch_net_rop
+// passed to its kernels before the geometry moved into the plan.  Every list
+// is preceded by its length and every record lists its numbers in one fixed
+// order, so the reader takes the file as the sequence of its integers outside
+// quoted strings.
+struct IntStream {
+    std::vector<long> v;
+    size_t at = 0;
+    bool load(const char* path) {
+        std::FILE* f = std::fopen(path, "rb");
+        if (!f) return false;
+        bool quoted = false, num = false, neg = false;
+        long x = 0;
+        for (int c; (c = std::fgetc(f)) != EOF;) {
+            if (quoted) {
+                if (c == '\\') (void)std::fgetc(f);
+                quoted = c != '"';
+                continue;
+            }
+            if (c >= '0' && c <= '9') {
+                x = 10 * x + (c - '0');
+                num = true;
+                continue;
+            }
+            if (num) v.push_back(neg ? -x : x);
+            num = neg = false;
+            x = 0;
+            quoted = c == '"';
+            neg = c == '-';
+        }
+        std::fclose(f);
+        return true;
+    }
+    bool over = false;  // read past the end
+    bool done() const { return at >= v.size(); }
+    long next() {
+        if (at < v.size()) return v[at++];
+        over = true;
+        return -1;
+    }
+};
+
+// a layout's regions (float offsets and extents) on a buffer of exactly its
+// bytes: apart, inside, 16-byte aligned, first and last float written (the
+// sanitizer's redzone right behind the buffer)
+struct FloatRegion {
+    const char* name;
+    int off;
+    size_t count;
+};
+void check_float_regions(size_t bytes, std::vector<FloatRegion> r) {
+    CHECK(bytes % sizeof(float) == 0);
+    const Buf buf(bytes);
+    float* base = reinterpret_cast<float*>(buf.p);
+    std::sort(r.begin(), r.end(), [](const FloatRegion& a, const FloatRegion& b) { return a.off < b.off; });
+    size_t end = 0;
+    for (const FloatRegion& q : r) {
+        if (q.count == 0) continue;
+        if (q.off < 0 || (size_t)q.off < end || q.off % 4 != 0 || (q.off + q.count) * sizeof(float) > bytes) {
+            if (++g_failed <= 50)
+                std::fprintf(stderr, "[%s] %s: offset %d, %zu floats, previous end %zu, total %zu bytes\n",
+                             g_what.c_str(), q.name, q.off, q.count, end, bytes);
+            return;
+        }
+        base[q.off] = 1.f;
+        base[q.off + q.count - 1] = 2.f;
+        end = q.off + q.count;
+    }
+}
+
+void check_rop_valu(const psvi_plan& p, const RopValuLds& v, bool with_g) {
+    const int L = p.L;
+    const size_t rc = v.rc, nt = p.n_tot;
+    size_t xtot = 0;
+    int wmax = 0;
+    for (int l = 0; l < L; ++l) {
+        // odd row strides: a lane per output row hits its own bank
+        CHECK(v.ldw[l] % 2 == 1 && v.ldw[l] >= p.lay[l].din && v.xo[l] == (int)xtot);
+        xtot += (size_t)p.lay[l].dout * v.ldw[l] + p.lay[l].dout;
+        wmax = std::max(wmax, std::max(p.lay[l].din, p.lay[l].dout));
+    }
+    CHECK(v.maxd % 2 == 1 && v.maxd >= wmax);
+    std::vector<FloatRegion> r{{"X", v.lx, xtot}, {"XD", v.lxd, xtot}};
+    if (with_g) {
+        r.push_back({"G", v.lg, nt});
+        r.push_back({"GD", v.lgd, nt});
+    } else {
+        CHECK(v.lg == 0 && v.lgd == 0);
+    }
+    for (int l = 0; l <= L; ++l) {
+        const size_t d = l < L ? p.lay[l].din : p.lay[L - 1].dout;
+        r.push_back({"h", v.lh[l], rc * d});
+        r.push_back({"hd", v.lhd[l], rc * d});
+    }
+    for (int o : {v.ld0, v.ld1, v.ldd0, v.ldd1}) r.push_back({"delta", o, rc * v.maxd});
+    check_float_regions(v.bytes, r);
+}
+
+void check_rop_mfma(const psvi_plan& p, const RopMfmaLds& m, int rows) {
+    const int L = p.L;
+    const size_t floats = m.bytes / sizeof(float), rows16 = (size_t)((rows + 15) & ~15);
+    std::vector<FloatRegion> r;
+    for (int l = 0; l <= L; ++l) {
+        const int width = l < L ? p.lay[l].din : p.lay[L - 1].dout;
+        // [h | h_dot] halves of kx and the stride's 8 floats; the halves are read as float4
+        CHECK(m.kx[l] % 16 == 0 && m.kx[l] >= width && m.kx[l] < width + 16);
+        CHECK(m.ldxm[l] == 2 * m.kx[l] + 8);
+        r.push_back({"X", m.mxo[l], (size_t)rows * m.ldxm[l]});
+        // a 16-row tile's reads past the region's rows stay inside the allocation
+        CHECK(m.mxo[l] + rows16 * m.ldxm[l] <= floats);
+    }
+    int jobs = 0;
+    for (int l = 0; l < L; ++l) {
+        CHECK(m.ldwm[l] == 2 * m.kx[l] + 8);
+        r.push_back({"W2", m.mwo[l], (size_t)m.kx[l + 1] * m.ldwm[l]});
+        r.push_back({"b", m.mbo[l], 2 * (size_t)m.kx[l + 1]});
+        // W2 jobs: a row of up to 64 columns each, layer by layer
+        CHECK(m.jw[l] == jobs);
+        jobs += m.kx[l + 1] * ((m.kx[l] + 63) / 64);
+    }
+    CHECK(m.jb == jobs);
+    for (int l = 0; l < L; ++l) {
+        CHECK(m.jb + m.jbl[l] == jobs);
+        jobs += (m.kx[l + 1] + 63) / 64;
+    }
+    CHECK(m.ju == jobs);
+    r.push_back({"stamps", m.lstamp, 20});  // 10 uint64
+    check_float_regions(m.bytes, r);
+}
+
+int g_rop_plans = 0, g_rop_class[7] = {0, 0, 0, 0, 0, 0, 0};
+
+// The fixture's numbers of one stack: each layout once (matrix-core by its
+// padded rows, VALU by rows per chunk and with_g), then what every (M, nsplit)
+// of the grid launches, refering to them.
+struct RopStack {
+    std::vector<int> dims;
+    std::map<int, std::vector<long>> mfma;                  // rows -> bytes, offsets, job table
+    std::map<std::pair<int, int>, std::vector<long>> valu;  // (rc, with_g) -> bytes, offsets
+    std::map<std::pair<int, int>, std::vector<long>> cases; // (M, nsplit) -> form[2], lds[2], fits, rows, rc, single
+    bool read(IntStream& in) {
+        const int L = (int)in.next();
+        if (L < 1 || L > kMaxL) return false;
+        for (int i = 0; i <= L; ++i) dims.push_back((int)in.next());
+        auto take = [&](std::vector<long>& v, int n) {
+            for (int i = 0; i < n; ++i) v.push_back(in.next());
+        };
+        for (long n = in.next(); n > 0; --n) take(mfma[(int)in.next()], 1 + 3 * (L + 1) + 3 * L + 1 + 2 * L + 2);
+        for (long n = in.next(); n > 0; --n) {
+            const int rc = (int)in.next(), with_g = (int)in.next();
+            take(valu[{rc, with_g}], 6 + 2 * (L + 1) + 4 + 2 * L);
+        }
+        for (long n = in.next(); n > 0; --n) {
+            const int M = (int)in.next(), nsplit = (int)in.next();
+            take(cases[{M, nsplit}], 8);
+        }
+        return !in.over;
+    }
+};
+void put(std::vector<long>& v, const int* a, int n) { v.insert(v.end(), a, a + n); }
+std::vector<long> flat(const RopMfmaLds& m, int L) {
+    std::vector<long> v{(long)m.bytes};
+    put(v, m.mxo, L + 1), put(v, m.ldxm, L + 1), put(v, m.kx, L + 1);
+    put(v, m.mwo, L), put(v, m.ldwm, L), put(v, m.mbo, L), v.push_back(m.lstamp);
+    put(v, m.jw, L), put(v, m.jbl, L), v.push_back(m.jb), v.push_back(m.ju);
+    return v;
+}
+std::vector<long> flat(const RopValuLds& q, int L) {
+    std::vector<long> v{(long)q.bytes, q.maxd, q.lx, q.lxd, q.lg, q.lgd};
+    put(v, q.lh, L + 1), put(v, q.lhd, L + 1);
+    for (int o : {q.ld0, q.ld1, q.ldd0, q.ldd1}) v.push_back(o);
+    put(v, q.ldw, L), put(v, q.xo, L);
+    return v;
+}
+
+// one plan of the grid against the fixture, then the layouts' structure
+void check_rop_plan(const RopStack& st, int family, int S, int M, int nsplit) {
+    g_what = "rop family=" + std::to_string(family);
+    for (int d : st.dims) g_what += "-" + std::to_string(d);
+    g_what += " S=" + std::to_string(S) + " M=" + std::to_string(M);
+    std::unique_ptr<psvi_plan> pp(new psvi_plan());
+    psvi_plan& p = *pp;
+    p.family = family;
+    p.d.n_layers = (int)st.dims.size() - 1;
+    for (size_t i = 0; i < st.dims.size(); ++i) p.d.dims[i] = st.dims[i];
+    p.d.S = S;
+    p.d.M = M;
+    p.d.prior_sd = 1.f;
+    p.world = 1;
+    p.rank = 0;
+    std::string err;
+    CHECK(build_plan(p, err) == 0);
+    ++g_rop_plans;
+    const RopGeometry& g = p.rop;
+    const int L = p.L;
+    const RopMfmaLds& m = g.mfma;
+    const RopValuLds& v = g.valu;
+    // what the launcher does with it under PSVI_DBG_ROP_VALU = 0 and 1
+    const bool refused = v.rc == 0;
+    const std::vector<long> now{refused ? 2 : g.mfma_fits ? 0 : 1, refused ? 2 : 1,
+                                refused ? 0 : (long)(g.mfma_fits ? m.bytes : v.bytes), refused ? 0 : (long)v.bytes,
+                                g.mfma_fits, g.mfma_rows, v.rc, g.single};
+    CHECK(g.nsplit == nsplit);
+    const auto c = st.cases.find({M, nsplit});
+    CHECK(c != st.cases.end() && c->second == now);
+    const auto fm = st.mfma.find(g.mfma_rows);
+    CHECK(fm != st.mfma.end() && fm->second == flat(m, L));
+    if (!refused) {
+        const auto fv = st.valu.find({v.rc, g.single ? 0 : 1});
+        CHECK(fv != st.valu.end() && fv->second == flat(v, L));
+    }
+    // structure
+    const int rows_per = (M + g.nsplit - 1) / g.nsplit;
+    CHECK(g.nsplit == rop_splits(p) && g.mfma_rows % 16 == 0 && g.mfma_rows >= rows_per && g.mfma_rows < rows_per + 16);
+    CHECK(g.mfma_fits == (m.bytes <= kRopLds));
+    check_rop_mfma(p, m, g.mfma_rows);
+    // the over-read rule at rows off the 16-multiple (the tail slack)
+    for (int rows : {1, 5, 17, rows_per}) check_rop_mfma(p, rop_mfma_lds(p, rows), rows);
+    if (refused) {
+        CHECK(g.single == 0 && rop_valu_lds(p, 1, true).bytes > kRopLds);
+        ++g_rop_class[6];
+        return;
+    }
+    CHECK(v.bytes <= kRopLds);
+    if (g.single) {
+        CHECK(v.rc == rows_per);
+    } else {
+        // the largest power of two up to 64 that fits beside the accumulators
+        CHECK(v.rc >= 1 && v.rc <= 64 && (v.rc & (v.rc - 1)) == 0);
+        CHECK(v.rc == 64 || rop_valu_lds(p, 2 * v.rc, true).bytes > kRopLds);
+        CHECK(rop_valu_lds(p, rows_per, false).bytes > kRopLds);
+    }
+    check_rop_valu(p, v, !g.single);
+    if (g.mfma_fits) ++g_rop_class[0];
+    if (!g.mfma_fits && g.single) ++g_rop_class[1];
+    if (!g.single) ++g_rop_class[v.rc == 64 ? 2 : v.rc == 32 ? 3 : v.rc == 16 ? 4 : 5];
+}
+
+void check_rop_geometry(const char* fixture) {
+    g_what = fixture;
+    IntStream in;
+    CHECK(in.load(fixture));
+    // the grid: S, M, families, nsplit of every (M, S), then the stacks
+    std::vector<long> grid[3];
+    for (auto& ax : grid)
+        for (long n = in.next(); n > 0 && !in.done(); --n) ax.push_back(in.next());
+    const std::vector<long>&Ss = grid[0], &Ms = grid[1], &fams = grid[2];
+    std::vector<long> nsplit(Ms.size() * Ss.size());
+    for (long& x : nsplit) x = in.next();
+    int plans = 0;
+    for (long n = in.next(); n > 0; --n) {
+        RopStack st;
+        g_what = fixture;
+        CHECK(st.read(in));
+        for (long fam : fams)
+            for (size_t i = 0; i < Ms.size(); ++i)
+                for (size_t j = 0; j < Ss.size(); ++j, ++plans)
+                    check_rop_plan(st, (int)fam, (int)Ss[j], (int)Ms[i], (int)nsplit[i * Ss.size() + j]);
+    }
+    g_what = fixture;
+    CHECK(in.done() && !in.over && plans == g_rop_plans && plans >= 700);
+    // the grid holds every class: matrix-core, VALU single without it, VALU
+    // chunked at 64, 32, 16 and below, unsupported
+    for (int c : g_rop_class) CHECK(c > 0);
+}
+
 // ------------------------------------------------------------------- plans
 std::unique_ptr<psvi_plan> make_plan(int family, const std::vector<int>& dims, int S, int M, int world,
                                      int rank) {
@@ -766,7 +1035,11 @@ void check_empty(int family, const char* name) {
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc != 2) {
+        std::fprintf(stderr, "usage: plan_tables_check tests/golden/w3_rop_geometry.json\n");
+        return 2;
+    }
     const std::vector<int> fn2{64, 40, 40, 2};
     for (int S : {128, 32, 96, 100, 130, 256, 1024}) check_fullcov(fn2, S, 1, 0);
     for (int r = 0; r < 8; ++r) check_fullcov(fn2, 1024, 8, r);
@@ -790,10 +1063,15 @@ int main() {
     check_lds_laplace();
     check_lds_mfvi_fit();
     check_lds_kmeans();
+    check_rop_geometry(argv[1]);
     if (g_failed) {
         std::fprintf(stderr, "plan_tables_check: %d failed checks\n", g_failed);
         return 1;
     }
     std::printf("plan_tables_check: %d plans ok, %d LDS layouts ok\n", g_plans, g_lds_cases);
+    std::printf("R-op geometry: %d plans ok; matrix-core %d, VALU single without it %d, chunked rc 64: %d, "
+                "32: %d, 16: %d, below: %d, unsupported %d\n",
+                g_rop_plans, g_rop_class[0], g_rop_class[1], g_rop_class[2], g_rop_class[3], g_rop_class[4],
+                g_rop_class[5], g_rop_class[6]);
     return 0;
 }

@@ -85,6 +85,17 @@ def test_hvp_fullsize_vs_oracle(case):
     ("fullcov", [(33, 17), (17, 5)], 300, 11),              # three sample passes, the last ragged
     ("meanfield", [(2, 100), (100, 4)], 32, 50),            # C2
     ("meanfield", [(5, 7), (7, 7), (7, 3)], 6, 70),
+    # the shapes above: matrix-core by default, the VALU kernel in one chunk
+    # under the switch.  The other branches of the plan's R-op geometry:
+    # matrix-core (48 padded rows, 136 KB) against the VALU kernel in chunks
+    # of 16, 16 and 8 rows
+    ("meanfield", [(120, 48), (48, 4)], 4, 80),
+    # a 200-row block is past the matrix-core form's LDS: the VALU kernel is
+    # the default, in chunks of 32 rows (full-cov), ...
+    ("fullcov", [(64, 40), (40, 40), (40, 2)], 4, 400),
+    # ... in one chunk of 350 rows, and in chunks of 64
+    ("meanfield", [(5, 7), (7, 7), (7, 3)], 4, 700),
+    ("meanfield", [(5, 7), (7, 7), (7, 3)], 4, 1100),
 ])
 def test_hvp_kernel_forms_agree(family, layers, S, M):
     """The matrix-core R-op (net_rop_mfma_kernel, the default where a row block

@@ -3,7 +3,8 @@
 plan_tables.cpp builds every table of a plan on the host.  The stand-alone
 program tests/cpp/plan_tables_check.cpp builds the plans of a list of shapes
 (no GPU use) and checks the streaming run table, the K-split and segmented
-tables, the forward items and the update chunks; `make check-tables` compiles
+tables, the forward items and the update chunks, and holds the R-op geometry of
+every plan of a grid to tests/golden/w3_rop_geometry.json; `make check-tables` compiles
 both with the address and undefined-behaviour sanitizers and runs the program.
 """
 import os
