@@ -12,7 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "psvi_internal.hpp"
+#include "mvn_common.hpp"  // diag_grad: the mean / sd gradient arithmetic shared with the full-cov head
 
 namespace psvi {
 
@@ -165,18 +165,11 @@ __global__ __launch_bounds__(256) void mf_update_kernel(MfUpdArgs a) {
     if (e < a.n_tot && grp == 0) {
         const int64_t pmu = a.poff[l] + idx, prho = pmu + a.n[l];
         const float mu = a.params[pmu], rho = a.params[prho];
-        const float sp = softplus_f(rho), sg = sigmoid_f(rho);
-        float gmu, grho;
-        if (SLOTS) {
-            gmu = sg_acc;
-            grho = sge_acc * sg;
-        } else {
-            gmu = a.acc[e];
-            grho = a.acc[a.n_tot + e] * sg;
-        }
-        if (a.include_kl && ((a.kl_mask >> l) & 1u)) {
-            gmu += mu * a.inv_s0sq;
-            grho += (sp * a.inv_s0sq - 1.f / sp) * sg;
+        const bool kl = a.include_kl && ((a.kl_mask >> l) & 1u);
+        float sp, gmu, grho;
+        diag_grad(mu, rho, SLOTS ? sg_acc : a.acc[e], SLOTS ? sge_acc : a.acc[a.n_tot + e], kl,
+                  a.inv_s0sq, sp, gmu, grho);
+        if (kl) {
             // _kl_normal_normal with q = N(0, s0): 0.5(vr + mu^2/s0^2 - 1 - log vr)
             const float vr = sp * sp * a.inv_s0sq;
             klp = 0.5f * (vr + mu * mu * a.inv_s0sq - 1.f - logf(vr));

@@ -437,7 +437,6 @@ template <bool PAIR>
 __global__ __launch_bounds__(PAIR ? 512 : 256, PAIR ? 1 : 2) void mvn_fwd_seg_bf_kernel(FwdArgs a) {
     constexpr int NG = PAIR ? 2 : 1;  // matrices (wave groups)
     __shared__ __attribute__((aligned(16))) uint8_t smb[3 * kSegEImg + NG * 3 * kSegLImg];
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
     const int gw = PAIR ? __builtin_amdgcn_readfirstlane(wave_id() >> 2) : 0;  // wave group
     const int wv = wave_id() & 3, tl = tid & 255;

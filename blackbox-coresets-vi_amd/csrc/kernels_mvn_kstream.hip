@@ -30,31 +30,13 @@ namespace psvi {
 // ordering the drain does not give.  The last arriver resets the counter in
 // the same launch; an aborted launch ends the process, so no half-counted
 // ticket reaches a later launch.
-struct KsArgs {
+struct KsArgs : MvnUpdCommon, MvnUpdGrad {
     const KsTile* tiles;
     const KsSeg* segs;
     const int* seg_off;
     float* slots;
     int* cnt;
     int64_t slot_bytes;
-    const float* eps;
-    const float* g;
-    int ldg, S;
-    int64_t g_total, e_total;
-    float* params;
-    float* m;
-    float* v;
-    double* kl_out;
-    int64_t pcount;
-    int include_kl;
-    float inv_s0sq, log_s0;
-    AdamC adam;
-    unsigned long long* stamps;  // diagnostics: 16 slots per workgroup (nullptr in production)
-    MvnLayerArgs lay[kMaxL];
-    // GRAD: the reparameterised gradient into grad_out instead of Adam (the
-    // HVP's J^T G_dot), + kl_vec / s0^2 on the corr entries when kl_vec is set
-    float* grad_out;
-    const float* kl_vec;
     const float* g2;  // GRAD: a second G slot added at staging (slot 0 + slot 1, as slot_sum_kernel)
 };
 
@@ -88,9 +70,7 @@ __global__ __launch_bounds__(256, 2) void mvn_kstream_kernel(KsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id(), h = lane >> 5, l32 = lane & 31;
     const int wr = wv >> 1, wc = wv & 1;
     const int col4 = tid & 15, srow = tid >> 4;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const FragPos fp{wr, wc, h, l32};
     const rsrc_t rs = make_rsrc(a.slots, a.slot_bytes);
     const rsrc_t rg = make_rsrc(a.g, 4 * a.g_total), re = make_rsrc(a.eps, 4 * a.e_total);
     const rsrc_t rg2 = make_rsrc(a.g2, GRAD && a.g2 ? 4 * a.g_total : 0);
@@ -430,10 +410,7 @@ __global__ __launch_bounds__(256, 2) void mvn_kstream_kernel(KsArgs a) {
         // -> T[r][c] in Es, then the rows' 256-byte runs of corr / m / v
         float* T = BF ? reinterpret_cast<float*>(&sh) : Es;
         if constexpr (BF) __syncthreads();  // the images are T now: every wave past its last reads
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(&T[(32 * wr + l32) * TLD + 32 * wc + 8 * g + 4 * h]) =
-                make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        store_frag_T(T, fp, acc);
         __syncthreads();
         const int cb = tl.k * UB + 4 * col4;
         float klt = 0.f;
@@ -461,29 +438,13 @@ __global__ __launch_bounds__(256, 2) void mvn_kstream_kernel(KsArgs a) {
                 mn[i] = mm;
                 vn[i] = vv;
             }
-            if (GRAD) {
-                if (cb + 3 < r) {
-                    *reinterpret_cast<float4*>(a.grad_out + o) = make_float4(pn[0], pn[1], pn[2], pn[3]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        if (cb + i < r) a.grad_out[o + i] = pn[i];
-                }
-                continue;
-            }
-            if (cb + 3 < r) {
-                *reinterpret_cast<float4*>(a.params + o) = make_float4(pn[0], pn[1], pn[2], pn[3]);
-                *reinterpret_cast<float4*>(a.m + o) = make_float4(mn[0], mn[1], mn[2], mn[3]);
-                *reinterpret_cast<float4*>(a.v + o) = make_float4(vn[0], vn[1], vn[2], vn[3]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    if (cb + i < r) {
-                        a.params[o + i] = pn[i];
-                        a.m[o + i] = mn[i];
-                        a.v[o + i] = vn[i];
-                    }
-            }
+            const float4 pn4 = make_float4(pn[0], pn[1], pn[2], pn[3]);
+            if (GRAD)
+                store_packed_run<1>({a.grad_out}, {pn4}, o, cb, r);
+            else
+                store_packed_run<3>({a.params, a.m, a.v},
+                                    {pn4, make_float4(mn[0], mn[1], mn[2], mn[3]),
+                                     make_float4(vn[0], vn[1], vn[2], vn[3])}, o, cb, r);
         }
         klp += klt * (0.5f * a.inv_s0sq);
         if (tl.diag) {
@@ -497,27 +458,19 @@ __global__ __launch_bounds__(256, 2) void mvn_kstream_kernel(KsArgs a) {
                 const float gm = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
                 const float gs = red[256 + tid] + red[320 + tid] + red[384 + tid] + red[448 + tid];
                 const int pm = pm_d, ps = ps_d;  // rr = r0 + tid
-                const float mu = dmu, sdr = dsd;
-                const float sp = softplus_f(sdr), sgm = sigmoid_f(sdr);
-                float gmean = gm, gsd = gs * sgm;
-                if (a.include_kl) {
-                    gmean += mu * a.inv_s0sq;
-                    gsd += (sp * a.inv_s0sq - 1.f / sp) * sgm;
-                    klp += a.log_s0 - logf(sp) + 0.5f * ((sp * sp + mu * mu) * a.inv_s0sq - 1.f);
-                }
+                float gmean, gsd;
+                diag_head(a, dmu, dsd, gm, gs, gmean, gsd, klp);
                 if (GRAD) {
                     a.grad_out[pm] = gmean;
                     a.grad_out[ps] = gsd;
                 } else {
-                float mm = dmm, vv = dmv;
-                a.params[pm] = adam_apply(a.adam, mu, gmean, mm, vv);
-                a.m[pm] = mm;
-                a.v[pm] = vv;
-                mm = dsm;
-                vv = dsv;
-                a.params[ps] = adam_apply(a.adam, sdr, gsd, mm, vv);
-                a.m[ps] = mm;
-                a.v[ps] = vv;
+                    adam_diag(a.adam, dmu, gmean, dmm, dmv, dsd, gsd, dsm, dsv, dmu, dsd);
+                    a.params[pm] = dmu;
+                    a.m[pm] = dmm;
+                    a.v[pm] = dmv;
+                    a.params[ps] = dsd;
+                    a.m[ps] = dsm;
+                    a.v[ps] = dsv;
                 }
             }
         }
@@ -540,36 +493,25 @@ __global__ __launch_bounds__(256, 2) void mvn_kstream_kernel(KsArgs a) {
     }
 }
 
-bool mvn_grad_takes_slots(const psvi_plan& p) {
-    return p.n_kwg() > 0 && !g_diag.ks_off && !g_diag.ks_bf_off;
-}
-
-// K = S > 128, or gradient mode on the slots (ks_grad): the K-split update,
-// then the next step's sample from the new parameters when asked
-hipError_t launch_mvn_kstream(const psvi_plan& p, const MvnUpdate& r, bool ks_grad, hipStream_t st) {
+// the K-split update (launch_mvn_update: K = S > 128, or gradient mode on the slots)
+hipError_t launch_mvn_kstream(const psvi_plan& p, const MvnUpdate& r, const MvnRoute& rt, hipStream_t st) {
     KsArgs k{};
     fill_update(p, r, k);
+    fill_grad(p, r, k);
     k.tiles = p.ks_tiles.dev;
     k.segs = p.ks_segs.dev;
     k.seg_off = p.ks_off.dev;
     k.slots = p.ks_slots.dev;
     k.cnt = p.ks_cnt.dev;
     k.slot_bytes = (int64_t)sizeof(float) * std::max(1, p.n_ks_slots) * kKsSlotFloats;
-    k.pcount = p.P;
-    k.grad_out = r.grad_out;
-    k.kl_vec = r.kl_vec;
     k.g2 = r.g_shard2;
     const dim3 grid(p.n_kwg()), block(256);
-    if (ks_grad)
+    if (rt.grad)
         hipLaunchKernelGGL((mvn_kstream_kernel<true, true>), grid, block, 0, st, k);
-    else if (g_diag.ks_bf_off || k.stamps)
+    else if (!rt.bf)
         hipLaunchKernelGGL(mvn_kstream_kernel<false>, grid, block, 0, st, k);
     else
         hipLaunchKernelGGL(mvn_kstream_kernel<true>, grid, block, 0, st, k);
-    if (r.next.eps) {
-        const hipError_t e = hipGetLastError();
-        return e != hipSuccess ? e : launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
-    }
     return hipGetLastError();
 }
 

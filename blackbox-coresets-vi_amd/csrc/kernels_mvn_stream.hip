@@ -27,28 +27,10 @@ namespace psvi {
 // c4 stored at c4 ^ (s & 15): the dL reads (one row, 32 columns) and the x'
 // reads (16 rows, one float4 column) are both bank-conflict free.
 // One barrier per tile (three at a band's end).
-struct StrArgs {
+struct StrArgs : MvnUpdCommon, MvnUpdTiled {  // stamps: the DIAG builds only
     const StreamRange* ranges;
     int nb[kMaxL];         // bands per layer
-    const float* eps;
-    const float* eps_next;
-    const float* g;
-    int ldg, S;
-    int64_t g_total, e_total;
-    float* params;
-    float* m;
-    float* v;
-    float* tp;
-    float* tm;
-    float* tv;
-    float* part;
-    double* kl_out;
-    int include_kl;
-    unsigned long long* stamps;    // diagnostics: 16 slots per workgroup (DIAG build only)
-    float inv_s0sq, log_s0;
-    AdamC adam;
     int xcol[kMaxL];
-    MvnLayerArgs lay[kMaxL];
     // mvn_stream_bf2_kernel: the bf16 planes of eps / eps_next (EpsPlanes layout)
     const uint16_t* ep;
     const uint16_t* enp;
@@ -87,7 +69,6 @@ __device__ __forceinline__ StrTile str_tile(const StrArgs& a, int l, int b, int 
     return T;
 }
 
-constexpr int kFoldMax = 64;  // band ends per run the in-kernel combine can take (FOLD)
 constexpr int kStrBuf = 128 * 16;  // float4 per eps block buffer ([128 samples][16 slots])
 typedef float f32x4 __attribute__((ext_vector_type(4)));  // plain vector loads / stores (no memcpy)
 
@@ -319,22 +300,10 @@ __global__ __launch_bounds__(256, 1) void mvn_stream_kernel(StrArgs a) {
             if (h == 0 && r < n) {
                 const int pm = (int)cur.poff + r, ps = pm + n;
                 const float mu = a.params[pm], sdr = a.params[ps];
-                const float sp = softplus_f(sdr), sg = sigmoid_f(sdr);
-                float gmean = dgm, gsd = dgs * sg;
-                if (a.include_kl) {
-                    gmean += mu * a.inv_s0sq;
-                    gsd += (sp * a.inv_s0sq - 1.f / sp) * sg;
-                    kld += a.log_s0 - logf(sp) + 0.5f * ((sp * sp + mu * mu) * a.inv_s0sq - 1.f);
-                }
-                float mm = a.m[pm], vv = a.v[pm];
-                a.params[pm] = adam_apply(a.adam, mu, gmean, mm, vv);
-                a.m[pm] = mm;
-                a.v[pm] = vv;
-                mm = a.m[ps];
-                vv = a.v[ps];
-                a.params[ps] = adam_apply(a.adam, sdr, gsd, mm, vv);
-                a.m[ps] = mm;
-                a.v[ps] = vv;
+                float gmean, gsd;
+                diag_head(a, mu, sdr, dgm, dgs, gmean, gsd, kld);
+                adam_diag(a.adam, mu, gmean, a.m[pm], a.v[pm], sdr, gsd, a.m[ps], a.v[ps], a.params[pm],
+                          a.params[ps]);
             }
         }
         ph(1);
@@ -390,7 +359,6 @@ __global__ __launch_bounds__(256, 1) void mvn_stream_kernel(StrArgs a) {
             }
             const int64_t o = frag_off(cur, g);
             if constexpr (SC1) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 const uint32_t ob = (uint32_t)(o * 4);
                 BSTORE128(
                     __builtin_bit_cast(u32x4, f32x4{pn[0], pn[1], pn[2], pn[3]}), rs_t, ob, 0, 16);
@@ -563,8 +531,6 @@ __global__ __launch_bounds__(512, 1) void mvn_stream_bf2_kernel(StrArgs a) {
     float* const Xd = reinterpret_cast<float*>(Eb);                  // dL partials: 8 waves x 8 x 64 (16 KB)
     uint32_t* const Xl = reinterpret_cast<uint32_t*>(Eb + 16384);    // L' pieces: 8 waves x 12 x 64 (24 KB)
     float* const Xg = reinterpret_cast<float*>(Eb + 40960);          // diagonal sums: 8 waves x 2 x 64 (4 KB)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
     const int q = wv & 3, hk = wv >> 2, wr = q >> 1, wc = q & 1, h = lane >> 5, l32 = lane & 31;
     const int pw = wv ^ 4;  // the partner wave (same quadrant, other sample half)
@@ -889,22 +855,9 @@ __global__ __launch_bounds__(512, 1) void mvn_stream_bf2_kernel(StrArgs a) {
             if (h == 0 && r < n) {
                 const int pm = (int)cur.poff + r, ps = pm + n;
                 const float mu = a.params[pm], sdr = a.params[ps];
-                const float sp = softplus_f(sdr), sg = sigmoid_f(sdr);
-                float gmean = dgm, gsd = dgs * sg;
-                if (a.include_kl) {
-                    gmean += mu * a.inv_s0sq;
-                    gsd += (sp * a.inv_s0sq - 1.f / sp) * sg;
-                    kld += a.log_s0 - logf(sp) + 0.5f * ((sp * sp + mu * mu) * a.inv_s0sq - 1.f);
-                }
-                float mm = a.m[pm], vv = a.v[pm];
-                const float mun = adam_apply(a.adam, mu, gmean, mm, vv);
-                a.m[pm] = mm;
-                a.v[pm] = vv;
-                mm = a.m[ps];
-                vv = a.v[ps];
-                const float sdn = adam_apply(a.adam, sdr, gsd, mm, vv);
-                a.m[ps] = mm;
-                a.v[ps] = vv;
+                float gmean, gsd, mun, sdn;
+                diag_head(a, mu, sdr, dgm, dgs, gmean, gsd, kld);
+                adam_diag(a.adam, mu, gmean, a.m[pm], a.v[pm], sdr, gsd, a.m[ps], a.v[ps], mun, sdn);
                 a.params[pm] = mun;
                 a.params[ps] = sdn;
                 if constexpr (FOLD) {
@@ -1106,13 +1059,6 @@ __global__ __launch_bounds__(512, 1) void mvn_stream_bf2_kernel(StrArgs a) {
     }
 }
 
-// the trainers' variants (higher / hypergrad Adam) at S = 128 (C3 and the
-// sharded C4 per-GPU count); other S take the chunked kernel (the stream
-// kernel's narrower instantiations spilled their scalar registers to scratch)
-bool stream_ok(int S, int kind) {
-    return S == 128 && (kind == PSVI_ADAM_HIGHER || kind == PSVI_ADAM_HYPERGRAD);
-}
-
 // The instantiations of one Adam kind; the diagnostics builds (DIAG: phase
 // stamps) exist for PSVI_ADAM_HIGHER only.  fp32 MFMAs, four 32-sample groups:
 template <int KIND>
@@ -1137,25 +1083,19 @@ static void launch_stream_bf(bool diag, bool fold, dim3 g, hipStream_t st, const
         hipLaunchKernelGGL(mvn_stream_bf2_kernel<KIND>, g, bl, 0, st, b);
 }
 
-// tiled state with next.eps on a stream_ok request (launch_mvn_update)
-hipError_t launch_mvn_stream(const psvi_plan& p, const MvnUpdate& r, hipStream_t st) {
+// the streaming update of a tiled-state step with a next one (launch_mvn_update)
+hipError_t launch_mvn_stream(const psvi_plan& p, const MvnUpdate& r, const MvnRoute& rt, hipStream_t st) {
     StrArgs b{};
     fill_update(p, r, b);
-    const int64_t tf = p.tiles_total * 4096;
+    fill_tiled(p, r, p.str_part.dev, b);
     b.ranges = p.str.dev;
-    b.eps_next = r.next.eps;
-    b.tp = r.tstate;
-    b.tm = r.tstate + tf;
-    b.tv = r.tstate + 2 * tf;
-    b.part = p.str_part.dev;
     for (int l = 0; l < p.L; ++l) {
         b.xcol[l] = p.xcol_l[p.rank][l];
         b.nb[l] = p.lay[l].nb;
     }
     const dim3 sg(p.str.n());
     const bool higher = b.adam.kind == PSVI_ADAM_HIGHER;
-    const bool bf = r.eps_planes && r.next.planes && p.bf_stream && r.padded && !g_diag.stream_bf_off;
-    if (bf) {
+    if (rt.kernel == MvnRoute::STREAM_BF) {
         b.stamps = g_diag.bf_stamps;
         b.ep = r.eps_planes;
         b.enp = r.next.planes;
@@ -1164,21 +1104,19 @@ hipError_t launch_mvn_stream(const psvi_plan& p, const MvnUpdate& r, hipStream_t
             b.ppoff[l] = p.eps_planes.poff[l];
             b.npad[l] = p.eps_planes.npad[l];
         }
-        const bool fold = p.str_cnt.dev && p.str_bms.dev && p.str_max_ends <= kFoldMax && !g_diag.stream_fold_off;
         b.rbs = p.sfrb.dev;
         b.bcnt = p.str_cnt.dev;
         b.bms = p.str_bms.dev;
         b.x = r.next.x;
         b.ldx = p.rows_tot[p.rank];
-        if (higher) launch_stream_bf<PSVI_ADAM_HIGHER>(b.stamps, fold, sg, st, b);
-        else launch_stream_bf<PSVI_ADAM_HYPERGRAD>(b.stamps, fold, sg, st, b);
-        if (fold) return hipGetLastError();
+        if (higher) launch_stream_bf<PSVI_ADAM_HIGHER>(b.stamps, rt.fold, sg, st, b);
+        else launch_stream_bf<PSVI_ADAM_HYPERGRAD>(b.stamps, rt.fold, sg, st, b);
     } else {
         const bool diag = b.stamps && b.S == 128;
         if (higher) launch_stream_f32<PSVI_ADAM_HIGHER>(diag, r.padded, sg, st, b);
         else launch_stream_f32<PSVI_ADAM_HYPERGRAD>(diag, r.padded, sg, st, b);
     }
-    return launch_next_reduce(p, r, p.sfrb.dev, p.sfrb.n(), p.str_part.dev, st);
+    return hipGetLastError();
 }
 
 }  // namespace psvi

@@ -1,38 +1,15 @@
 // kernels_mvn_update.hip -- the full-covariance update (backward): the chunked
-// kernel and its forms, the packed <-> tiled state converter, and
-// launch_mvn_update, the router over this unit's, the K-split and the
-// streaming launchers (see mvn_common.hpp).
+// kernel and its forms, the packed <-> tiled state converter, mvn_route (which
+// kernel a request takes) and launch_mvn_update, which switches on it over this
+// unit's, the K-split and the streaming launchers (see mvn_common.hpp).
 #include "mvn_common.hpp"
 
 namespace psvi {
 
-struct UpdArgs {
+// FUSE kernels: part holds the partial x_next per chunk slot
+struct UpdArgs : MvnUpdCommon, MvnUpdGrad, MvnUpdTiled {
     const UpdChunk* chunks;
-    const float* eps;
-    const float* g;    // g_shard [S][ldg]
-    int ldg, S;
-    int64_t g_total, e_total;  // floats in g_shard / eps (load guards)
-    float* params;
-    float* m;
-    float* v;
-    float* grad_out;   // GRAD mode output
-    const float* kl_vec;  // GRAD mode, nullable: + kl_vec / s0^2 on the corr entries (the
-                          // KL Hessian's corr block in an HVP: kl_vec = the direction)
-    double* kl_out;    // nullable
-    int64_t pcount;    // parameter vector length
-    int include_kl;
-    int abl;                       // diagnostics ablation mask (0 in production)
-    unsigned long long* stamps;    // diagnostics: 16 slots per workgroup (nullptr in production)
-    float inv_s0sq, log_s0;
-    AdamC adam;
-    // fused next-step sample (FUSE kernels): partial x_next per chunk slot
-    const float* eps_next;
-    float* part;
-    // tiled corr / m / v (TILED kernels)
-    float* tp;
-    float* tm;
-    float* tv;
-    MvnLayerArgs lay[kMaxL];
+    int abl;  // diagnostics ablation mask (0 in production)
 };
 
 template <bool GRAD>
@@ -78,6 +55,7 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
     float* Es = sh.Es;
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id(), h = lane >> 5, l32 = lane & 31;
     const int wr = wv >> 1, wc = wv & 1;
+    const FragPos fp{wr, wc, h, l32};
     const int n = a.lay[ch.layer].n;
     const int eoff = (int)a.lay[ch.layer].eoff;
     const float* E = a.eps + eoff;  // [S][n]; the whole eps buffer is [-eoff, e_rem)
@@ -311,7 +289,6 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
                 } else if (!(a.abl & 8)) {
                     // write-through (sc1): the state leaves the XCD's L2, which keeps
                     // the eps / G blocks other chunks re-read (as the stream kernel)
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                     const rsrc_t rs_t = make_rsrc(a.tp, 0x7fffffff);
                     const int tmb = __builtin_amdgcn_readfirstlane((int)((a.tm - a.tp) * 4));
                     const int tvb = __builtin_amdgcn_readfirstlane((int)((a.tv - a.tp) * 4));
@@ -324,8 +301,7 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
                         __builtin_bit_cast(u32x4, make_float4(vn[0], vn[1], vn[2], vn[3])), rs_t, ob, tvb, 16);
                 }
                 if (FUSE)  // L_new fragment -> the [r][c] tile for the sample GEMM
-                    *reinterpret_cast<float4*>(&Es[(32 * wr + l32) * TLD + 32 * wc + 8 * g + 4 * h]) =
-                        make_float4(pn[0], pn[1], pn[2], pn[3]);
+                    frag_T(Es, fp, g) = make_float4(pn[0], pn[1], pn[2], pn[3]);
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = 0.f;
@@ -336,26 +312,15 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
                 const int cb = (ch.k0 + ti) * UB + 4 * col4;
 #pragma unroll
                 for (int ai = 0; ai < 3; ++ai) {
-                    const float* kk = ai == 0 ? kp : ai == 1 ? km : kv;
-                    float* dst = ai == 0 ? a.params : ai == 1 ? a.m : a.v;
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<float4*>(&T[(32 * wr + l32) * TLD + 32 * wc + 8 * g + 4 * h]) =
-                            make_float4(kk[4 * g], kk[4 * g + 1], kk[4 * g + 2], kk[4 * g + 3]);
+                    store_frag_T(T, fp, ai == 0 ? kp : ai == 1 ? km : kv);
                     __syncthreads();
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int rr = ch.r0 + srow + 16 * j;
                         if (!rown[j] || cb >= rr) continue;
-                        const int o = rowp[j] + cb;
-                        const float4 d4 = *reinterpret_cast<const float4*>(&T[(srow + 16 * j) * TLD + 4 * col4]);
-                        if (cb + 3 < rr) {
-                            *reinterpret_cast<float4*>(dst + o) = d4;
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 3; ++i)
-                                if (cb + i < rr) dst[o + i] = f4get(d4, i);
-                        }
+                        store_packed_run<1>({ai == 0 ? a.params : ai == 1 ? a.m : a.v},
+                                            {*reinterpret_cast<const float4*>(&T[(srow + 16 * j) * TLD + 4 * col4])},
+                                            rowp[j] + cb, cb, rr);
                     }
                     __syncthreads();
                 }
@@ -364,10 +329,7 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
         }
         // D[i = c][j = r]: j = lane & 31, i = (q & 3) + 8 (q >> 2) + 4 h  ->  T[r][c] in Es
         float* T = Es;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(&T[(32 * wr + l32) * TLD + 32 * wc + 8 * g + 4 * h]) =
-                make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        store_frag_T(T, fp, acc);
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[q] = 0.f;
         __syncthreads();
@@ -405,7 +367,6 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
                     vn[i] = vv;
                 }
             }
-            float* dp = GRAD ? a.grad_out : a.params;
             if (FUSE) {  // L_new row segment (strict lower part only)
                 float4 lv;
                 lv.x = cb + 0 < r ? pn[0] : 0.f;
@@ -414,6 +375,7 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
                 lv.w = cb + 3 < r ? pn[3] : 0.f;
                 *reinterpret_cast<float4*>(&T[(srow + 16 * j) * TLD + 4 * col4]) = lv;
             }
+            float* dp = GRAD ? a.grad_out : a.params;
             if (cb + 3 < r) {
                 *reinterpret_cast<float4*>(dp + o) = make_float4(pn[0], pn[1], pn[2], pn[3]);
                 if (!GRAD) {
@@ -542,14 +504,8 @@ __device__ __forceinline__ void upd_chunk(const UpdArgs& a, const UpdChunk& ch,
             const float gm = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
             const float gs = red[256 + tid] + red[320 + tid] + red[384 + tid] + red[448 + tid];
             const int pm = poff + rr, ps = pm + n;
-            const float mu = a.params[pm], sdr = a.params[ps];
-            const float sp = softplus_f(sdr), sg = sigmoid_f(sdr);
-            float gmean = gm, gsd = gs * sg;
-            if (a.include_kl) {
-                gmean += mu * a.inv_s0sq;
-                gsd += (sp * a.inv_s0sq - 1.f / sp) * sg;
-                klp += a.log_s0 - logf(sp) + 0.5f * ((sp * sp + mu * mu) * a.inv_s0sq - 1.f);
-            }
+            float gmean, gsd;
+            diag_head(a, a.params[pm], a.params[ps], gm, gs, gmean, gsd, klp);
             upd_elem<GRAD>(a, pm, gmean);
             upd_elem<GRAD>(a, ps, gsd);
         }
@@ -705,56 +661,92 @@ static void launch_chunked(int mode, dim3 grid, hipStream_t st, const UpdArgs& a
     else hipLaunchKernelGGL((mvn_update_kernel<GRAD, 0, FUSE, TILED, PKO>), grid, block, 0, st, a);
 }
 
-hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t st) {
-    UpdArgs a{};
-    fill_update(p, r, a);
-    a.kl_vec = r.kl_vec;
-    a.chunks = p.upd.dev;
-    a.grad_out = r.grad_out;
-    a.abl = g_diag.upd_ablation;
-    a.pcount = p.P;
-    if (p.upd.n() == 0) return hipSuccess;
-    const dim3 grid(p.upd.n());
-    const int mode = a.S > USB ? 2 : a.S > UEH ? 1 : 0;  // samples per LDS pass
+// the streaming kernels exist for the trainers' variants (higher / hypergrad
+// Adam) at S = 128 (C3 and the sharded C4 per-GPU count); other S take the
+// chunked kernel (the stream kernel's narrower instantiations spilled their
+// scalar registers to scratch)
+static bool stream_ok(int S, int kind) {
+    return S == 128 && (kind == PSVI_ADAM_HIGHER || kind == PSVI_ADAM_HYPERGRAD);
+}
+// gradient mode (the HVP's J^T G_dot) at any S on the bf16-piece K-split kernel
+bool mvn_grad_takes_slots(const psvi_plan& p) {
+    return p.n_kwg() > 0 && !g_diag.ks_off && !g_diag.ks_bf_off;
+}
+
+// Which kernel a request takes, in which form, and what follows it: decided
+// here and nowhere else, at launch time (the request and g_diag's A/B switches).
+static MvnRoute mvn_route(const psvi_plan& p, const MvnUpdate& r) {
+    MvnRoute t{};
+    const int S = p.d.S;
+    t.mode = S > USB ? 2 : S > UEH ? 1 : 0;
     if (r.tstate) {
-        // tiled state (psvi_inner_loop on a fusable plan): corr / m / v in tstate
-        if (r.next.eps && p.str.n() > 0 && g_diag.stream_off != 1 && stream_ok(a.S, a.adam.kind))
-            return launch_mvn_stream(p, r, st);
-        const int64_t tf = p.tiles_total * 4096;
-        a.tp = r.tstate;
-        a.tm = r.tstate + tf;
-        a.tv = r.tstate + 2 * tf;
-        if (r.next.eps) {
-            a.eps_next = r.next.eps;
-            a.part = p.upd_part.dev;
-            launch_chunked<false, true, true>(mode, grid, st, a);
-            return launch_next_reduce(p, r, p.ufrb.dev, p.ufrb.n(), p.upd_part.dev, st);
+        // tiled state (psvi_inner_loop on a fusable plan): Adam only; with a next
+        // step the streaming kernels, else (or switched off) the chunked forms
+        t.tiled = true;
+        const int kind = r.hp ? r.hp->kind : PSVI_ADAM_HIGHER;
+        if (r.next.eps && p.str.n() > 0 && g_diag.stream_off != 1 && stream_ok(S, kind)) {
+            const bool bf = r.eps_planes && r.next.planes && p.bf_stream && r.padded && !g_diag.stream_bf_off;
+            t.kernel = bf ? MvnRoute::STREAM_BF : MvnRoute::STREAM_F32;
+            t.fold = bf && p.str_cnt.dev && p.str_bms.dev && p.str_max_ends <= kFoldMax &&
+                     !g_diag.stream_fold_off;
+            t.after = t.fold ? MvnRoute::NONE : MvnRoute::REDUCE_SFRB;
+            return t;
         }
-        if (r.packed_out) launch_chunked<false, false, true, true>(mode, grid, st, a);
-        else launch_chunked<false, false, true>(mode, grid, st, a);
-        return hipGetLastError();
+        t.fuse = r.next.eps != nullptr;
+        t.pko = !t.fuse && r.packed_out;
+        t.after = t.fuse ? MvnRoute::REDUCE_UFRB : MvnRoute::NONE;
+        return t;
     }
-    // gradient mode (the HVP's J^T G_dot) at any S on the bf16-piece K-split kernel
-    const bool ks_grad = r.grad_out && mvn_grad_takes_slots(p);
-    if (r.g_shard2 && !ks_grad) return hipErrorInvalidValue;
-    if ((mode == 2 && !r.grad_out && p.n_kwg() > 0 && g_diag.ks_off != 1) || ks_grad)
-        return launch_mvn_kstream(p, r, ks_grad, st);
-    if (r.next.eps && !r.grad_out) {
-        if (!(p.fuse_sample && mode < 2)) {
-            // no fusion for this plan: update, then sample from the new params
-            MvnUpdate plain = r;
-            plain.next = MvnUpdate::Next{};
-            const hipError_t e = launch_mvn_update(p, plain, st);
-            return e != hipSuccess ? e : launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
-        }
-        a.eps_next = r.next.eps;
-        a.part = p.upd_part.dev;
-        launch_chunked<false, true>(mode, grid, st, a);
-        return launch_next_reduce(p, r, p.ufrb.dev, p.ufrb.n(), p.upd_part.dev, st);
+    t.grad = r.grad_out != nullptr;
+    const bool ks_grad = t.grad && mvn_grad_takes_slots(p);
+    if ((t.mode == 2 && !t.grad && p.n_kwg() > 0 && g_diag.ks_off != 1) || ks_grad) {
+        // K = S > 128, or gradient mode on the slots; fp32 MFMAs for the A/B and the stamps
+        t.kernel = MvnRoute::KSPLIT;
+        t.bf = ks_grad || !(g_diag.ks_bf_off || g_diag.upd_stamps);
+        t.after = r.next.eps ? MvnRoute::FWD : MvnRoute::NONE;
+        return t;
     }
-    if (r.grad_out) launch_chunked<true>(mode, grid, st, a);
-    else launch_chunked<false>(mode, grid, st, a);
-    return hipGetLastError();
+    if (r.next.eps && !t.grad) {
+        // the fused sample where the plan has it, else the sample kernel on the new params
+        t.fuse = p.fuse_sample && t.mode < 2;
+        t.after = t.fuse ? MvnRoute::REDUCE_UFRB : MvnRoute::FWD;
+    }
+    return t;
+}
+
+hipError_t launch_mvn_update(const psvi_plan& p, const MvnUpdate& r, hipStream_t st) {
+    if (p.upd.n() == 0) return hipSuccess;
+    const MvnRoute t = mvn_route(p, r);
+    // a second G slot is the K-split gradient kernel's alone
+    if (r.g_shard2 && !r.tstate && !(t.kernel == MvnRoute::KSPLIT && t.grad)) return hipErrorInvalidValue;
+    hipError_t e;
+    if (t.kernel == MvnRoute::KSPLIT) {
+        e = launch_mvn_kstream(p, r, t, st);
+    } else if (t.kernel != MvnRoute::CHUNKED) {
+        e = launch_mvn_stream(p, r, t, st);
+    } else {
+        UpdArgs a{};
+        fill_update(p, r, a);
+        fill_grad(p, r, a);
+        fill_tiled(p, r, p.upd_part.dev, a);
+        a.chunks = p.upd.dev;
+        a.abl = g_diag.upd_ablation;
+        const dim3 grid(p.upd.n());
+        if (t.grad) launch_chunked<true>(t.mode, grid, st, a);
+        else if (t.tiled && t.fuse) launch_chunked<false, true, true>(t.mode, grid, st, a);
+        else if (t.tiled && t.pko) launch_chunked<false, false, true, true>(t.mode, grid, st, a);
+        else if (t.tiled) launch_chunked<false, false, true>(t.mode, grid, st, a);
+        else if (t.fuse) launch_chunked<false, true>(t.mode, grid, st, a);
+        else launch_chunked<false>(t.mode, grid, st, a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return e;
+    switch (t.after) {
+    case MvnRoute::REDUCE_UFRB: return launch_next_reduce(p, r, p.ufrb.dev, p.ufrb.n(), p.upd_part.dev, st);
+    case MvnRoute::REDUCE_SFRB: return launch_next_reduce(p, r, p.sfrb.dev, p.sfrb.n(), p.str_part.dev, st);
+    case MvnRoute::FWD: return launch_mvn_fwd(p, r.next.eps, r.params, r.next.x, st);
+    default: return hipSuccess;
+    }
 }
 
 }  // namespace psvi

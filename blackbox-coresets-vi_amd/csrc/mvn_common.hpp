@@ -64,6 +64,8 @@ inline void fill_layers(const psvi_plan& p, MvnLayerArgs* la) {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short bf8v __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ floatx16 mfma6(const bf8v (&x)[3], const bf8v (&y)[3], floatx16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2], y[0], c, 0, 0, 0);
@@ -162,9 +164,35 @@ struct UpdShared {
     float red[2 * 4 * 64];
 };
 
-// the fields UpdArgs, StrArgs and KsArgs share by name
-template <class Args>
-inline void fill_update(const psvi_plan& p, const MvnUpdate& r, Args& a) {
+// What every full-cov update kernel takes: UpdArgs, StrArgs and KsArgs derive
+// from it and add only their own fields.
+struct MvnUpdCommon {
+    const float* eps;
+    const float* g;  // g_shard [S][ldg]
+    int ldg, S;
+    int64_t g_total, e_total;  // floats in g_shard / eps (load guards)
+    float *params, *m, *v;
+    double* kl_out;  // nullable
+    int include_kl;
+    unsigned long long* stamps;  // diagnostics: 16 slots per workgroup (nullptr in production)
+    float inv_s0sq, log_s0;
+    AdamC adam;
+    MvnLayerArgs lay[kMaxL];
+};
+// the packed-state kernels (chunked, K-split): the parameter count and gradient mode
+struct MvnUpdGrad {
+    int64_t pcount;       // parameter vector length
+    float* grad_out;      // GRAD mode output (the HVP's J^T G_dot instead of Adam)
+    const float* kl_vec;  // GRAD mode, nullable: + kl_vec / s0^2 on the corr entries (an HVP's direction)
+};
+// the tiled-state kernels (chunked TILED / FUSE, streaming): + the next draw, the partial x_next slots
+struct MvnUpdTiled {
+    float *tp, *tm, *tv;
+    const float* eps_next;
+    float* part;
+};
+
+inline void fill_update(const psvi_plan& p, const MvnUpdate& r, MvnUpdCommon& a) {
     a.eps = r.eps;
     a.g = r.g_shard;
     a.ldg = p.rows_tot[p.rank];
@@ -183,14 +211,111 @@ inline void fill_update(const psvi_plan& p, const MvnUpdate& r, Args& a) {
     if (r.hp) a.adam = make_adam(r.hp);
     fill_layers(p, a.lay);
 }
+inline void fill_grad(const psvi_plan& p, const MvnUpdate& r, MvnUpdGrad& a) {
+    a.pcount = p.P;
+    a.grad_out = r.grad_out;
+    a.kl_vec = r.kl_vec;
+}
+inline void fill_tiled(const psvi_plan& p, const MvnUpdate& r, float* part, MvnUpdTiled& a) {
+    if (r.tstate) {
+        a.tp = r.tstate;
+        a.tm = a.tp + p.tiles_total * 4096;
+        a.tv = a.tm + p.tiles_total * 4096;
+    }
+    a.eps_next = r.next.eps;
+    a.part = part;
+}
 
-// launch_mvn_update's routes (each in its kernel's unit) and the next step's
-// reduce: x_next = mean' + softplus(sd') eps_next + the sum of each row
-// block's partial slots (kernels_mvn_fwd.hip)
+// The diagonal head: a band row's mean / sd gradients from its sums over the
+// samples, gm = sum_s G and gs = sum_s G eps (kl: + the KL's):
+//   sp = softplus(sdr), sg = sigmoid(sdr)
+//   gmean = gm (+ mu / s0^2),  gsd = gs sg (+ (sp / s0^2 - 1 / sp) sg)
+__device__ __forceinline__ void diag_head(float mu, float sdr, float gm, float gs, bool kl, float inv_s0sq,
+                                          float log_s0, float& sp, float& gmean, float& gsd, float& klp) {
+    sp = softplus_f(sdr);
+    const float sg = sigmoid_f(sdr);
+    gmean = gm;
+    gsd = gs * sg;
+    if (kl) {
+        gmean += mu * inv_s0sq;
+        gsd += (sp * inv_s0sq - 1.f / sp) * sg;
+        klp += log_s0 - logf(sp) + 0.5f * ((sp * sp + mu * mu) * inv_s0sq - 1.f);
+    }
+}
+__device__ __forceinline__ void diag_grad(float mu, float sdr, float gm, float gs, bool kl,
+                                          float inv_s0sq, float& sp, float& gmean, float& gsd) {
+    float unused = 0.f;
+    diag_head(mu, sdr, gm, gs, kl, inv_s0sq, 0.f, sp, gmean, gsd, unused);
+}
+__device__ __forceinline__ void diag_head(const MvnUpdCommon& a, float mu, float sdr, float gm,
+                                          float gs, float& gmean, float& gsd, float& klp) {
+    float sp;
+    diag_head(mu, sdr, gm, gs, a.include_kl, a.inv_s0sq, a.log_s0, sp, gmean, gsd, klp);
+}
+// Adam on a band row's mean and sd entries, given their moments (registers, or
+// the state in memory: read and written in place, the mean's before the sd's)
+__device__ __forceinline__ void adam_diag(const AdamC& ad, float mu, float gmean, float& mm, float& mv,
+                                          float sd, float gsd, float& sm, float& sv, float& mun,
+                                          float& sdn) {
+    float m_ = mm, v_ = mv;
+    mun = adam_apply(ad, mu, gmean, m_, v_);
+    mm = m_;
+    mv = v_;
+    m_ = sm;
+    v_ = sv;
+    sdn = adam_apply(ad, sd, gsd, m_, v_);
+    sm = m_;
+    sv = v_;
+}
+
+// The update accumulator D[i = c][j = r] (j = lane & 31, i = (q & 3) + 8 (q >> 2)
+// + 4 h) of wave (wr, wc): float4 g (entries 4 g .. 4 g + 3) in the transposed
+// tile T[r][c], and all four from x (the accumulators, or 16 floats in their order)
+struct FragPos {
+    int wr, wc, h, l32;
+};
+__device__ __forceinline__ float4& frag_T(float* T, const FragPos& f, int g) {
+    return *reinterpret_cast<float4*>(&T[(32 * f.wr + f.l32) * TLD + 32 * f.wc + 8 * g + 4 * f.h]);
+}
+template <class X>
+__device__ __forceinline__ void store_frag_T(float* T, const FragPos& f, const X& x) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) frag_T(T, f, g) = make_float4(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]);
+}
+// One row's float4 run of N packed arrays -- columns cb .. cb + 3 of row r at
+// packed offset o: whole left of the diagonal, element by element (the strict
+// lower part) on the run that crosses it
+template <int N>
+__device__ __forceinline__ void store_packed_run(float* const (&dst)[N], const float4 (&x)[N], int o,
+                                                 int cb, int r) {
+    if (cb + 3 < r) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) *reinterpret_cast<float4*>(dst[k] + o) = x[k];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            if (cb + i < r) {
+#pragma unroll
+                for (int k = 0; k < N; ++k) dst[k][o + i] = f4get(x[k], i);
+            }
+    }
+}
+
+// The route of one update request: the kernel, its form, and what follows it
+// (mvn_route decides, launch_mvn_update switches: kernels_mvn_update.hip)
+struct MvnRoute {
+    enum Kernel { CHUNKED, STREAM_F32, STREAM_BF, KSPLIT } kernel;
+    bool grad, fuse, tiled, pko;  // CHUNKED's template flags; grad: KSPLIT's too
+    bool fold;                    // STREAM_BF: the band combine in the kernel
+    bool bf;                      // KSPLIT: the dL GEMM on bf16 pieces
+    int mode;                     // CHUNKED: samples per LDS pass (0: <= 64, 1: <= 128, 2: more)
+    enum After { NONE, REDUCE_UFRB, REDUCE_SFRB, FWD } after;
+};
+// x_next = mean' + softplus(sd') eps_next + each row block's partial slots (kernels_mvn_fwd.hip)
 hipError_t launch_next_reduce(const psvi_plan& p, const MvnUpdate& r, const FwdRowBlock* rbs,
                               int nrb, const float* part, hipStream_t st);
-bool stream_ok(int S, int kind);
-hipError_t launch_mvn_stream(const psvi_plan& p, const MvnUpdate& r, hipStream_t st);
-hipError_t launch_mvn_kstream(const psvi_plan& p, const MvnUpdate& r, bool ks_grad, hipStream_t st);
+hipError_t launch_mvn_stream(const psvi_plan& p, const MvnUpdate& r, const MvnRoute& rt, hipStream_t st);
+hipError_t launch_mvn_kstream(const psvi_plan& p, const MvnUpdate& r, const MvnRoute& rt, hipStream_t st);
+constexpr int kFoldMax = 64;  // band ends per run the in-kernel combine can take (FOLD)
 
 }  // namespace psvi

@@ -98,6 +98,59 @@ def test_stream_update_equals_chunked(layers, S, kind):
         assert np.abs(a - b).max() <= 1e-7 * np.abs(b).max(), k
 
 
+def test_mean_sd_bitwise_across_routes():
+    """The mean / sd entries of params, m and v bit for bit the same from the
+    chunked packed kernel, the chunked tiled kernel (converted back) and the
+    fp32 streaming kernel: all three sum the samples in the same order and go
+    through one diagonal head (diag_head / adam_diag in mvn_common.hpp).
+    n = 91 (two bands, a 27-row tail) and n = 28 (one band)."""
+    from psvi.runtime import InnerLoopPlan
+
+    DBG_STREAM_BF_OFF = 24
+    layers, S = [(6, 13), (13, 2)], 128
+    plan = InnerLoopPlan("fullcov", layers, S, 10)
+    rng, p0, m0, v0 = _case(layers, S, 17)
+    t = lambda a: torch.tensor(a, device=DEV)
+    eps0 = t(rng.standard_normal(plan.eps_count).astype(np.float32))
+    eps1 = t(rng.standard_normal(plan.eps_count).astype(np.float32))
+    gs = t((0.05 * rng.standard_normal(plan.xshard_count)).astype(np.float32))
+    head = []  # the mean and sd entries: the first 2 n of each layer's block
+    off = 0
+    for din, dout in layers:
+        n = din * dout + dout
+        head.append(np.arange(off, off + 2 * n))
+        off += 2 * n + (n - 1) * (n - 2) // 2
+    head = np.concatenate(head)
+    out = {}
+    for route in ("packed", "tiled", "stream"):
+        p, m, v = t(p0), t(m0), t(v0)
+        kl = torch.zeros(1, dtype=torch.float64, device=DEV)
+        kw = dict(step=3, lr=1e-3, kind="higher", kl_out=kl, include_kl=True)
+        if route == "packed":
+            plan.mvn_update(eps0, gs, p, m, v, **kw)
+        else:
+            ts = plan.tiled_state()
+            plan.tiled_convert(p, m, v, ts, True)
+            if route == "tiled":  # no next step: the chunked tiled form
+                plan.mvn_update_tiled(eps0, gs, p, m, v, ts, **kw)
+            else:
+                x = torch.empty(plan.xshard_count, device=DEV)
+                _lib().psvi_debug_set(DBG_STREAM_BF_OFF, 1)
+                try:
+                    plan.mvn_update_tiled(eps0, gs, p, m, v, ts, eps_next=eps1, x_next=x, **kw)
+                finally:
+                    _lib().psvi_debug_set(DBG_STREAM_BF_OFF, 0)
+            plan.tiled_convert(p, m, v, ts, False)
+        torch.cuda.synchronize()
+        out[route] = [a.cpu().numpy()[head] for a in (p, m, v)]
+    assert not np.array_equal(out["packed"][0], p0[head])  # the step moved them
+    for route in ("tiled", "stream"):
+        for a, b, what in zip(out[route], out["packed"], "pmv"):
+            nd = int((a != b).sum())
+            print(f"{route} vs packed, {what}: {nd} of {a.size} mean / sd entries differ")
+            assert np.array_equal(a, b), (route, what, nd)
+
+
 def test_c3_inner_loop_stream_matches_oracle():
     """Three chained C3 steps through psvi_inner_loop (fused, tiled, streaming)
     against the chunked kernel's loop (tight) and the float64 oracle's
