@@ -147,6 +147,21 @@ int psvi_mfvi_fit(const psvi_mfvi_fit_req* q, void* stream) {
     return 0;
 }
 
+int psvi_predict_query(const psvi_plan* p, int32_t rows_per_draw, int64_t* out) {
+    if (!p || !out) return fail(PSVI_EINVAL, "null pointer");
+    if (p->family != PSVI_FAMILY_MEANFIELD || p->lik != PSVI_LIK_CATEGORICAL || p->world != 1)
+        return fail(PSVI_ESTATE, "the predictive scores need a mean-field categorical plan of world 1");
+    if (rows_per_draw < 1) return fail(PSVI_EINVAL, "rows_per_draw must be >= 1");
+    PredictShape s;
+    if (predict_shape(*p, rows_per_draw, s) != 0)
+        return fail(PSVI_EUNSUP, "a layer of the network does not fit the predictive scores' LDS "
+                                 "budget: one unit's weights and one row's activations exceed 160 KiB");
+    out[0] = s.RG;
+    out[1] = s.wcap;
+    for (int l = 0; l < kMaxL; ++l) out[2 + l] = l < s.L ? s.ut[l] : 0;
+    return 0;
+}
+
 int psvi_predict_scores(const psvi_predict_scores_req* q, void* stream) {
     if (!q) return fail(PSVI_EINVAL, "null request");
     const psvi_plan* p = q->plan;

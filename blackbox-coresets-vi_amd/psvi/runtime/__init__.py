@@ -3,4 +3,4 @@ from ._lib import PsviError, load  # noqa: F401
 from .engine import (InnerLoopPlan, adam_adjoint_, adam_update_, make_adam, nonfinite_,  # noqa: F401
                      randn_, check_binary, select_scores, select_weight_grad, laplace_fit,
                      laplace_sample_full, laplace_scores, giga_step, mfvi_fit, mfvi_fit_query, coreset_draw, predict_scores,
-                     kmeans, kmeans_query)
+                     predict_query, kmeans, kmeans_query)

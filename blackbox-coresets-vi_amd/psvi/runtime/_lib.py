@@ -252,6 +252,7 @@ SIGNATURES = {
     "psvi_giga_step": (_I32, [ctypes.POINTER(GigaStepReq), _P]),
     "psvi_coreset_draw": (_I32, [ctypes.POINTER(CoresetDrawReq), _P]),
     "psvi_predict_scores": (_I32, [ctypes.POINTER(PredictScoresReq), _P]),
+    "psvi_predict_query": (_I32, [_P, _I32, ctypes.POINTER(_I64)]),
     "psvi_kmeans": (_I32, [ctypes.POINTER(KmeansReq), _P]),
     "psvi_kmeans_query": (_I32, [_I32, _I32, _I32, ctypes.POINTER(_I64)]),
     "psvi_hvp": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -989,7 +989,20 @@ def predict_scores(plan, x, z, eps, params, rows_per_draw, want=PREDICT_OUTPUTS,
     return out
 
 
-DRAW_STATUS = {1: "a weight is negative or not finite", 2: "the weights sum to zero",
+def predict_query(plan, rows_per_draw):
+    """How psvi_predict_scores cuts a plan's work at rows_per_draw
+    (psvi_predict_query; no device needed): a dict with rows_per_group,
+    tile_floats (the W tile in LDS) and units_per_tile (per layer; less than
+    the layer's width where the layer runs in several tiles)."""
+    if not isinstance(plan, InnerLoopPlan):
+        raise ValueError("plan must be an InnerLoopPlan")
+    out = (ctypes.c_int64 * (2 + _lib.MAX_LAYERS))()
+    check(plan.lib.psvi_predict_query(plan.handle, int(rows_per_draw), out), "psvi_predict_query")
+    return {"rows_per_group": int(out[0]), "tile_floats": int(out[1]),
+            "units_per_tile": [int(out[2 + l]) for l in range(len(plan.layers))]}
+
+
+DRAW_STATUS = {1:"a weight is negative or not finite", 2: "the weights sum to zero",
                3: "fewer positive weights than rows to draw without replacement"}
 
 

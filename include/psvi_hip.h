@@ -953,6 +953,13 @@ typedef struct psvi_predict_scores_req {
     double* stats_out;         /* [2]: correct count, sum_j -log p_j[z_j]    (nullable)   */
 } psvi_predict_scores_req;
 int psvi_predict_scores(const psvi_predict_scores_req* req, void* stream);
+/* What psvi_predict_scores does with `plan` at rows_per_draw (no device
+ * needed): out[0] = the rows of a group, out[1] = the floats of the W tile in
+ * LDS, out[2 + l] = the output units per tile of layer l (less than the
+ * layer's width: the layer runs in several tiles); out holds
+ * 2 + PSVI_MAX_LAYERS values, zero past the last layer.  Errors as
+ * psvi_predict_scores' for the plan and rows_per_draw. */
+int psvi_predict_query(const psvi_plan* plan, int32_t rows_per_draw, int64_t* out);
 
 /* ---- second order (the `hyper` trainer's implicit hypergradient) ----------
  * Hessian-vector product of the negative inner ELBO (psvi_inner_step's

@@ -26,6 +26,46 @@ def test_nonfinite_flag():
             assert int(flag.item()) == 1
 
 
+CAP = 1024 * 256          # psvi_nonfinite's launch: at most 1024 workgroups of 256 threads
+N_FLAG2 = CAP + 13        # a second pass of 13 elements
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+def test_nonfinite_flag_past_the_grid_cap(dt):
+    """One bad value at the first element, at the last of the first pass, at
+    the first of the second pass and at the end; a clean tensor leaves the
+    flag as it finds it, 0 or 1."""
+    from psvi.runtime import nonfinite_
+
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(N_FLAG2, generator=g, dtype=dt).cuda()
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    nonfinite_(flag, x)
+    assert int(flag.item()) == 0
+    y = x.clone()
+    for at in (0, CAP - 1, CAP, N_FLAG2 - 1):
+        for bad in (float("nan"), float("inf"), -float("inf")):
+            y[at] = bad
+            flag.zero_()
+            nonfinite_(flag, y)
+            assert int(flag.item()) == 1, (at, bad)
+            flag.zero_()
+            nonfinite_(flag, x, y)          # the bad value in the second tensor only
+            assert int(flag.item()) == 1, (at, bad)
+        y[at] = x[at]
+    nonfinite_(flag, x)                     # a flag at 1 is not cleared
+    assert int(flag.item()) == 1
+    flag.zero_()
+    nonfinite_(flag, y)
+    assert int(flag.item()) == 0
+    one = torch.ones(1, dtype=dt, device="cuda")
+    nonfinite_(flag, one)
+    assert int(flag.item()) == 0
+    one[0] = float("inf")
+    nonfinite_(flag, one)
+    assert int(flag.item()) == 1
+
+
 def _ps():
     from psvi.inference import PSVILearnV
     from psvi.models import make_fcnet

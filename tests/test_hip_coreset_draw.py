@@ -217,3 +217,71 @@ def test_wrapper():
         coreset_draw(few, 3, False, 0, 0)
     with pytest.raises(ValueError):
         coreset_draw(w, M + 1, False, 0, 0)
+
+
+# --------------------------------------------------------------------------
+# Past the first trip of the capped launches: the draws run on at most 512
+# workgroups x 256 threads x 4 draws (a second pass from n > 524,288), the
+# gather's row loop on at most 4096 workgroups x 4 waves (n > 16,384), its
+# targets loop on 4096 x 256 threads (n > 1,048,576); the float4 row copy's
+# lane loop takes a second trip from D / 4 > 64.  _raw keeps the sentinel pad
+# around every output and asserts it intact.
+N_DRAW2 = 524_288 + 5
+N_ROWS2 = 16_384 + 3
+N_TARGETS2 = 1_048_576 + 7
+
+
+def test_replace_second_pass_exact_weights():
+    """Exact weights: every index equals the restatement's, on a 16-byte
+    aligned idx_out (int4 stores) and on one offset by one int (the scalar
+    stores of the launcher's vec == false path)."""
+    M, n = 257, N_DRAW2
+    w = _exact_weights(M, zeros=True)
+    wd = torch.tensor(w, device=DEV)
+    ref, st_ref = CD.replace(w, n, SEED, OFFSETS[2])
+    assert st_ref == 0
+    for pad in (4, 1):
+        got, _, _, st = _raw(wd, n, True, SEED, OFFSETS[2], pad=pad)
+        assert st == 0 and np.array_equal(got, ref), pad
+
+
+def test_replace_second_pass_generic_weights():
+    M, n, seed = 257, N_DRAW2, REPLACE_SEEDS[0]
+    w = _generic_weights(M, seed)
+    ref, st, t, C = CD.replace(w, n, seed, 8, detail=True)
+    unsafe = CD.replace_unsafe(t, C)
+    assert st == 0 and unsafe.mean() <= 1e-3
+    got, _, _, st = _raw(torch.tensor(w, device=DEV), n, True, seed, 8)
+    assert st == 0
+    assert np.array_equal(got[~unsafe], ref[~unsafe])
+    assert (w[got] > 0).all()
+
+
+@pytest.mark.parametrize("D", [3, 260, 257])
+def test_gather_rows_second_pass(D):
+    """More rows than the gather's 16,384 waves: D = 3 the scalar copy, 260 the
+    float4 copy at 65 float4 per row (a second lane trip), 257 the scalar copy
+    at five lane trips."""
+    M, n = 300, N_ROWS2
+    rng = np.random.default_rng(D)
+    w = _exact_weights(M, zeros=False)
+    rows = torch.tensor(rng.standard_normal((M, D)).astype(np.float32), device=DEV)
+    targets = torch.tensor(rng.integers(-2**31, 2**31 - 1, M).astype(np.int32), device=DEV)
+    idx, r_out, t_out, st = _raw(torch.tensor(w, device=DEV), n, True, SEED, 0, rows=rows,
+                                 targets=targets)
+    assert st == 0
+    assert np.array_equal(idx, CD.replace(w, n, SEED, 0)[0])
+    assert np.array_equal(r_out.view(np.int32), rows.cpu().numpy()[idx].view(np.int32))
+    assert np.array_equal(t_out, targets.cpu().numpy()[idx])
+
+
+def test_gather_targets_second_pass():
+    """More targets than the gather's 1,048,576 threads; no rows."""
+    M, n = 300, N_TARGETS2
+    rng = np.random.default_rng(9)
+    w = _exact_weights(M, zeros=False)
+    targets = torch.tensor(rng.integers(-2**31, 2**31 - 1, M).astype(np.int32), device=DEV)
+    idx, r_out, t_out, st = _raw(torch.tensor(w, device=DEV), n, True, SEED, 4, targets=targets)
+    assert st == 0 and r_out is None
+    assert np.array_equal(idx, CD.replace(w, n, SEED, 4)[0])
+    assert np.array_equal(t_out, targets.cpu().numpy()[idx])

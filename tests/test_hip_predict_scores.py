@@ -24,6 +24,22 @@ CASES = {
     "two_hidden": dict(layers=[(7, 33), (33, 33), (33, 10)], S=5, n=70, rpd=70),
     "c2_s1": dict(layers=[(6, 5), (5, 2)], S=1, n=67, rpd=16),
 }
+# Past the first trip of the capped loops.  The item loop runs on at most
+# kPredMaxGrid = 2048 workgroups and the statistics kernel's kPredThreads = 256
+# threads stride over their partials: 2050 items, and 6151 rows in blocks of 3
+# (2051 items, the last one ragged).  The sigma kernel covers 64 x 256 = 16,384
+# elements of a layer per pass: 130 x 127 + 127 = 16,637.  A layer runs in
+# several weight tiles when ut < dout: at 64 rows of 350 inputs a group's
+# inputs leave the tile 28 of the 50 units (asserted from psvi_predict_query).
+# "safe": the rows whose float64 top-two gap is >= 1e-3 at seed 0, counted with
+# the restatement alone.
+CAPPED = {
+    "items_2050": dict(layers=[(5, 3)], S=2, n=2050, rpd=1, safe=2048),
+    "items_6151_ragged": dict(layers=[(5, 3)], S=2, n=6151, rpd=3, safe=6148),
+    "sigma_16637": dict(layers=[(130, 127), (127, 3)], S=1, n=5, rpd=5, safe=5),
+    "two_tiles": dict(layers=[(350, 50), (50, 3)], S=2, n=70, rpd=64, safe=70),
+}
+CASES.update(CAPPED)
 
 
 def _t(a, dtype=torch.float32):
@@ -56,7 +72,11 @@ def _run(c, want=ALL, state=None, stats=True, z=True, params=None):
     return out
 
 
-def _check(out, ref, C):
+def _check(out, ref, C, safe_rows=None):
+    """safe_rows=None: every row's float64 top-two gap is at least 1e-3 and
+    ``correct`` is compared on all of them.  safe_rows=k: exactly k rows have
+    such a gap (counted on the CPU from the restatement for the case's seed),
+    ``correct`` is compared on those and the correct count within the others."""
     caps = dict(least_conf=1.0, entropy=np.log(C), el2n=np.sqrt(2.0))
     assert rel(out["mean_logits"].cpu().numpy(), ref["mean_logits"]) < 1e-4
     for k, cap in caps.items():
@@ -64,18 +84,50 @@ def _check(out, ref, C):
         err = np.abs(got - ref[k])
         print(k, "max err", err.max())
         assert (err <= 1e-4 * np.abs(ref[k]) + 1e-4 * cap).all(), k
-    assert R.top2_gap(ref["mean_logits"]).min() >= 1e-3
-    assert np.array_equal(out["correct"].cpu().numpy(), ref["correct"])
+    safe = R.top2_gap(ref["mean_logits"]) >= 1e-3
+    assert safe.all() if safe_rows is None else int(safe.sum()) == safe_rows
+    correct = out["correct"].cpu().numpy()
+    assert np.array_equal(correct[safe], ref["correct"][safe])
     st = out["stats"].cpu().numpy()
-    assert st[0] == ref["stats"][0] and abs(st[1] - ref["stats"][1]) <= 1e-4 * abs(ref["stats"][1])
+    assert st[0] == correct.sum() and abs(st[0] - ref["stats"][0]) <= (~safe).sum()
+    assert abs(st[1] - ref["stats"][1]) <= 1e-4 * abs(ref["stats"][1])
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
+@pytest.mark.parametrize("name", sorted(set(CASES) - set(CAPPED)))
 def test_against_restatement(name):
     c = _case(name)
     ref = R.scores(R.mean_logits(c["layers"], c["S"], c["params"], c["eps"], c["x"], c["rpd"]),
                    c["z"])
     _check(_run(c), ref, c["layers"][-1][1])
+
+
+@pytest.mark.parametrize("name", sorted(CAPPED))
+def test_past_one_trip_against_restatement(name):
+    """Every output on every row within _check's tolerances; ``correct`` on the
+    rows with a top-two gap (at least 99 % of them: 2048 of 2050, 6148 of
+    6151, all of the others).  Then the same launch without the statistics --
+    no barrier then separates an item's scoring from the next item's staging
+    -- gives the same bits on every row."""
+    from psvi.runtime import InnerLoopPlan, predict_query
+
+    c = _case(name)
+    assert c["safe"] >= 0.99 * c["n"]
+    q = predict_query(InnerLoopPlan("meanfield", c["layers"], c["S"], 3), c["rpd"])
+    if name == "two_tiles":
+        assert q["units_per_tile"][0] < c["layers"][0][1], q       # ut < dout: the tile loop
+    if name == "sigma_16637":
+        assert c["layers"][0][0] * c["layers"][0][1] + c["layers"][0][1] > 64 * 256
+    if name.startswith("items"):
+        items = -(-c["n"] // c["rpd"]) * -(-c["rpd"] // q["rows_per_group"])
+        assert items > 2048
+    ref = R.scores(R.mean_logits(c["layers"], c["S"], c["params"], c["eps"], c["x"], c["rpd"]),
+                   c["z"])
+    out = _run(c)
+    _check(out, ref, c["layers"][-1][1], safe_rows=c["safe"])
+    quiet = _run(c, stats=False)
+    assert sorted(quiet) == sorted(ALL)
+    for k in ALL:
+        assert torch.equal(quiet[k], out[k]), k
 
 
 def test_zero_row_under_zero_mean_net():

@@ -344,3 +344,120 @@ def test_experiment_driver_runs_sparsebbvi(tmp_path):
     assert set(r) == {"accs", "nlls", "csizes", "times", "elbos"}
     assert len(r["accs"]) == 3 and np.isfinite(r["accs"]).all() and np.isfinite(r["nlls"]).all()
     assert r["csizes"][0] == 0 and r["csizes"][-1] >= 1
+
+
+# --------------------------------------------------------------------------
+# The one-workgroup selection kernels past the first trip of their loops:
+# kSelThreads = 512 threads stride over the samples (S > 512, up to kSelMaxS =
+# 2048), over the columns (Nu + B > 512) and over grad_w (Nu > 512).
+SEL_SHAPES = [(513, 0, 1), (1025, 513, 600), (2048, 3, 515)]
+
+
+def _sel_inputs(S, Nu, B, seed):
+    """ll at log-likelihood scale (negative, 0.5 to 10), nkl and core weights
+    whose weighted sums spread the samples' softmax weights over a few units."""
+    g = torch.Generator().manual_seed(seed)
+    ll = -(0.5 + 9.5 * torch.rand(S, Nu + B, generator=g))
+    nkl = 2.0 * torch.randn(S, generator=g, dtype=torch.float64)
+    w = (0.5 + 2 * torch.rand(Nu, generator=g)) * (3.0 / max(Nu, 1))
+    return ll, nkl, w
+
+
+def _scores_dev(ll, nkl, w, Nu, scale):
+    from psvi.runtime.engine import select_scores
+
+    sc = select_scores(dev(ll), dev(nkl, torch.float64), dev(w) if Nu else None, Nu, scale)
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in sc.items() if v is not None}
+
+
+@pytest.mark.parametrize("S,Nu,B", SEL_SHAPES)
+def test_scores_past_one_trip(S, Nu, B):
+    ll, nkl, w = _sel_inputs(S, Nu, B, S + Nu + B)
+    scale = 1000.0 / B
+    a, b = _scores_dev(ll, nkl, w, Nu, scale), _scores_dev(ll, nkl, w, Nu, scale)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    W, corr, corecorr = U.scores(ll.double(), nkl, U.t64(w), Nu, scale)
+    res = a["result"].tolist()
+    print(f"scores S {S} Nu {Nu} B {B}: W rel {rel(a['W'], W):.2e} corr rel {rel(a['corr'], corr):.2e}")
+    assert rel(a["W"], W) < 1e-6 and rel(a["corr"], corr) < 1e-6
+    assert corr[int(res[1])] >= corr.max() - 1e-6 * corr.max().abs()
+    assert res[0] == pytest.approx(float(corr.max()), rel=1e-6)
+    if Nu:
+        assert rel(a["corecorr"], corecorr) < 1e-6
+        assert res[2] == pytest.approx(float(corecorr.max()), rel=1e-6)
+        assert res[3] == (1.0 if res[0] > res[2] else 0.0)
+    else:
+        assert res[3] == 1.0
+
+
+@pytest.mark.parametrize("other", [300, 3])
+def test_argmax_takes_the_first_of_equal_maxima_across_trips(other):
+    """The winning data column, as bits, in columns 4 and 4 + 512 (one thread's
+    first and second trip) and in a column of another thread, above (300) or
+    below (3) them.  A column's sums run in sample order whichever thread owns
+    it, so equal columns score equal bits; the lowest index must win."""
+    S, Nu, B = SEL_SHAPES[2]
+    ll, nkl, w = _sel_inputs(S, Nu, B, 77)
+    scale = 1000.0 / B
+    win = int(_scores_dev(ll, nkl, w, Nu, scale)["result"][1])
+    col = ll[:, Nu + win].clone()
+    for j in (4, 4 + 512, other):           # global columns; data index j - Nu
+        ll[:, j] = col
+    tied = [c for c in range(B) if torch.equal(ll[:, Nu + c], col)]
+    assert {4 - Nu, 4 + 512 - Nu, other - Nu} <= set(tied) and len(tied) <= 4
+    _, corr, _ = U.scores(ll.double(), nkl, U.t64(w), Nu, scale)
+    rest = torch.ones(B, dtype=torch.bool)
+    rest[tied] = False
+    assert corr[tied].min() > corr[rest].max() + 1e-4 * corr.abs().max()   # the tied columns lead
+    a = _scores_dev(ll, nkl, w, Nu, scale)
+    res = a["result"].tolist()
+    cb = a["corr"].view(torch.int32)
+    assert len({int(cb[c]) for c in tied}) == 1
+    assert int(res[1]) == min(tied), (res, tied)
+    assert res[0] == pytest.approx(float(corr.max()), rel=1e-6)
+    assert res[3] == (1.0 if res[0] > res[2] else 0.0)
+
+
+def _weight_dev(ll, nkl, w, N):
+    from psvi.runtime.engine import select_weight_grad
+
+    loss, gw = select_weight_grad(dev(ll), dev(nkl, torch.float64), dev(w), N)
+    torch.cuda.synchronize()
+    return loss.cpu(), gw.cpu()
+
+
+@pytest.mark.parametrize("S,Nu,B,late_max", [(1025, 513, 600, False), (2048, 3, 515, False),
+                                             (1025, 513, 600, True)])
+def test_weight_objective_past_one_trip(S, Nu, B, late_max):
+    """late_max: the samples of the first trip lie 800 below those from s = 512
+    on, so lw spans more than 700 and sel_softmax's maximum is one the second
+    trip finds (exp of a difference to the first trip's maximum overflows)."""
+    ll, nkl, w = _sel_inputs(S, Nu, B, 3 * S + Nu + B)
+    if late_max:
+        nkl[:512] -= 800.0
+    N = 1000.0
+    a, b = _weight_dev(ll, nkl, w, N), _weight_dev(ll, nkl, w, N)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    loss, gw = U.weight_objective(ll.double(), nkl, U.t64(w), N)
+    if late_max:
+        lw = -N / Nu * (-ll[:, :Nu].double() @ U.t64(w)) + nkl
+        assert lw.max() - lw[:512].max() > 700 and int(lw.argmax()) >= 512
+    print(f"weights S {S} Nu {Nu} B {B} late {late_max}: loss rel {rel(a[0], loss):.2e} "
+          f"grad rel {rel(a[1], gw):.2e}")
+    assert torch.isfinite(a[0]).all() and torch.isfinite(a[1]).all()
+    assert rel(a[0], loss) < 1e-9 and rel(a[1], gw) < 1e-6
+
+
+def test_more_samples_than_the_lds_holds_are_refused():
+    from psvi.runtime import PsviError
+    from psvi.runtime.engine import select_scores, select_weight_grad
+
+    S = 2049                                  # kSelMaxS + 1
+    ll, nkl, w = _sel_inputs(S, 3, 5, 1)
+    with pytest.raises(PsviError):
+        select_scores(dev(ll), dev(nkl, torch.float64), dev(w), 3, 2.0)
+    with pytest.raises(PsviError):
+        select_weight_grad(dev(ll), dev(nkl, torch.float64), dev(w), 10.0)
+    torch.cuda.synchronize()

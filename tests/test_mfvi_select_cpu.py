@@ -133,6 +133,30 @@ def test_wrapper_checks():
         predict_scores(None, x, None, x, x, 2)
 
 
+def test_predict_query_reports_the_tiles():
+    """psvi_predict_query: a small net runs every layer in one tile; 64 rows of
+    350 inputs leave a tile 28 of the first layer's 50 units (whole groups of
+    four, the tile's rows and biases within tile_floats); its refusals."""
+    from psvi.runtime import InnerLoopPlan, _lib, predict_query
+
+    lib = _lib.load()
+    small = InnerLoopPlan("meanfield", [(5, 4), (4, 3)], 3, 7)
+    assert predict_query(small, 1) == dict(rows_per_group=1, tile_floats=24, units_per_tile=[4, 3])
+    assert predict_query(small, 100)["rows_per_group"] == 50      # even shares of at most 64 rows
+    wide = InnerLoopPlan("meanfield", [(350, 50), (50, 3)], 2, 3)
+    q = predict_query(wide, 64)
+    assert q["rows_per_group"] == 64 and q["units_per_tile"] == [28, 3]
+    assert q["tile_floats"] == 28 * 351
+    assert predict_query(wide, 1)["units_per_tile"] == [50, 3]
+    out = (ctypes.c_int64 * 10)()
+    assert lib.psvi_predict_query(None, 1, out) == EINVAL
+    assert lib.psvi_predict_query(small.handle, 1, None) == EINVAL
+    assert lib.psvi_predict_query(small.handle, 0, out) == EINVAL
+    assert lib.psvi_predict_query(InnerLoopPlan("fullcov", [(5, 3)], 4, 7).handle, 1, out) == ESTATE
+    with pytest.raises(ValueError):
+        predict_query(None, 1)
+
+
 def test_header_and_request_struct_agree():
     from psvi.runtime import _lib
 
